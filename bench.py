@@ -5,7 +5,12 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" is one neighbour-list build over positions already resident in HBM (the reference's timing loop,
-make_list.cu:124-127: MakeNeighList(q, N, sync=false) back to back, one device sync at the end).
+make_list.cu:124-127: MakeNeighList(q, N, sync=false) back to back, one device sync at the end).  Exactly --steps
+builds are timed, split into up to --batches batches; ms_per_step is the median batch's time per build.
+
+``--dump-outputs DIR`` writes what the last timed build handed its caller (the half list CSR) as float64 .npy files
+under DIR, at most 64 MB in all: see dump_outputs().  Inputs are generated from fixed seeds, so two runs with the same
+arguments -- of the same or of another build of the project -- can be compared file by file.
 
   N = 1   workload = BASELINE config 2: 1 048 576 particles, rho = 1.0, rc = 3.3, fp32, uniform random box
           (``--workload cfg3 | cfg4 | cfg5`` select the other single-device configurations: rho = 0.5; the
@@ -37,6 +42,53 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
 SIMDS, CLK_HZ, VALU_CYCLES = 256 * 4, 2.4e9, 2.0  # 256 CUs x 4 SIMD-32; a wave64 VALU instruction issues over 2 cycles
 N_PER_GPU = 1 << 20
+MIN_BATCH_STEPS = 10  # fewer batches rather than batches so short that their synchronisation shows in ms_per_step
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files of all ranks together
+DUMP_MAX_ROWS = 1 << 16
+DUMP_SEED = 20240611
+
+
+def dump_outputs(nl, out_dir, rank=0, world=1):
+    """Writes the half list of the last build as float64 arrays (exact: every value is an integer below 2**53).
+
+      summary.npy            [rows, half pairs, list checksum >> 32, list checksum & 0xffffffff]: the device's
+                             order-independent checksum covers the WHOLE pair set
+      rows.npy               the rows sampled: all of them up to DUMP_MAX_ROWS, else a fixed seeded sample (ascending);
+                             trimmed so that their partners fit the byte budget
+      number_of_partners.npy half_number_of_partners() at those rows
+      key_pointer.npy        key_pointer64() at those rows (where each row's partners start in sorted_list)
+      sorted_list.npy        the partners of those rows, row after row, each row ascending: the partners of a row are
+                             a fixed set, their order within the row is not (particles are ranked within their cell by
+                             atomics), so each row is sorted as the reference's harness does (make_list.cpp:120-128)
+
+    With N > 1 ranks every rank writes its own rows (the slab's local list) with the prefix rank<r>_."""
+    import torch
+
+    kp = nl.key_pointer64()
+    nop = nl.half_number_of_partners()
+    sl = nl.sorted_list()
+    n, p = int(nop.numel()), int(sl.numel())
+    cs, _ = nl.list_checksum()
+    budget = DUMP_BYTES // world // 8 - 4 * 32  # float64 values; 128-byte .npy headers
+    k = min(n, DUMP_MAX_ROWS, max(1, int(budget / (3 + p / max(n, 1)) * 0.9)))  # 3 values per row + its partners
+    rows = np.arange(n, dtype=np.int64) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    rows_d = torch.from_numpy(rows).to(kp.device)
+    cnt = nop[rows_d].to(torch.int64).cpu().numpy()
+    start = kp[rows_d].cpu().numpy()
+    keep = int(np.searchsorted(np.cumsum(3 + cnt), budget - 4, side="right"))  # rows whose partners still fit
+    rows, cnt, start, rows_d = rows[:keep], cnt[:keep], start[:keep], rows_d[:keep]
+    cnt_d = torch.from_numpy(cnt).to(kp.device)
+    first = np.cumsum(cnt) - cnt  # where each row's partners go in the dump
+    idx = (torch.repeat_interleave(torch.from_numpy(start - first).to(kp.device), cnt_d)
+           + torch.arange(int(cnt.sum()), device=kp.device, dtype=torch.int64))
+    part = sl[idx].to(torch.int64).cpu().numpy()
+    seg = np.repeat(np.arange(keep, dtype=np.int64), cnt)
+    part = part[np.lexsort((part, seg))]  # ascending within each row, rows kept in place
+    prefix = f"rank{rank}_" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("summary", [n, nl.half_number_of_pairs(), cs >> 32, cs & 0xFFFFFFFF]), ("rows", rows),
+                    ("number_of_partners", cnt), ("key_pointer", start), ("sorted_list", part)):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(q32, box, rc, budget_s=90.0):
@@ -207,11 +259,13 @@ def _stage_table(stages, info, n, p, vec_bytes, pos_bytes, full=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed builds in all (the reference times LOOP = 100 builds, make_list.cu:20,124-132)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batches", type=int, default=7,
-                    help="timed batches of --steps builds each (SURVEY.md section 8d: the reference times LOOP = 100 builds, make_list.cu:20,124-132); "
-                         "ms_per_step is the median batch, min and max are reported next to it")
+                    help=f"the --steps timed builds are split into this many batches of about equal size (fewer where a batch would have "
+                         f"fewer than {MIN_BATCH_STEPS} builds); ms_per_step is the median batch, min and max are reported next to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed builds, write the half list of the last one as float64 .npy files under DIR (dump_outputs)")
     ap.add_argument("--workload", default="auto", choices=["auto", "cfg2", "cfg3", "cfg4", "cfg5", "weak"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cfg4-baseline", action="store_true",
@@ -222,6 +276,8 @@ def main():
                          "kernel, fixed-capacity halo messages over RCCL, unpack, slab build; no host synchronisation per build), or the halo "
                          "exchange by torch.distributed p2p around nl_make_list_slab (md_neighbor_list_amd/slab.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -330,17 +386,21 @@ def main():
     for _ in range(args.warmup):
         step()
     nl.synchronize()  # surfaces any error (capacity, out of box) before timing
-    # every batch: exactly --steps builds between a barrier + device synchronisation on both sides
+    # exactly --steps builds in all; every batch between a barrier + device synchronisation on both sides
+    n_batches = max(1, min(args.batches, args.steps // MIN_BATCH_STEPS))
+    batch_steps = [args.steps // n_batches + (b < args.steps % n_batches) for b in range(n_batches)]
     batch_s = []
-    for _ in range(max(1, args.batches)):
+    for k in batch_steps:
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k):
             step()
         torch.cuda.synchronize()
         fence()
         batch_s.append(time.perf_counter() - t0)
     nl.synchronize()
+    if args.dump_outputs:
+        dump_outputs(nl, args.dump_outputs, rank, world)
 
     npairs_local = nl.half_number_of_pairs()
     cs_local, _ = nl.list_checksum()
@@ -349,7 +409,7 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)  # a batch takes as long as its slowest rank
         dist.all_reduce(p, op=dist.ReduceOp.SUM)
-    batch_ms = sorted(float(x) / args.steps * 1e3 for x in t.tolist())
+    batch_ms = sorted(float(x) / k * 1e3 for x, k in zip(t.tolist(), batch_steps))
     npairs = int(p[0].item())
     checksum = ((int(p[1].item()) << 32) + int(p[2].item())) & ((1 << 64) - 1)  # wrapping sum of the ranks' checksums
     ms_per_step = batch_ms[len(batch_ms) // 2]  # the median batch

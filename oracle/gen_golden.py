@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.npz from the REFERENCE ITSELF (oracle/_ref, compiled from /root/reference).
 
-Run here (where /root/reference exists):   python oracle/gen_golden.py
+Run here (where /root/reference exists):   python oracle/gen_golden.py   [--big | --big-count | --ref-cases]
 Each fixture holds inputs (q, rc, box) and the reference's outputs: number_of_partners, key_pointer and the
 canonical (per-particle ascending, make_list.cpp:120-128) sorted_list, plus npairs and the pair-set hash.
 A fixture is data only; no reference source text is stored.
@@ -92,6 +92,29 @@ def main():
             sorted_list_naive_order=outs["naive"].sorted_list,
         )
         print(f"N={len(q):5d} mesh={mesh} P={h.npairs:7d} hash={h.hash():016x} dup={dup}")
+
+
+# the boxes of tests/test_oracle.py::test_restatement_matches_compiled_reference: (seed, n, box, rc)
+REF_CASES = ((1, 700, (11.0, 12.0, 13.5), 3.3), (2, 2500, (20.0, 20.0, 20.0), 3.3), (3, 900, (9.0, 30.0, 9.5), 2.9))
+
+
+def ref_cases():
+    """tests/golden/ref_cases/uniform_<f32|f64>.npz: the raw output of the -DWITHOUT_LOOP_FUSION and -DLOOP_FUSION
+    builds of the reference on REF_CASES (each in its own visit order), so that the test that pins the restatement to
+    them runs where oracle/_ref cannot be built.  Keys c<k>_q, c<k>_box, c<k>_rc and c<k>_<variant>_<array>."""
+    out_dir = os.path.join(OUT, "ref_cases")
+    os.makedirs(out_dir, exist_ok=True)
+    for dt in (np.float32, np.float64):
+        arrays = {}
+        for c, (seed, n, box, rc) in enumerate(REF_CASES):
+            q, box = inputs.uniform_box(n, dtype=dt, seed=seed, box=box)
+            arrays.update({f"c{c}_q": q, f"c{c}_box": np.array(box, dtype=np.float64), f"c{c}_rc": np.float64(rc)})
+            for v in ("naive", "fused"):
+                h = po.ref_build(q, rc, box, v)[0]
+                arrays.update({f"c{c}_{v}_number_of_partners": h.number_of_partners,
+                               f"c{c}_{v}_key_pointer": h.key_pointer.astype(np.int64), f"c{c}_{v}_sorted_list": h.sorted_list})
+            print(f"ref_cases {np.dtype(dt).name} case {c}: N={n} P={int(arrays[f'c{c}_naive_key_pointer'][-1])}")
+        np.savez_compressed(os.path.join(out_dir, f"uniform_{'f32' if dt == np.float32 else 'f64'}.npz"), **arrays)
 
 
 def big(only=None):
@@ -188,5 +211,7 @@ if __name__ == "__main__":
     elif "--big" in sys.argv:  # optionally: --big name,name  (only those entries, merged into the stored file)
         k = sys.argv.index("--big")
         big(set(sys.argv[k + 1].split(",")) if len(sys.argv) > k + 1 else None)
+    elif "--ref-cases" in sys.argv:
+        ref_cases()
     else:
         main()

@@ -1,7 +1,8 @@
 """CPU tests: the oracle (oracle/nl_oracle.c) is pinned against the reference's outputs.
 
   * every golden fixture under tests/golden/ (generated from the compiled reference by oracle/gen_golden.py)
-  * the compiled reference itself where oracle/_ref exists (raw array equality, WITHOUT_LOOP_FUSION order)
+  * the raw output of the compiled reference on three more boxes, stored under tests/golden/ref_cases/, and the
+    compiled reference itself where oracle/_ref exists (raw array equality, WITHOUT_LOOP_FUSION order)
   * the harness's brute-force definition (make_list.cpp:79-99)
 """
 import json
@@ -54,11 +55,19 @@ def test_bruteforce_agrees_where_cells_are_wider_than_cutoff(name):
 @pytest.mark.parametrize("variant", ["naive", "fused"])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_restatement_matches_compiled_reference(variant, dtype):
-    if not po.ref_available(variant):
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    for seed, n, box, rc in ((1, 700, (11.0, 12.0, 13.5), 3.3), (2, 2500, (20.0, 20.0, 20.0), 3.3), (3, 900, (9.0, 30.0, 9.5), 2.9)):
+    """Against the reference's answers stored in tests/golden/ref_cases/ (oracle/gen_golden.py --ref-cases), and against
+    the compiled reference itself where oracle/_ref exists."""
+    z = np.load(os.path.join(GOLDEN, "ref_cases", f"uniform_{'f32' if dtype == np.float32 else 'f64'}.npz"))
+    for c, (seed, n, box, rc) in enumerate(((1, 700, (11.0, 12.0, 13.5), 3.3), (2, 2500, (20.0, 20.0, 20.0), 3.3),
+                                            (3, 900, (9.0, 30.0, 9.5), 2.9))):
         q, box = inputs.uniform_box(n, dtype=dtype, seed=seed, box=box)
-        r, _, _ = po.ref_build(q, rc, box, variant)
+        assert np.array_equal(q, z[f"c{c}_q"]) and tuple(z[f"c{c}_box"]) == box and float(z[f"c{c}_rc"]) == rc
+        r = po.HalfList(*(z[f"c{c}_{variant}_{a}"] for a in ("number_of_partners", "key_pointer", "sorted_list")))
+        if po.ref_available(variant):
+            live, _, _ = po.ref_build(q, rc, box, variant)
+            assert np.array_equal(live.key_pointer, r.key_pointer)
+            assert np.array_equal(live.number_of_partners, r.number_of_partners)
+            assert np.array_equal(live.sorted_list, r.sorted_list)
         h = po.build(q, rc, box)
         assert np.array_equal(r.key_pointer, h.key_pointer)
         assert np.array_equal(r.number_of_partners, h.number_of_partners)
