@@ -292,6 +292,11 @@ int nl_debug_occupancy(int32_t out[8]); /* LDS per CU/block (KiB), occupancy API
  * info[7] = 1 when the build used the small instances of the COUNT sweep and the expansion (sparse boxes: 2 waves /
  * 1 wave per cell, half the LDS buffer), else 0. */
 int nl_get_build_info(nl_handle_t h, int32_t info[8]);
+/* How the builds of this handle ran: stats[0] = builds run again because a row of x-cells overflowed its bucket in the
+ * one-pass binning, stats[1] = builds run again because cells whose stencil exceeds the LDS buffer were there while the
+ * build had left out the kernels for them, stats[2] = bucket size of the last build's one-pass binning (0: the
+ * two-pass binning), stats[3] = 1 when the last build launched those kernels. */
+int nl_get_build_stats(nl_handle_t h, int64_t stats[4]);
 int nl_last_error(nl_handle_t h);     /* status of the last failed call on this handle */
 int nl_last_hip_error(nl_handle_t h); /* raw hipError_t behind the last NL_ERR_HIP */
 

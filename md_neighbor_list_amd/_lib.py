@@ -56,6 +56,7 @@ PROTOTYPES = {
     "nl_debug_read": (C.c_int, [_P, C.c_void_p, _I32, C.c_int]),
     "nl_debug_occupancy": (C.c_int, [C.POINTER(_I32 * 8)]),
     "nl_get_build_info": (C.c_int, [_P, C.POINTER(_I32 * 8)]),
+    "nl_get_build_stats": (C.c_int, [_P, C.POINTER(_I64 * 4)]),
     "nl_last_error": (C.c_int, [_P]),
     "nl_last_hip_error": (C.c_int, [_P]),
     "nl_profile_stages": (C.c_int, [_P, _P, _I32, _I32, _I32, C.POINTER(_D * NL_NUM_STAGES)]),

@@ -29,6 +29,9 @@ constexpr int META_TOTAL = 18;  // int32 offset of total_lo from the status word
 constexpr int META_FULL27 = 1;  // number of cells the COUNT sweep hands to the batched search (first "ticket" word)
 constexpr int META_FILL_LIST = 10;  // number of cells k_fill_masks hands to k_fill_list ("ticket" word 10)
 constexpr int META_WORDS = 20;
+// k_sweep_list_f32 / k_fill_list are launched until this many builds in a row have been enqueued since one was seen to
+// hand them cells (and always by a build that runs one again)
+constexpr int32_t LIST_QUIET_BUILDS = 4;
 
 }  // namespace
 
@@ -65,6 +68,12 @@ struct nl_handle_s {
   int32_t* blk_base = nullptr;    // [bin_blocks][nrows]
   void* tmp_pos = nullptr;        // particles grouped by row
   int32_t* tmp_row = nullptr;
+  size_t tmp_slots = 0;           // entries of tmp_pos / tmp_row
+  // one-pass binning of a whole build (k_bin_bucket): a bucket of cap_row slots per row of x-cells
+  int32_t* row_cursor = nullptr;  // [my * mz] fill levels of the buckets; zero between builds (k_bin_bucket resets them)
+  int bucket_env = 1;             // NL_BIN_BUCKETS=0: always the two-pass binning (same-box A/B)
+  int32_t bucket_scale = 1;       // cap_row multiplier: doubled when a row has overflowed its bucket
+  bool bucket_off = false;        // the buckets outgrew their memory: the two-pass binning from then on
   int32_t bin_blocks = 0, bin_chunk = 0;
   bool bin_two_level = true;      // NL_BINNING=1 selects the atomic-rank path (k_hash/k_reorder)
   void* base_sorted = nullptr;     // key_pointer of every sorted slot (mask expansion), same width as key_pointer
@@ -120,12 +129,13 @@ struct nl_handle_s {
     const void* q = nullptr;
     const int32_t* gid = nullptr;
     int32_t stride = 0, n_rows = 0, n = 0, z_lo = 0, mzl = 0, slab = 0, list_kind = 0, pbc = 0, offset_width = 0;
+    int32_t cap_row = 0, list = 0;  // the captured binning and search launches (b_cap_row, b_list)
     int64_t capacity = 0;
     uint64_t epoch = 0;
     bool operator==(const GraphKey& o) const {
       return q == o.q && gid == o.gid && stride == o.stride && n_rows == o.n_rows && n == o.n && z_lo == o.z_lo &&
              mzl == o.mzl && slab == o.slab && list_kind == o.list_kind && pbc == o.pbc && offset_width == o.offset_width &&
-             capacity == o.capacity &&
+             cap_row == o.cap_row && list == o.list && capacity == o.capacity &&
              epoch == o.epoch;
     }
   } graph_key;
@@ -136,6 +146,11 @@ struct nl_handle_s {
   hipEvent_t ev[NL_NUM_STAGES + 1] = {};
 
   // state of the last build
+  int32_t b_cap_row = 0;     // this build: k_bin_bucket's bucket size (0: the two-pass binning)
+  bool b_list = true;        // this build launches k_sweep_list_f32 / k_fill_list (if its path has them)
+  int32_t list_quiet = 0;    // builds enqueued since one was seen to hand cells to k_sweep_list_f32 / k_fill_list
+  bool rerun = false;        // the build being enqueued runs one again (finish): two-pass binning, every launch
+  int64_t reruns[2] = {0, 0};  // builds run again: [0] a row overflowed its bucket, [1] cells listed without the launches
   bool built = false, pending = false;
   int32_t n = 0, n_rows = 0;
   int64_t ncell_local = 0;
@@ -338,7 +353,7 @@ template <typename T, bool FULL, bool PBC, typename OFF> void launch_fill_masks(
   if constexpr (sizeof(T) == 4 && !PBC) {
     if (h->b_lean_small && h->fill_small_env) {  // sparse boxes: a wave per cell (its ~19 rows in one batch), ids of half a stream
       hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 24, 1, SweepCfg<T>::CAP / 2>), dim3(ncells_i), dim3(WAVE), 0, s, a);
-      hipLaunchKernelGGL((k_fill_list<T, FULL, PBC>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
+      if (h->b_list) hipLaunchKernelGGL((k_fill_list<T, FULL, PBC>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
       return;
     }
   }
@@ -347,7 +362,7 @@ template <typename T, bool FULL, bool PBC, typename OFF> void launch_fill_masks(
   else
     hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 24>), dim3(ncells_i), dim3(EXPAND_WAVES * WAVE), 0, s, a);
   // cells without masks (a stream of several LDS batches among one-batch neighbours): a second distance search
-  hipLaunchKernelGGL((k_fill_list<T, FULL, PBC>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
+  if (h->b_list) hipLaunchKernelGGL((k_fill_list<T, FULL, PBC>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
 }
 
 template <typename T, bool FULL, bool PBC> void launch_sweep_kind(nl_handle_t h, int mode, hipStream_t s) {
@@ -369,7 +384,7 @@ template <typename T, bool FULL, bool PBC> void launch_sweep_kind(nl_handle_t h,
           // a workgroup per cell, single-batch cells only; the others go on the hand-over list of the batched search
           if (h->b_lean_small) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, 2, LEAN_SMALL_CAP>), dim3(ncells_i), dim3(2 * WAVE), 0, s, a);
           else hipLaunchKernelGGL((k_sweep_lean_f32<FULL>), dim3(ncells_i), dim3(SWEEP_WAVES * WAVE), 0, s, a);
-          hipLaunchKernelGGL((k_sweep_list_f32<FULL>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
+          if (h->b_list) hipLaunchKernelGGL((k_sweep_list_f32<FULL>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
         } else {
           hipLaunchKernelGGL((k_sweep_count_masks_f32<FULL, PBC>), dim3(ncells_i), dim3(SWEEP_WAVES * WAVE), h->dbg_lds_pad, s, a);
         }
@@ -439,11 +454,39 @@ bool rows_margin_ok(nl_handle_t h) {
   return ms / h->rc >= 1.0 + 8.0 * h->m[2] * 5.9604644775390625e-8 + 9.5367431640625e-7;
 }
 
+// Bucket size of the one-pass binning (k_bin_bucket) for a whole build of n particles in my * mzl rows of x-cells, or 0:
+// the two-pass binning.  The mean row plus a Poisson-safe margin (BASELINE config 2: 1165 particles a row, sigma 34:
+// 1712 slots), times bucket_scale; the buckets (re)allocated on first need, at most 4 n_max + 512 slots a row.
+template <typename T> int32_t bucket_cap(nl_handle_t h, int32_t n, int32_t mzl) {
+  const int64_t nrows = (int64_t)h->m[1] * mzl;
+  if (!h->bucket_env || h->bucket_off || !h->bin_two_level || nrows > BIN_MAX_ROWS || h->m[0] > BIN_MAX_MX) return 0;
+  const int64_t cap = (int64_t)h->bucket_scale * ((int64_t)(1.25 * (double)n / (double)nrows) + 256);
+  const size_t slots = (size_t)(nrows * cap) + 16;
+  if (slots > 4 * ((size_t)h->n_max + 16) + 512 * (size_t)nrows) {
+    h->bucket_off = true;
+    return 0;
+  }
+  if (slots > h->tmp_slots) {
+    if (dev_alloc(h, &h->tmp_pos, sizeof(Pos<T>) * slots) || dev_alloc(h, &h->tmp_row, sizeof(int32_t) * slots)) {
+      // no room: the two-pass binning, with the buffers it needs
+      h->bucket_off = true;
+      h->tmp_slots = 0;
+      const size_t n_slots = (size_t)h->n_max + 16;
+      if (dev_alloc(h, &h->tmp_pos, sizeof(Pos<T>) * n_slots) == NL_OK && dev_alloc(h, &h->tmp_row, sizeof(int32_t) * n_slots) == NL_OK)
+        h->tmp_slots = n_slots, h->last_error = NL_OK;
+      return 0;
+    }
+    h->tmp_slots = slots;
+  }
+  return (int32_t)cap;
+}
+
 // What the handle remembers about the build being enqueued (also set when a captured graph of it is replayed): how the
-// later stages, the getters and a refill after growth have to read the buffers.
+// later stages, the getters and a refill after growth have to read the buffers.  whole: a build that finish() can run
+// again (not the two passes of a split slab build, not a distributed one).
 template <typename T>
 void set_build_state(nl_handle_t h, const void* q_dev, int32_t stride, const int32_t* gid, int32_t n, int32_t z_lo,
-                     int32_t mzl, int32_t slab) {
+                     int32_t mzl, int32_t slab, bool whole = true) {
   const int64_t ncl = (int64_t)h->m[0] * h->m[1] * mzl;
   h->ncell_local = ncl;
   h->b_mzl = mzl, h->b_slab = slab, h->b_zlo = z_lo, h->b_stride = stride, h->b_q = q_dev, h->b_gid = gid;
@@ -494,6 +537,12 @@ void set_build_state(nl_handle_t h, const void* q_dev, int32_t stride, const int
   }
   h->b_wide = h->offset_width == 64 || (h->offset_width == 0 && h->capacity > 2147483647LL);
   h->kp_alt_valid = false;
+  // A build that can be run again bins in one pass into row buckets, and leaves out the launches for cells whose stencil
+  // exceeds the LDS buffer once LIST_QUIET_BUILDS builds in a row have been enqueued without such cells being seen;
+  // finish() runs it again without either when a row overflowed its bucket or such a cell was there after all.
+  const bool again_ok = whole && !h->b_dyn && !h->rerun;
+  h->b_list = !again_ok || h->list_quiet < LIST_QUIET_BUILDS;
+  h->b_cap_row = again_ok ? bucket_cap<T>(h, n, mzl) : 0;
 }
 
 template <typename T>
@@ -502,17 +551,17 @@ int enqueue_build(nl_handle_t h, const void* q_dev, int32_t stride, const int32_
                   int32_t n_ghost_lo = 0) {
   const Grid<T> g = make_grid<T>(h, n_rows, z_lo, mzl, slab);
   const int64_t ncl = (int64_t)h->m[0] * h->m[1] * mzl;
-  set_build_state<T>(h, q_dev, stride, gid, h->b_dyn ? h->b_n_est : n, z_lo, mzl, slab);
   const int32_t nbp = (n + 255) / 256;
   const T* q = static_cast<const T*>(q_dev);
 
   const int32_t nrows = h->m[1] * mzl;
   const bool two_level = h->bin_two_level && nrows <= BIN_MAX_ROWS && h->m[0] <= BIN_MAX_MX;
   // One allocation = [cell histogram | status, tickets, total (32 words) | row totals]: one memset node clears
-  // what this build's path needs (histogram + meta, or meta + row totals).
+  // what this build's path needs (histogram + meta, or meta + row totals); the one-pass binning needs none.
   // two binning passes: owned, then ghosts (the persistent sweep, variant 2, has its own cell walk without the guard
   // against an inconsistent cell table: no split there)
   const bool split = part != PART_ALL && two_level && slab;
+  set_build_state<T>(h, q_dev, stride, gid, h->b_dyn ? h->b_n_est : n, z_lo, mzl, slab, !split);
   if (part != PART_ALL && !split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
     if (part == PART_BEGIN) return NL_OK;
     part = PART_ALL;
@@ -546,7 +595,35 @@ int enqueue_build(nl_handle_t h, const void* q_dev, int32_t stride, const int32_
                          static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
                          h->sorted_row, h->sorted_gid, ph);
     };
-    if (!split) {
+    if (!split && h->b_cap_row > 0) {
+      // one pass into the row buckets; k_bin_bucket also starts the meta words and leaves its cursors at zero
+      if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
+      const int32_t blocks = std::max(1, (n + h->bin_chunk - 1) / h->bin_chunk);
+      // (8 particles a thread in registers: 127 VGPRs in fp32; fp64 would spill, and reads its chunk twice instead)
+      bool wide = false;
+      if constexpr (sizeof(T) == 4) {
+        if ((wide = h->bin_chunk >= 8 * BIN_THREADS))
+          hipLaunchKernelGGL((k_bin_bucket<T, 8>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, stride, gid, n, h->bin_chunk, g, nrows,
+                             h->b_cap_row, h->row_cursor, h->row_start, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row, h->status);
+      }
+      if (!wide)
+        hipLaunchKernelGGL((k_bin_bucket<T, 4>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, stride, gid, n, h->bin_chunk, g, nrows,
+                           h->b_cap_row, h->row_cursor, h->row_start, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row, h->status);
+      if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_CELL_SCAN], s));
+      if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_REORDER], s));
+      const BinPhase all = {0, n, nrows, 0, 0, 0, nrows, nrows, -1, nullptr};
+      bool fine = false;
+      if constexpr (sizeof(T) == 4) {
+        if ((fine = h->b_rows))
+          hipLaunchKernelGGL((k_bin_cells<T, true>), dim3(nrows), dim3(256), 0, s, g, nrows, h->row_start,
+                             static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
+                             h->sorted_row, h->sorted_gid, all, h->b_cap_row);
+      }
+      if (!fine)
+        hipLaunchKernelGGL((k_bin_cells<T, false>), dim3(nrows), dim3(256), 0, s, g, nrows, h->row_start,
+                           static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
+                           h->sorted_row, h->sorted_gid, all, h->b_cap_row);
+    } else if (!split) {
       HIPCHK(h, hipMemsetAsync(h->cell_count + h->ncell, 0, sizeof(int32_t) * (size_t)(32 + nrows), s));
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
       const BinPhase all = {0, n, nrows, 0, 0, 0, nrows, nrows, -1, h->b_dyn};
@@ -630,21 +707,44 @@ int grow_list(nl_handle_t h, int64_t need) {
   return NL_OK;
 }
 
+// The last build once more, from its own arguments, with the two-pass binning and every launch of its path; waits for it.
+int run_again(nl_handle_t h) {
+  h->rerun = true;
+  int rc = dispatch_build(h, h->b_q, h->b_stride, h->b_gid, h->n_rows, h->n, h->b_zlo, h->b_mzl, h->b_slab, h->last_stream, nullptr);
+  h->rerun = false;
+  if (!rc) rc = enqueue_result_copy(h, h->last_stream);
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->last_stream));
+  return NL_OK;
+}
+
 // Waits for the pending build; in a synchronous build an undersized list is grown and the fill pass re-run.
 int finish(nl_handle_t h, bool may_grow) {
   if (!h->pending) return h->built ? NL_OK : fail(h, NL_ERR_STATE);
   HIPCHK(h, hipStreamSynchronize(h->last_stream));
   h->pending = false;
   uint32_t st = h->host->status;
+  {
+    // A row past its bucket, or cells handed to k_sweep_list_f32 / k_fill_list by a build that did not launch them: the
+    // build is incomplete (whatever else its status says) and runs again without either shortcut.  An overflowed row
+    // doubles the buckets of later builds, once; a second overflow ends the one-pass binning for this handle.
+    const bool lean = h->b_use_masks && !h->b_rows && h->b_mask_nb == 1;  // (the paths with those two kernels)
+    const bool listed = lean && (h->host->tickets[META_FULL27 - 1] | h->host->tickets[META_FILL_LIST - 1]) != 0;
+    const bool overflow = h->b_cap_row > 0 && (st & ST_ROW_OVERFLOW);
+    if (listed) h->list_quiet = 0;
+    if (overflow || (listed && !h->b_list)) {
+      if (overflow) h->reruns[0]++, h->bucket_scale *= 2;
+      else h->reruns[1]++;
+      if (int rc = run_again(h)) return rc;
+      st = h->host->status;
+    }
+  }
   if ((st & ST_INDEX_OVERFLOW) && !(st & ~(ST_CAPACITY | ST_INDEX_OVERFLOW)) && may_grow && !h->b_wide && h->offset_width == 0) {
     // more than INT32_MAX entries in a build with 32-bit offsets: the list grows past that size, which makes builds of
     // this handle wide (64-bit key_pointer), and the whole build runs again
     int rc = grow_list(h, h->host->total());
     if (rc) return rc;
-    rc = dispatch_build(h, h->b_q, h->b_stride, h->b_gid, h->n_rows, h->n, h->b_zlo, h->b_mzl, h->b_slab, h->last_stream, nullptr);
-    if (!rc) rc = enqueue_result_copy(h, h->last_stream);
-    if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->last_stream));
+    if ((rc = run_again(h))) return rc;
     st = h->host->status;
   } else if ((st & ST_CAPACITY) && !(st & ~ST_CAPACITY) && may_grow) {
     int rc = grow_list(h, h->host->total());
@@ -866,6 +966,7 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
     if (const char* v = getenv("NL_FILL_SMALL")) h->fill_small_env = atoi(v) != 0;
     if (const char* v = getenv("NL_OFFSET_WIDTH")) h->offset_width = atoi(v) == 64 ? 64 : atoi(v) == 32 ? 32 : 0;
     if (const char* v = getenv("NL_BINNING")) h->bin_two_level = atoi(v) != 1;
+    if (const char* v = getenv("NL_BIN_BUCKETS")) h->bucket_env = atoi(v) != 0;
     if (const char* v = getenv("NL_GRAPH")) h->use_graph = atoi(v) != 0;
     if (const char* v = getenv("NL_DEBUG_FLAGS")) h->dbg_flags = atoi(v);
     if (const char* v = getenv("NL_DEBUG_WG_PER_CU")) h->dbg_wg_per_cu = std::max(1, atoi(v));
@@ -879,7 +980,7 @@ int nl_destroy(nl_handle_t h) {
   if (!h) return NL_ERR_ARG;
   (void)hipSetDevice(h->device);
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
-  void* bufs[] = {h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
+  void* bufs[] = {h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
                   h->cell_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -909,6 +1010,9 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   if ((rc = dev_alloc(h, &h->sorted_row, 4 * (n + 64)))) return rc;  // (+64: k_fill_masks reads whole row batches)
   if ((rc = dev_alloc(h, &h->sorted_gid, 4 * (n + 16)))) return rc;
   if ((rc = dev_alloc(h, &h->count, 4 * (n + 32)))) return rc;
+  // (zero once: a build that leaves out k_sweep_list_f32 -- and then runs again -- scans the stale counts of the cells it
+  // listed, which must be counts of earlier builds, never garbage)
+  HIPCHK(h, hipMemset(h->count, 0, 4 * (n + 32)));
   if ((rc = dev_alloc(h, &h->key_pointer, 8 * (n + 32)))) return rc;  // int32 or int64 offsets (b_wide)
   if (h->kp_alt) (void)hipFree(h->kp_alt), h->kp_alt = nullptr;
   h->kp_alt_valid = false;
@@ -928,6 +1032,9 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
     if ((rc = dev_alloc(h, &h->blk_base, 4 * (nrows * (size_t)h->bin_blocks + 16)))) return rc;
     if ((rc = dev_alloc(h, &h->tmp_pos, pos_bytes * (n + 16)))) return rc;
     if ((rc = dev_alloc(h, &h->tmp_row, 4 * (n + 16)))) return rc;
+    h->tmp_slots = n + 16;  // (the buckets of the one-pass binning grow them on first use)
+    if ((rc = dev_alloc(h, &h->row_cursor, 4 * (nrows + 16)))) return rc;
+    HIPCHK(h, hipMemset(h->row_cursor, 0, 4 * (nrows + 16)));
   }
   if (h->sweep_variant >= 3) {
     if ((rc = dev_alloc(h, &h->masks, (size_t)MASK_ROW_BYTES * (n + 64)))) return rc;
@@ -1055,17 +1162,19 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
     return NL_OK;
   }
   if (h->use_graph && part == PART_ALL) {
+    // The handle's per-build state first (on replay: the captured build's, whatever ran in between): it picks the
+    // launches the graph holds.  Whatever the build has to allocate -- the mask rows of a first dense build, the row
+    // buckets -- is allocated here, before a capture.
+    if (h->dtype == NL_F32) set_build_state<float>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
+    else set_build_state<double>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
     nl_handle_s::GraphKey key;
     key.q = q_dev, key.gid = gid_dev, key.stride = q_stride, key.n_rows = n_rows, key.n = n, key.z_lo = z_lo, key.mzl = mzl;
     key.slab = slab, key.list_kind = h->list_kind, key.pbc = h->pbc ? 1 : 0, key.capacity = h->capacity;
     key.epoch = h->buffers_epoch, key.offset_width = h->offset_width;
+    key.cap_row = h->b_cap_row, key.list = h->b_list ? 1 : 0;
     if (!h->graph_exec || !(key == h->graph_key)) {
       if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec), h->graph_exec = nullptr;
       if (h->graph) (void)hipGraphDestroy(h->graph), h->graph = nullptr;
-      // (whatever the build has to allocate -- the mask rows of a first dense build -- is allocated before the capture)
-      if (h->dtype == NL_F32) set_build_state<float>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
-      else set_build_state<double>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
-      key.epoch = h->buffers_epoch;
       // captured on the private stream (the null stream cannot be captured); replayed on the caller's stream
       HIPCHK(h, hipStreamBeginCapture(h->own_stream, hipStreamCaptureModeRelaxed));
       rc = dispatch_build(h, q_dev, q_stride, gid_dev, n_rows, n, z_lo, mzl, slab, h->own_stream, nullptr);
@@ -1081,10 +1190,6 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
       HIPCHK(h, hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
       h->graph_key = key;
     }
-    else {  // replay: the handle's per-build state is the captured build's, whatever ran in between
-      if (h->dtype == NL_F32) set_build_state<float>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
-      else set_build_state<double>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
-    }
     HIPCHK(h, hipGraphLaunch(h->graph_exec, s));
   } else {
     rc = dispatch_build(h, q_dev, q_stride, gid_dev, n_rows, n, z_lo, mzl, slab, s, nullptr, part, n_ghost_lo);
@@ -1094,6 +1199,7 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
   }
   h->last_stream = s;
   h->pending = true;
+  if (h->list_quiet < LIST_QUIET_BUILDS) h->list_quiet++;
   if (sync) return finish(h, true);
   return NL_OK;
 }
@@ -1296,6 +1402,15 @@ int nl_get_build_info(nl_handle_t h, int32_t info[8]) {
   info[1] = h->sweep_variant;
   info[2] = h->dtype == NL_F32 ? SweepCfg<float>::CAP : SweepCfg<double>::CAP;
   info[3] = h->num_cus;
+  return NL_OK;
+}
+
+int nl_get_build_stats(nl_handle_t h, int64_t stats[4]) {
+  if (!h || !stats) return NL_ERR_ARG;
+  stats[0] = h->reruns[0];
+  stats[1] = h->reruns[1];
+  stats[2] = h->b_cap_row;
+  stats[3] = h->b_list ? 1 : 0;
   return NL_OK;
 }
 

@@ -24,7 +24,9 @@ namespace nl {
 constexpr int WAVE = 64;
 
 // bits of the device status word
-enum : uint32_t { ST_OUT_OF_BOX = 1u, ST_CAPACITY = 2u, ST_DOMAIN = 4u, ST_INDEX_OVERFLOW = 8u };
+// (ST_ROW_OVERFLOW: a row of x-cells held more particles than its bucket in k_bin_bucket; the host runs the build
+// again with the two-pass binning)
+enum : uint32_t { ST_OUT_OF_BOX = 1u, ST_CAPACITY = 2u, ST_DOMAIN = 4u, ST_INDEX_OVERFLOW = 8u, ST_ROW_OVERFLOW = 16u };
 
 // One cell-sorted particle. gid = the id written into neighbour rows and used for the i<j half-list rule.
 template <typename T> struct Pos;
@@ -468,6 +470,41 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_rows(const T* __restrict__ 
   }
 }
 
+// The UNROLL particles i0 + u * BIN_THREADS (clamped to end - 1) of one trip of a binning block: position and id, all
+// loads in flight together.  Three loops, one per id source, each free of branches between its loads: a load under a
+// branch is waited for at the join (one memory round trip per particle instead of one per trip).
+template <typename T, int UNROLL>
+__device__ __forceinline__ void bin_load_trip(const T* __restrict__ q, int32_t stride, const int32_t* __restrict__ gid,
+                                              int32_t i0, int32_t end, int32_t dbg, T* x, T* y, T* z, int32_t* id) {
+  if (gid == reinterpret_cast<const int32_t*>(1)) {  // NL_GID_IN_W: the id travels in the w component
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      const int32_t i = min(i0 + u * BIN_THREADS, end - 1);
+      load_xyz(q, stride, i, x[u], y[u], z[u]);
+      if constexpr (sizeof(T) == 4) id[u] = __float_as_int(q[(size_t)i * 4 + 3]);
+      else id[u] = (int32_t)__double_as_longlong(q[(size_t)i * 4 + 3]);
+    }
+  } else if (gid) {
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      const int32_t i = min(i0 + u * BIN_THREADS, end - 1);
+      load_xyz(q, stride, i, x[u], y[u], z[u]);
+      id[u] = gid[i];
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      const int32_t i = min(i0 + u * BIN_THREADS, end - 1);
+      load_xyz(q, stride, i, x[u], y[u], z[u]);
+      id[u] = i;
+    }
+  }
+  if (!(dbg & 512)) {
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) keep_in_flight(x[u]), keep_in_flight(y[u]), keep_in_flight(z[u]), keep_in_flight(id[u]);
+  }
+}
+
 // UNROLL: particles per thread whose loads are in flight together: 8 where a chunk is 8 particles per thread (one round
 // trip per chunk: binning 2 + 3 at cfg 2 41.6 -> 38.1 us), 4 for the smaller chunks of small boxes.  (k_bin_rows is
 // 1 us slower with 8.)
@@ -515,39 +552,10 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(const T* __restrict
   __syncthreads();
   const int32_t i_end = ph.dyn ? min(ph.i_end, g.n_rows + ph.dyn[0] + ph.dyn[1]) : ph.i_end;
   const int32_t beg = ph.i_beg + blockIdx.x * chunk, end = min(beg + chunk, i_end);
-  const bool gid_in_w = gid == reinterpret_cast<const int32_t*>(1);  // NL_GID_IN_W: the id travels in the w component
   for (int32_t i0 = beg + tid; i0 < end; i0 += UNROLL * BIN_THREADS) {  // all loads of a trip first (see k_bin_rows)
     T x[UNROLL], y[UNROLL], z[UNROLL];
     int32_t id[UNROLL];
-    // three loops, one per id source, each free of branches between its loads: a load under a branch is waited for at
-    // the join (one memory round trip per particle instead of one per trip)
-    if (gid_in_w) {
-#pragma unroll
-      for (int u = 0; u < UNROLL; u++) {
-        const int32_t i = min(i0 + u * BIN_THREADS, end - 1);
-        load_xyz(q, stride, i, x[u], y[u], z[u]);
-        if constexpr (sizeof(T) == 4) id[u] = __float_as_int(q[(size_t)i * 4 + 3]);
-        else id[u] = (int32_t)__double_as_longlong(q[(size_t)i * 4 + 3]);
-      }
-    } else if (gid) {
-#pragma unroll
-      for (int u = 0; u < UNROLL; u++) {
-        const int32_t i = min(i0 + u * BIN_THREADS, end - 1);
-        load_xyz(q, stride, i, x[u], y[u], z[u]);
-        id[u] = gid[i];
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < UNROLL; u++) {
-        const int32_t i = min(i0 + u * BIN_THREADS, end - 1);
-        load_xyz(q, stride, i, x[u], y[u], z[u]);
-        id[u] = i;
-      }
-    }
-    if (!(g.dbg & 512)) {
-#pragma unroll
-      for (int u = 0; u < UNROLL; u++) keep_in_flight(x[u]), keep_in_flight(y[u]), keep_in_flight(z[u]), keep_in_flight(id[u]);
-    }
+    bin_load_trip<T, UNROLL>(q, stride, gid, i0, end, g.dbg, x, y, z, id);
 #pragma unroll
     for (int u = 0; u < UNROLL; u++) {
       const int32_t i = i0 + u * BIN_THREADS;
@@ -569,6 +577,147 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(const T* __restrict
   }
 }
 
+// Meta words (int32 offsets from the status word; the words 1 .. 16 are the tickets of the search and expansion
+// kernels) that k_bin_bucket keeps between its blocks.  Both are zero between builds.
+constexpr int META_BIN_STATUS = 20;  // status bits the blocks of k_bin_bucket raise
+constexpr int META_BIN_DONE = 21;    // blocks of k_bin_bucket through with their reservations
+
+// k_bin_rows + k_bin_scatter in ONE pass over the positions, for a whole build: every row of x-cells has a bucket of
+// cap_row slots in tmp[] / tmp_row[] (row r from r * cap_row).  A block takes its chunk's row histogram in LDS (the
+// returning LDS atomic is a particle's rank in its row within the chunk), reserves its range in each row with one
+// device-scope atomic per (block, row) on row_cursor[r], and writes its particles into the buckets; the order of the
+// particles of a row is the order of the reservations (k_bin_cells sorts them by cell).  A row past cap_row drops
+// what does not fit and raises ST_ROW_OVERFLOW: the host runs the build again with the two-pass binning.
+// The last block through with its reservations (a ticket in META_BIN_DONE) turns the row totals into row_start (rows
+// packed as the two-pass binning places them), sets the cursors back to zero for the next build and starts the
+// build's meta words: status = what the binning raised, tickets zero.  No memset per build; graph replays included.
+// Chunks of more than UNROLL particles per thread read their positions twice (the histogram, then the placement).
+template <typename T, int UNROLL>
+__global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict__ q, int32_t stride,
+                                                            const int32_t* __restrict__ gid, int32_t n, int32_t chunk,
+                                                            Grid<T> g, int32_t nrows, int32_t cap_row,
+                                                            int32_t* __restrict__ row_cursor, int32_t* __restrict__ row_start,
+                                                            Pos<T>* __restrict__ tmp, int32_t* __restrict__ tmp_row,
+                                                            uint32_t* __restrict__ status) {
+  __shared__ int32_t slot[BIN_MAX_ROWS];  // the chunk's row histogram, then its first slot in every row's bucket
+  __shared__ int32_t wsum[BIN_THREADS / WAVE];
+  __shared__ uint32_t flags_s;
+  __shared__ int32_t last_s;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int32_t r = tid; r < nrows; r += BIN_THREADS) slot[r] = 0;
+  if (tid == 0) flags_s = 0;
+  __syncthreads();
+  const int32_t beg = blockIdx.x * chunk, end = min(beg + chunk, n);
+  const bool keep = end - beg <= UNROLL * BIN_THREADS;  // one trip: the particles stay in registers until they are placed
+  T x[UNROLL], y[UNROLL], z[UNROLL];
+  int32_t id[UNROLL], row[UNROLL], rank[UNROLL];
+#pragma unroll
+  for (int u = 0; u < UNROLL; u++) row[u] = -1, rank[u] = 0;
+  // the row of a particle (-1: rejected, its status bit noted); minimum-image mode: y and z moved to their image
+  // (x keeps its value until k_bin_cells has derived the x-cell from it)
+  auto classify = [&](int32_t i, T& xi, T& yi, T& zi, uint32_t& fl) {
+    int32_t lz = 0, r = 0;
+    T sh[3];
+    const int32_t c = local_cell(g, xi, yi, zi, &lz, &r, sh);
+    if (c < 0) {
+      fl |= c == -1 ? ST_OUT_OF_BOX : ST_DOMAIN;
+      return -1;
+    }
+    if (g.slab) {
+      const bool in_owned_layer = lz >= 1 && lz < g.mzl - 1;
+      if (in_owned_layer != (i < g.n_rows)) fl |= ST_DOMAIN;
+    }
+    if (g.pbc) yi = add_rn(yi, sh[1]), zi = add_rn(zi, sh[2]);
+    return r;
+  };
+  uint32_t fl = 0;
+  for (int32_t i0 = beg + tid; i0 < end; i0 += UNROLL * BIN_THREADS) {
+    bin_load_trip<T, UNROLL>(q, stride, gid, i0, end, g.dbg, x, y, z, id);
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      const int32_t i = i0 + u * BIN_THREADS;
+      row[u] = i < end ? classify(i, x[u], y[u], z[u], fl) : -1;
+      if (row[u] >= 0) rank[u] = atomicAdd(&slot[row[u]], 1);
+    }
+  }
+  if (fl) atomicOr(&flags_s, fl);
+  __syncthreads();
+  for (int32_t r = tid; r < nrows; r += BIN_THREADS) {
+    const int32_t h = slot[r];
+    if (h) {
+      const int32_t b = atomicAdd(&row_cursor[r], h);
+      if (b + h > cap_row) atomicOr(&flags_s, ST_ROW_OVERFLOW);
+      slot[r] = b;
+    }
+  }
+  __syncthreads();  // (every reservation has returned: it is done)
+  if (tid == 0) {
+    if (flags_s) atomicOr(status + META_BIN_STATUS, flags_s);
+    __builtin_amdgcn_s_waitcnt(0);  // the status bits are in before the ticket
+    last_s = atomicAdd(reinterpret_cast<int32_t*>(status) + META_BIN_DONE, 1) == (int32_t)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (last_s) {  // every block has reserved: the cursors hold the row totals
+    const int32_t K = (nrows + BIN_THREADS - 1) / BIN_THREADS;
+    const int32_t b = min(tid * K, nrows), e = min(b + K, nrows);
+    auto total_of = [&](int32_t r) {
+      return min(__hip_atomic_load(&row_cursor[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), cap_row);
+    };
+    int32_t ssum = 0;
+    for (int32_t i = b; i < e; i++) ssum += total_of(i);
+    const int32_t inc = wave_incl_scan(ssum, lane);
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int32_t woff = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < BIN_THREADS / WAVE; k++) {
+      const int32_t v = wsum[k];
+      woff += k < w ? v : 0;
+      all += v;
+    }
+    int32_t run = woff + inc - ssum;
+    for (int32_t i = b; i < e; i++) {
+      row_start[i] = run;
+      run += total_of(i);
+      __hip_atomic_store(&row_cursor[i], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid == 0) {
+      row_start[nrows] = all;
+      int32_t* meta = reinterpret_cast<int32_t*>(status);
+      status[0] = (uint32_t)__hip_atomic_load(meta + META_BIN_STATUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int k = 1; k <= 17; k++) meta[k] = 0;  // tickets (and the pad word)
+      __hip_atomic_store(meta + META_BIN_STATUS, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(meta + META_BIN_DONE, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  auto put = [&](int32_t r, int32_t dst, int32_t i, T xi, T yi, T zi, int32_t idi) {
+    if (dst >= cap_row) return;  // (ST_ROW_OVERFLOW is raised)
+    Pos<T> p;
+    p.x = xi, p.y = yi, p.z = zi;
+    p.gid = idi;
+    if constexpr (sizeof(T) == 8) p.row = i;
+    const size_t k = (size_t)r * cap_row + dst;
+    tmp[k] = p;
+    tmp_row[k] = i;
+  };
+  if (keep) {
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++)
+      if (row[u] >= 0) put(row[u], slot[row[u]] + rank[u], beg + tid + u * BIN_THREADS, x[u], y[u], z[u], id[u]);
+    return;
+  }
+  for (int32_t i0 = beg + tid; i0 < end; i0 += UNROLL * BIN_THREADS) {
+    bin_load_trip<T, UNROLL>(q, stride, gid, i0, end, g.dbg, x, y, z, id);
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      const int32_t i = i0 + u * BIN_THREADS;
+      uint32_t unused = 0;
+      const int32_t r = i < end ? classify(i, x[u], y[u], z[u], unused) : -1;
+      if (r >= 0) put(r, atomicAdd(&slot[r], 1), i, x[u], y[u], z[u], id[u]);
+    }
+  }
+}
+
 // FINE (nl_rows.hpp, fp32 open box): the row's particles are sorted by (quarter of the cell along z, x-cell) instead of
 // the x-cell alone: the row of x-cells becomes four FINE ROWS, each contiguous in x, and the table written is
 // fine_start[(r * mx + cx) * 4 + qz] (4 M + 1 entries) in the place of cell_start.  The quarter a particle lies in
@@ -581,7 +730,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
                                                    const Pos<T>* __restrict__ tmp, const int32_t* __restrict__ tmp_row,
                                                    int32_t* __restrict__ cell_start, Pos<T>* __restrict__ sorted,
                                                    int32_t* __restrict__ sorted_row, int32_t* __restrict__ sorted_gid,
-                                                   BinPhase ph) {
+                                                   BinPhase ph, int32_t cap_row = 0) {
   __shared__ int32_t cnt[FINE ? 4 * BIN_FINE_MAX_MX : BIN_MAX_MX];
   __shared__ int32_t wsum[4];
   __shared__ int32_t carry_s;
@@ -590,6 +739,9 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
   const int32_t nb = FINE ? 4 * mx : mx;  // bins of the row
   const int32_t r = bx < ph.cells_n0 ? ph.cells_row0 + bx : ph.cells_row1 + (bx - ph.cells_n0);
   const int32_t beg = row_start[r], end = row_start[r + 1];
+  // cap_row > 0 (k_bin_bucket): the row's particles are at the front of its bucket, tmp[r * cap_row ...]
+  const Pos<T>* __restrict__ src = cap_row ? tmp + ((int64_t)r * cap_row - beg) : tmp;
+  const int32_t* __restrict__ src_row = cap_row ? tmp_row + ((int64_t)r * cap_row - beg) : tmp_row;
   for (int32_t c = tid; c < nb; c += 256) cnt[c] = 0;
   if (tid == 0) carry_s = 0;
   __syncthreads();
@@ -622,8 +774,8 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
 #pragma unroll
     for (int u = 0; u < BC_KEEP; u++) {
       const int32_t k = min(beg + tid + u * 256, end - 1);
-      pk[u] = tmp[k];
-      rk[u] = tmp_row[k];
+      pk[u] = src[k];
+      rk[u] = src_row[k];
     }
 #pragma unroll
     for (int u = 0; u < BC_KEEP; u++) {
@@ -634,7 +786,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
     for (int u = 0; u < BC_KEEP; u++)
       if (beg + tid + u * 256 < end) atomicAdd(&cnt[bin_of(pk[u])], 1);
   } else {
-    for (int32_t k = beg + tid; k < end; k += 256) atomicAdd(&cnt[bin_of(tmp[k])], 1);
+    for (int32_t k = beg + tid; k < end; k += 256) atomicAdd(&cnt[bin_of(src[k])], 1);
   }
   __syncthreads();
   // exclusive scan of cnt[0..nb) in place, 256 entries at a time, and the row's slice of cell_start
@@ -677,7 +829,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
     for (int u = 0; u < BC_KEEP; u++)
       if (beg + tid + u * 256 < end) place(pk[u], rk[u]);
   } else {
-    for (int32_t k = beg + tid; k < end; k += 256) place(tmp[k], tmp_row[k]);
+    for (int32_t k = beg + tid; k < end; k += 256) place(src[k], src_row[k]);
   }
 }
 

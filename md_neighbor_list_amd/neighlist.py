@@ -328,6 +328,14 @@ class NeighListGPU:
                 "offset_bits": int(info[4]), "mask_rows": int(info[5]), "fine_rows": int(info[6]),
                 "small_cells": int(info[7])}
 
+    def build_stats(self):
+        """{'row_overflow_reruns', 'list_reruns', 'cap_row', 'list_launched'}: builds of this handle run again (a row
+        past its bucket; cells for the list kernels while those were left out) and how the last build ran."""
+        st = (C.c_int64 * 4)()
+        check(self._lib.nl_get_build_stats(self._h, C.byref(st)), "nl_get_build_stats")
+        return {"row_overflow_reruns": int(st[0]), "list_reruns": int(st[1]), "cap_row": int(st[2]),
+                "list_launched": bool(st[3])}
+
     def profile_last_build(self, reps=10):
         """Same for the last build (also a slab build); its position/id tensors are kept alive by this object."""
         ms = (C.c_double * _lib.NL_NUM_STAGES)()
