@@ -199,6 +199,35 @@ int nl_distributed_ghosts(nl_comm_t comm, int32_t* n_ghost_lo, int32_t* n_ghost_
  * checkCudaErrors(cudaDeviceSynchronize()), make_list.cu:128). */
 int nl_synchronize(nl_handle_t h);
 
+/* ------------------------------------------------------------------------------------ Verlet-skin updates */
+
+/* The Verlet part of the Verlet list (no reference counterpart: its harnesses only build).  The
+ * handle's cut-off is rc = the physical cut-off + skin; a list stays valid until some particle has moved more than
+ * skin / 2 since its build.  nl_update_list decides that on the device and rebuilds only then, in stream order and with
+ * no host involvement, so that an MD step (integrate, nl_update_list, nl_lj_forces_enqueue) can be enqueued ahead and
+ * captured into a graph.
+ *   nl_set_skin: skin >= 0 (default 0: every particle that moved at all triggers a build); forces the next update to build.
+ *   nl_update_list: builds as nl_make_list does (the same list) exactly when
+ *     (a) the host knows a reason: no list of an update to keep (first update; nl_initialize, nl_set_list_kind,
+ *         nl_set_periodic, nl_set_offset_width, nl_set_capacity, nl_set_skin or nl_resort called, or a build other than
+ *         an update's run, since; the host has seen the last build fail) or q_dev, q_stride or n differ from that build's;
+ *     (b) the status word of the last performed build is not OK (an asynchronous build that overflowed its capacity);
+ *     (c) for some particle i < n, with d = q_now - snap per component in the position type (round to nearest, no
+ *         contraction), dd = (double)d, folded to the minimum image after nl_set_periodic(1) (dd -= L rint(dd / L)),
+ *         r2 = (ddx^2 + ddy^2) + ddz^2 in double without FMA is NaN or > (skin / 2)^2.  snap = the caller's positions
+ *         at the last build an update performed, in input order.
+ *   Otherwise nothing changes, on the device or the host: the getters, nl_lj_forces and nl_resort see the last build.
+ *   sync != 0 behaves like nl_make_list(sync = 1) (grows the list on capacity overflow, returns the status); sync == 0
+ *   only enqueues.  An update's build never needs a host re-run (two-pass binning, every launch of its path).  With
+ *   nl_set_graph(1) the whole chain (check, gated build, snapshot, result copy) is replayed from one graph.  On a stream
+ *   the caller is capturing, an update enqueues plain launches; one that the host would have to force (first build,
+ *   growth) or that would wait for another stream is NL_ERR_STATE there.  Slab and distributed builds have no update.
+ *   nl_get_update_stats: stats[0] = updates enqueued, stats[1] = builds they performed (device counters, including the
+ *   replays of captured updates); waits for the device. */
+int nl_set_skin(nl_handle_t h, double skin);
+int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, void* stream, int sync);
+int nl_get_update_stats(nl_handle_t h, int64_t stats[2]);
+
 /* ------------------------------------------------------------------------------------------------- results */
 
 /* The CPU class's accessors (neighlist_cpu.hpp:437-463): key_pointer()[N+1], sorted_list()[P],
@@ -269,6 +298,12 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream);
  * waits for the build first. */
 int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
                  void* f_dev, void* stream);
+/* nl_lj_forces without the wait: stream-ordered behind the last nl_update_list, which must have been enqueued on the same
+ * stream (or behind a build that has been synchronised); a pending plain asynchronous build is NL_ERR_STATE.
+ * rc_force <= rc - skin (what a list reused within the skin guarantees), else NL_ERR_ARG.  Where the build's status word
+ * says the list is invalid the forces are NaN; the error itself surfaces at the next nl_synchronize. */
+int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
+                         void* f_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------- introspection */
 

@@ -49,6 +49,10 @@ PROTOTYPES = {
     "nl_get_cell_order": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I32)]),
     "nl_resort": (C.c_int, [_P, _P, _SZ, _P]),
     "nl_lj_forces": (C.c_int, [_P, _P, _I32, _D, _D, _D, _P, _P]),
+    "nl_lj_forces_enqueue": (C.c_int, [_P, _P, _I32, _D, _D, _D, _P, _P]),
+    "nl_set_skin": (C.c_int, [_P, _D]),
+    "nl_update_list": (C.c_int, [_P, _P, _I32, _I32, _P, C.c_int]),
+    "nl_get_update_stats": (C.c_int, [_P, C.POINTER(_I64 * 2)]),
     "nl_get_full_transposed": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I32)]),
     "nl_number_of_pairs": (C.c_int, [_P, C.POINTER(_I64)]),
     "nl_get_mesh": (C.c_int, [_P, C.POINTER(_I32 * 3), C.POINTER(_I64)]),

@@ -130,12 +130,14 @@ struct nl_handle_s {
     const int32_t* gid = nullptr;
     int32_t stride = 0, n_rows = 0, n = 0, z_lo = 0, mzl = 0, slab = 0, list_kind = 0, pbc = 0, offset_width = 0;
     int32_t cap_row = 0, list = 0;  // the captured binning and search launches (b_cap_row, b_list)
+    int32_t update = 0;             // 1: nl_update_list's chain (check, gated build, snapshot, result copy)
+    double skin = 0;                // ... and the skin its check was captured with
     int64_t capacity = 0;
     uint64_t epoch = 0;
     bool operator==(const GraphKey& o) const {
       return q == o.q && gid == o.gid && stride == o.stride && n_rows == o.n_rows && n == o.n && z_lo == o.z_lo &&
              mzl == o.mzl && slab == o.slab && list_kind == o.list_kind && pbc == o.pbc && offset_width == o.offset_width &&
-             cap_row == o.cap_row && list == o.list && capacity == o.capacity &&
+             cap_row == o.cap_row && list == o.list && update == o.update && skin == o.skin && capacity == o.capacity &&
              epoch == o.epoch;
     }
   } graph_key;
@@ -169,6 +171,17 @@ struct nl_handle_s {
   const int32_t* b_dyn = nullptr;
   int32_t b_n_est = 0;             // particles expected (owned + the previous build's ghosts): path selection only
   const int32_t* dyn_host = nullptr;
+
+  // nl_update_list (nl_skin.inc): the Verlet-skin rebuild decision on the device
+  double skin = 0;                 // nl_set_skin
+  const uint32_t* gate = nullptr;  // while an update's build is enqueued: k_skin_check's `go` word (every launch waits on it)
+  void* snap = nullptr;            // the caller's positions at the last build an update performed (input order, q's stride)
+  size_t snap_bytes = 0;
+  uint32_t* skin_words = nullptr;  // [go, over, ticket, pad, updates (u64), builds (u64)] (SKIN_* in nl_skin.inc)
+  bool upd_valid = false;          // the last build was an update's, and nothing that forces a build happened since
+  bool last_update = false;        // the build enqueued last is an update's (complete without finish())
+  const void* upd_q = nullptr;     // positions, stride and n of that build
+  int32_t upd_stride = 0, upd_n = 0;
 };
 
 namespace {
@@ -228,6 +241,7 @@ template <typename T> Grid<T> make_grid(nl_handle_t h, int32_t n_rows, int32_t z
   g.dbg = h->dbg_flags;
   g.z_first = slab ? z_lo - 1 : 0;
   for (int d = 0; d < 3; d++) g.L[d] = (T)h->L[d];
+  g.gate = h->gate;
   return g;
 }
 
@@ -242,13 +256,13 @@ int launch_scan(nl_handle_t h, const int32_t* in, int64_t n, OFF* out, int64_t* 
     return NL_OK;
   }
   if (n <= SCAN_SMALL_MAX) {  // one launch instead of three (totals of such short arrays fit int32)
-    hipLaunchKernelGGL(k_scan_small<OFF>, dim3(1), dim3(1024), 0, s, in, (int32_t)n, total, out, total_split);
+    hipLaunchKernelGGL(k_scan_small<OFF>, dim3(1), dim3(1024), 0, s, in, (int32_t)n, total, out, total_split, h->gate);
     return NL_OK;
   }
   const int32_t nb = (int32_t)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
   if (nb > h->scan_blocks) return fail(h, NL_ERR_ARG);  // (sized for max(n_max, cells) in nl_reserve)
   hipLaunchKernelGGL(k_scan_chained<OFF>, dim3(nb), dim3(SCAN_THREADS), 0, s, in, n, h->scan_look, h->scan_blocks, total, out,
-                     h->status, total_split);
+                     h->status, total_split, h->gate);
   return NL_OK;
 }
 
@@ -294,6 +308,7 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.z_origin = h->b_slab ? h->b_zlo - 1 : 0;
   a.dbg = h->dbg_flags;
   a.dbg_buf = h->dbg_buf;
+  a.gate = h->gate;
   return a;
 }
 
@@ -316,6 +331,7 @@ RowsArgs rows_args(nl_handle_t h) {
   a.over_count = reinterpret_cast<int32_t*>(h->status) + META_FULL27;
   a.wide = h->b_wide ? 1 : 0;
   a.dbg_buf = h->dbg_buf;
+  a.gate = h->gate;
   return a;
 }
 
@@ -343,7 +359,7 @@ template <typename T, bool FULL, bool PBC, typename OFF> void launch_fill_masks(
     const int32_t nbp = (h->n + 255) / 256;
     if (h->n > 0)
       hipLaunchKernelGGL(k_row_base<OFF>, dim3(nbp), dim3(256), 0, s, static_cast<const OFF*>(h->key_pointer), h->sorted_row,
-                         h->n_rows, h->n, static_cast<OFF*>(h->base_sorted));
+                         h->n_rows, h->n, static_cast<OFF*>(h->base_sorted), h->gate);
     hipLaunchKernelGGL((k_fill_dense<T, FULL, PBC, OFF>), dim3(ncells_i), dim3(FD_WAVES * WAVE), 0, s, a,
                        static_cast<const OFF*>(h->base_sorted));
     return;
@@ -624,7 +640,8 @@ int enqueue_build(nl_handle_t h, const void* q_dev, int32_t stride, const int32_
                            static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
                            h->sorted_row, h->sorted_gid, all, h->b_cap_row);
     } else if (!split) {
-      HIPCHK(h, hipMemsetAsync(h->cell_count + h->ncell, 0, sizeof(int32_t) * (size_t)(32 + nrows), s));
+      // (an update's build: k_skin_check has cleared these words where it decided on a build)
+      if (!h->gate) HIPCHK(h, hipMemsetAsync(h->cell_count + h->ncell, 0, sizeof(int32_t) * (size_t)(32 + nrows), s));
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
       const BinPhase all = {0, n, nrows, 0, 0, 0, nrows, nrows, -1, h->b_dyn};
       run_pass(all, h->row_count, h->row_start, nrows, ev != nullptr);
@@ -641,7 +658,12 @@ int enqueue_build(nl_handle_t h, const void* q_dev, int32_t stride, const int32_
       run_pass(ghosts, h->row_count + nrows, h->row_start + nrows + 16, 2 * my, false);
     }
   } else {
-    HIPCHK(h, hipMemsetAsync(h->cell_count, 0, sizeof(int32_t) * (size_t)(h->ncell + 32), s));
+    if (h->gate) {  // an update's build: no memset node, a launch that waits on the decision like the others
+      const int64_t words = h->ncell + 32;
+      hipLaunchKernelGGL(k_zero_words, dim3((uint32_t)std::min<int64_t>((words + 1023) / 1024, 2048)), dim3(256), 0, s, h->cell_count, words, h->gate);
+    } else {
+      HIPCHK(h, hipMemsetAsync(h->cell_count, 0, sizeof(int32_t) * (size_t)(h->ncell + 32), s));
+    }
     if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
     if (n > 0) hipLaunchKernelGGL((k_hash<T>), dim3(nbp), dim3(256), 0, s, q, stride, n, g, h->cell_count, h->rank, h->status);
     if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_CELL_SCAN], s));
@@ -980,7 +1002,7 @@ int nl_destroy(nl_handle_t h) {
   if (!h) return NL_ERR_ARG;
   (void)hipSetDevice(h->device);
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
-  void* bufs[] = {h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
+  void* bufs[] = {h->snap, h->skin_words, h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
                   h->cell_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1002,6 +1024,7 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
     (void)rc;
   }
   h->built = false;
+  h->upd_valid = false;
   const size_t n = (size_t)n_max;
   const size_t pos_bytes = h->dtype == NL_F32 ? sizeof(Pos<float>) : sizeof(Pos<double>);
   int rc;
@@ -1065,6 +1088,7 @@ int nl_set_periodic(nl_handle_t h, int minimum_image) {
   if (!h) return NL_ERR_ARG;
   HIPCHK(h, hipSetDevice(h->device));
   if (h->pending) (void)finish(h, false);
+  h->upd_valid = false;
   if ((minimum_image != 0) != h->pbc) {
     h->pbc = minimum_image != 0;
     h->built = false;
@@ -1077,6 +1101,7 @@ int nl_set_list_kind(nl_handle_t h, int kind) {
   if (!h || (kind != NL_LIST_HALF && kind != NL_LIST_FULL)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (h->pending) (void)finish(h, false);
+  h->upd_valid = false;
   if (kind != h->list_kind) {
     h->list_kind = kind;
     h->built = false;
@@ -1099,6 +1124,7 @@ int nl_set_capacity(nl_handle_t h, int64_t max_pairs) {
   HIPCHK(h, hipSetDevice(h->device));
   if (h->pending) (void)finish(h, false);
   h->built = false;
+  h->upd_valid = false;
   int rc = dev_alloc(h, &h->list, 4 * (size_t)(max_pairs + 16));
   if (rc) {
     h->capacity = 0;
@@ -1124,6 +1150,7 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
     z_lo = h->begun_zlo, z_hi = h->begun_zhi;
   }
   h->begun = false;
+  h->upd_valid = false, h->last_update = false;  // (only an update's build writes the snapshot)
   if (h->n_max <= 0 && n > 0) return fail(h, NL_ERR_STATE);
   if (n < 0 || n_rows < 0 || n_rows > n || n > h->n_max || (q_stride != 3 && q_stride != 4) || (!q_dev && n > 0))
     return fail(h, NL_ERR_ARG);
@@ -1298,6 +1325,7 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream) {
   int rc = nl_synchronize(h);  // the permutation is the last build's
   if (rc) return rc;
   if (h->b_slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // a permutation of the caller's own particles
+  h->upd_valid = false;  // (the snapshot holds the old order)
   HIPCHK(h, hipSetDevice(h->device));
   const int32_t n = h->n;
   if (n == 0) return NL_OK;
@@ -1328,6 +1356,7 @@ int nl_set_offset_width(nl_handle_t h, int bits) {
   if (!h || (bits != 0 && bits != 32 && bits != 64)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (h->pending) (void)finish(h, false);
+  h->upd_valid = false;
   if (bits != h->offset_width) {
     h->offset_width = bits;
     h->built = false;
@@ -1504,5 +1533,6 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 }  // extern "C"
 
 #include "nl_transpose.inc"
+#include "nl_skin.inc"
 #include "nl_consumer.inc"
 #include "nl_dist.inc"

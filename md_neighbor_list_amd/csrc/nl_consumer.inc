@@ -24,13 +24,21 @@ template <typename T> __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
-// one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i
+// one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i.  status (nl_lj_forces_enqueue,
+// which does not wait for the build): the build's status word; a list whose build failed gives NaN forces.
 template <typename T, bool HALF, typename OFF>
 __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
                                             const int32_t* __restrict__ list, int32_t n, T eps4, T sig2, T rcf2,
-                                            T* __restrict__ f, T Lx, T Ly, T Lz) {
+                                            T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status) {
   const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (row >= n) return;
+  if (status && *status != 0u) {  // (uniform: every row of the launch takes this branch)
+    if (lane == 0) {
+      const T nan = (T)NAN;
+      f[(size_t)row * 4 + 0] = nan, f[(size_t)row * 4 + 1] = nan, f[(size_t)row * 4 + 2] = nan, f[(size_t)row * 4 + 3] = nan;
+    }
+    return;
+  }
   T xi, yi, zi;
   load_xyz(q, stride, row, xi, yi, zi);
   T ax = 0, ay = 0, az = 0, ae = 0;
@@ -72,7 +80,7 @@ __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t str
 
 template <typename T, typename OFF>
 int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, double eps, double sigma, double rc_force, void* f_dev,
-              hipStream_t s) {
+              hipStream_t s, const uint32_t* status = nullptr) {
   const int32_t n = h->n;
   const T eps4 = (T)(4.0 * eps), sig2 = (T)(sigma * sigma), rcf2 = (T)(rc_force * rc_force);
   const int32_t nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
@@ -81,11 +89,11 @@ int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, double eps, doub
   const T Lx = h->b_pbc ? (T)h->L[0] : (T)0, Ly = h->b_pbc ? (T)h->L[1] : (T)0, Lz = h->b_pbc ? (T)h->L[2] : (T)0;
   if (h->b_full) {
     hipLaunchKernelGGL((k_lj<T, false, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer),
-                       h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz);
+                       h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz, status);
   } else {
     HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
     hipLaunchKernelGGL((k_lj<T, true, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer),
-                       h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz);
+                       h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz, status);
   }
   HIPCHK(h, hipGetLastError());
   return NL_OK;
@@ -107,4 +115,23 @@ extern "C" int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, 
                               : lj_launch<double, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s);
   return h->dtype == NL_F32 ? lj_launch<float, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s)
                             : lj_launch<double, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s);
+}
+
+// nl_lj_forces without the wait: stream-ordered behind the update (or completed build) whose list it reads.
+extern "C" int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma,
+                                    double rc_force, void* f_dev, void* stream) {
+  if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4) || !(rc_force > 0) || !(sigma > 0)) return fail(h, NL_ERR_ARG);
+  if (!(rc_force <= h->rc - h->skin)) return fail(h, NL_ERR_ARG);  // beyond what a list reused within the skin guarantees
+  hipStream_t s = (hipStream_t)stream;
+  if (!h->pending && !h->built) return fail(h, NL_ERR_STATE);  // no build, or one the host has seen fail
+  // a pending build must be an update's (a plain asynchronous build may still need finish() to complete its list) and
+  // enqueued on this stream
+  if (h->pending && (!h->last_update || s != h->last_stream)) return fail(h, NL_ERR_STATE);
+  if (h->b_slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->b_wide)
+    return h->dtype == NL_F32 ? lj_launch<float, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status)
+                              : lj_launch<double, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status);
+  return h->dtype == NL_F32 ? lj_launch<float, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status)
+                            : lj_launch<double, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status);
 }

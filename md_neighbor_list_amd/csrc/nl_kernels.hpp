@@ -53,7 +53,18 @@ template <typename T> struct Grid {
                      //    stored at its periodic image next to that cell: coordinate -+ L
   int32_t z_first;   // slab: global layer that local layer 0 stands for, z_lo - 1 (may be -1)
   T L[3];            // box lengths rounded to T
+  const uint32_t* gate = nullptr;  // nl_update_list: the `go` word of k_skin_check (gate_closed); nullptr in plain builds
 };
+
+// A launch of the update path (nl_update_list) runs only where k_skin_check has decided on a build: every kernel of
+// the build leaves at entry while *gate == 0 -- one scalar load and a uniform branch.  Plain builds pass no gate.
+__device__ __forceinline__ bool gate_closed(const uint32_t* gate) { return gate != nullptr && *gate == 0u; }
+// The histogram and meta words of an update's build on the atomic-rank binning path (NL_BINNING=1); plain builds clear
+// them with a memset node.
+__global__ void __launch_bounds__(256) k_zero_words(int32_t* __restrict__ p, int64_t count, const uint32_t* __restrict__ gate) {
+  if (gate_closed(gate)) return;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) p[k] = 0;
+}
 
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
@@ -127,6 +138,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) k_hash(const T* __restrict__ q, int32_t stride, int32_t n, Grid<T> g,
                                                int32_t* __restrict__ cell_count, int32_t* __restrict__ rank,
                                                uint32_t* __restrict__ status) {
+  if (gate_closed(g.gate)) return;  // (nl_update_list: no build this time)
   const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   T x, y, z;
@@ -153,6 +165,7 @@ __global__ void __launch_bounds__(256) k_reorder(const T* __restrict__ q, int32_
                                                   const int32_t* __restrict__ cell_start,
                                                   const int32_t* __restrict__ rank, Pos<T>* __restrict__ sorted,
                                                   int32_t* __restrict__ sorted_row, int32_t* __restrict__ sorted_gid) {
+  if (gate_closed(g.gate)) return;  // (nl_update_list: no build this time)
   const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int32_t r = rank[i];
@@ -264,7 +277,9 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_chained(const int32_t* __
                                                                 int64_t* __restrict__ total,
                                                                 OFF* __restrict__ out,
                                                                 uint32_t* __restrict__ status,
-                                                                uint32_t* __restrict__ total_split) {
+                                                                uint32_t* __restrict__ total_split,
+                                                                const uint32_t* __restrict__ gate = nullptr) {
+  if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
   __shared__ int32_t wsum[SCAN_THREADS / WAVE];
   __shared__ int64_t before_s;
   __shared__ int32_t block_s;
@@ -364,7 +379,9 @@ constexpr int SCAN_SMALL_MAX = 4096;  // beyond that the per-thread runs get lon
 template <typename OFF>
 __global__ void __launch_bounds__(1024) k_scan_small(const int32_t* __restrict__ in, int32_t n,
                                                       int64_t* __restrict__ total, OFF* __restrict__ out,
-                                                      uint32_t* __restrict__ total_split) {
+                                                      uint32_t* __restrict__ total_split,
+                                                      const uint32_t* __restrict__ gate = nullptr) {
+  if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
   __shared__ int32_t wsum[16];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int32_t K = (n + 1023) / 1024;
@@ -430,6 +447,7 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_rows(const T* __restrict__ 
                                                           Grid<T> g, int32_t nrows, int32_t* __restrict__ row_count,
                                                           int32_t* __restrict__ blk_base, uint32_t* __restrict__ status,
                                                           BinPhase ph) {
+  if (gate_closed(g.gate)) return;  // (nl_update_list: no build this time)
   __shared__ int32_t hist[BIN_MAX_ROWS];
   const int tid = threadIdx.x;
   for (int32_t r = tid; r < nrows; r += BIN_THREADS) hist[r] = 0;
@@ -516,6 +534,7 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(const T* __restrict
                                                              const int32_t* __restrict__ blk_base, Pos<T>* __restrict__ tmp,
                                                              int32_t* __restrict__ tmp_row, uint32_t* __restrict__ status,
                                                              BinPhase ph) {
+  if (gate_closed(g.gate)) return;  // (nl_update_list: no build this time)
   __shared__ int32_t cursor[BIN_MAX_ROWS];
   __shared__ int32_t wsum[BIN_THREADS / WAVE];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -731,6 +750,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
                                                    int32_t* __restrict__ cell_start, Pos<T>* __restrict__ sorted,
                                                    int32_t* __restrict__ sorted_row, int32_t* __restrict__ sorted_gid,
                                                    BinPhase ph, int32_t cap_row = 0) {
+  if (gate_closed(g.gate)) return;  // (nl_update_list: no build this time)
   __shared__ int32_t cnt[FINE ? 4 * BIN_FINE_MAX_MX : BIN_MAX_MX];
   __shared__ int32_t wsum[4];
   __shared__ int32_t carry_s;
@@ -889,6 +909,7 @@ template <typename T> struct SweepArgs {
   uint8_t* __restrict__ masks_hi;  // [rows] high plane: 64 x 8 bits per row (tiles 16..23; not touched for a stream of <= 16 tiles)
   unsigned long long* dbg_buf;  // diagnostics only: cycle accumulators (dbg & 4)
   int32_t dbg;  // diagnostics only (NL_DEBUG_FLAGS): 1 = skip the search, 2 = skip the staging copy; 0 in production
+  const uint32_t* gate = nullptr;  // nl_update_list: see gate_closed
 };
 
 template <typename T> struct SweepCfg;
@@ -1631,6 +1652,7 @@ template <typename T, int MODE> constexpr int sweep_cap() { return SweepCfg<T>::
 
 template <typename T, int MODE, bool FULL = false, bool PBC = false>
 __device__ __forceinline__ void sweep_cell(const SweepArgs<T>& a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   constexpr int CAP = sweep_cap<T, MODE>();
   constexpr bool SCREEN = sizeof(T) == 8;  // fp64 sweeps: fp32 screening + exact test inside the band (search_group)
   __shared__ __attribute__((aligned(32))) char tile_bytes[SCREEN ? screen_lds_bytes(CAP) : CAP * (int)sizeof(Pos<T>)];
@@ -1716,6 +1738,7 @@ constexpr int EXPAND_WAVES = 2;  // waves per workgroup of k_fill_masks: 16 work
 template <typename T, bool FULL = false, bool PBC = false, typename OFF = int32_t, int RB = 24, int EW = EXPAND_WAVES, int CAP = SweepCfg<T>::CAP>
 __global__ void __launch_bounds__(EW* WAVE, (sizeof(OFF) == 8 ? 4 : sizeof(T) == 4 ? (FULL || RB > 12 ? 7 : 8) : 4)) __attribute__((amdgpu_num_sgpr(80)))
 k_fill_masks(SweepArgs<T> a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   constexpr int EXPAND_RMAX = EXPAND_RMAX_OF<FULL>;
   // One LDS array (a second __shared__ object next to an LDS-DMA target makes hipcc drain the DMA before every
   // ds_read): the ids of the stencil stream (4.5 KiB) + per wave four rows being put together.
@@ -1918,6 +1941,7 @@ k_fill_masks(SweepArgs<T> a) {
 // the batched FILL search of k_sweep<FILL>, a workgroup per listed cell.
 template <typename T, bool FULL = false, bool PBC = false>
 __global__ void __launch_bounds__(SWEEP_WAVES* WAVE) k_fill_list(SweepArgs<T> a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   constexpr int CAP = sweep_cap<T, MODE_FILL>();
   constexpr bool SCREEN = sizeof(T) == 8;
   __shared__ __attribute__((aligned(32))) char tile_bytes[SCREEN ? screen_lds_bytes(CAP) : CAP * (int)sizeof(Pos<T>)];
@@ -1949,6 +1973,7 @@ constexpr int FD_RMAX = 1024;  // longest row assembled in LDS (4 KB per wave); 
 
 template <typename T, bool FULL = false, bool PBC = false, typename OFF = int32_t>
 __global__ void __launch_bounds__(FD_WAVES* WAVE) k_fill_dense(SweepArgs<T> a, const OFF* __restrict__ base_sorted) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   constexpr int CAP = SweepCfg<T>::CAP;
   __shared__ __attribute__((aligned(32))) int32_t lds[FD_NB * CAP + FD_WAVES * FD_RMAX];
   int32_t* const gids = lds;
@@ -2071,7 +2096,8 @@ namespace nl {
 template <typename OFF>
 __global__ void __launch_bounds__(256) k_row_base(const OFF* __restrict__ key_pointer,
                                                    const int32_t* __restrict__ sorted_row, int32_t n_rows, int32_t n,
-                                                   OFF* __restrict__ base_sorted) {
+                                                   OFF* __restrict__ base_sorted, const uint32_t* __restrict__ gate = nullptr) {
+  if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
   const int32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   const int32_t r = sorted_row[s];

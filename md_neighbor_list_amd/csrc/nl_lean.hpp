@@ -111,6 +111,7 @@ __device__ __forceinline__ void pipe_search(const SweepArgs<float>& a, const Cel
 constexpr int LEAN_SMALL_CAP = SweepCfg<float>::CAP / 2;
 template <bool FULL, int NW = SWEEP_WAVES, int CAP = SweepCfg<float>::CAP>
 __global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80))) k_sweep_lean_f32(SweepArgs<float> a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   __shared__ __attribute__((aligned(32))) Pos<float> buf[CAP];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_amdgcn_s_setprio(NL_PRIO);  // everything but the tile loop of search_group
@@ -131,6 +132,7 @@ __global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80
 // The cells k_sweep_pipe_f32 left out (local cell indices in full27_list): the batched search, a workgroup per cell.
 template <bool FULL>
 __global__ void __launch_bounds__(SWEEP_WAVES* WAVE) __attribute__((amdgpu_num_sgpr(80))) k_sweep_list_f32(SweepArgs<float> a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   constexpr int CAP = SweepCfg<float>::CAP;
   __shared__ __attribute__((aligned(32))) Pos<float> tile[CAP];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -79,6 +79,7 @@ struct RowsArgs {
   int32_t* __restrict__ over_count;         // a meta word next to the status word, zeroed with it
   int32_t wide;
   unsigned long long* dbg_buf;              // timing experiments only (-DNL_STAMP / -DNL_STAMP_FILL): per-phase wave cycles
+  const uint32_t* gate = nullptr;           // nl_update_list: see gate_closed
 };
 
 // What a wave knows about the stencil of cell (cx, cy, cz).  Lane s < 36 holds the window staged as slot s: x-cells
@@ -382,6 +383,7 @@ __device__ __forceinline__ void rows_stage(const RowsCtx& c, const E* __restrict
 
 template <int V, bool FULL>
 __global__ void __launch_bounds__(ROWS_WAVES* WAVE, RowsCfg<V>::WS) __attribute__((amdgpu_num_sgpr(96))) k_sweep_rows_f32(RowsArgs a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   typedef RowsCfg<V> Cfg;
   typedef typename Cfg::word_t word_t;
   constexpr int CAP = Cfg::CAP;
@@ -547,6 +549,7 @@ template <typename OFF, typename word_t, int RB> struct FillRows {
 template <int V, bool FULL, typename OFF>
 __global__ void __launch_bounds__(ROWS_FW* WAVE, (sizeof(OFF) == 8 && RowsCfg<V>::WF > 6 ? 6 : RowsCfg<V>::WF)) __attribute__((amdgpu_num_sgpr(96)))
 k_fill_rows(RowsArgs a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   typedef RowsCfg<V> Cfg;
   typedef typename Cfg::word_t word_t;
   constexpr int CAP = Cfg::CAP, ROWB = WAVE * (int)sizeof(word_t), RB = ROWS_RBYTES / ROWB / 4 * 4;  // 20 rows of 16-bit words, 8 of 32-bit words
@@ -714,6 +717,7 @@ k_fill_rows(RowsArgs a) {
 // after the other against them (lane i keeps the count of particle i).  The reach of the quarter alone: 27 windows.
 template <int MODE, bool FULL, typename OFF>
 __global__ void __launch_bounds__(ROWS_WAVES* WAVE) k_rows_overflow(RowsArgs a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   if (MODE == MODE_FILL && a.total[0] > a.capacity) return;  // (k_fill_rows has raised ST_CAPACITY)
   const int tid = threadIdx.x, lane = tid & 63, q = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int32_t count = *a.over_count;

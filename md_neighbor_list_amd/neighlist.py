@@ -78,6 +78,7 @@ class NeighListGPU:
         if minimum_image:
             self.set_periodic(True)
         self._q = None  # keeps the positions of an asynchronous build alive
+        self.skin = 0.0
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -135,6 +136,29 @@ class NeighListGPU:
         self._q = q
         self._n = self._n_rows = n
         check(self._lib.nl_make_list(self._h, q.data_ptr(), q.shape[1], n, stream, 1 if sync else 0), "nl_make_list")
+
+    # ------------------------------------------------------------------ Verlet-skin updates
+    def set_skin(self, skin):
+        """Skin of the Verlet list (nl_set_skin): the handle's cut-off is the physical cut-off + skin, and update() keeps
+        the list until some particle has moved more than skin / 2 since its build."""
+        check(self._lib.nl_set_skin(self._h, float(skin)), "nl_set_skin")
+        self.skin = float(skin)
+
+    def update(self, q, particle_number=None, sync=False):
+        """Rebuilds the list only where it no longer holds (nl_update_list): decided on the device, in stream order, with
+        no host wait -- so that an MD step can be enqueued ahead or captured into a graph.  ``sync=True`` waits and grows
+        the list like ``MakeNeighList(sync=True)``."""
+        n = self._check_q(q, particle_number)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._q = q
+        self._n = self._n_rows = n
+        check(self._lib.nl_update_list(self._h, q.data_ptr(), q.shape[1], n, stream, 1 if sync else 0), "nl_update_list")
+
+    def update_stats(self):
+        """(updates, builds they performed) of this handle (nl_get_update_stats; waits for the device)."""
+        st = (C.c_int64 * 2)()
+        check(self._lib.nl_get_update_stats(self._h, C.byref(st)), "nl_get_update_stats")
+        return int(st[0]), int(st[1])
 
     GID_IN_W = "w"  # MakeNeighListSlab(gid=GID_IN_W): ids are stored in q[:, 3] as integer bit patterns (NL_GID_IN_W)
 
@@ -266,18 +290,24 @@ class NeighListGPU:
         return int(cs.value), int(ne.value)
 
     # ------------------------------------------------------------------ a consumer of the list
-    def lj_forces(self, q, epsilon=1.0, sigma=1.0, rc_force=None):
+    def lj_forces(self, q, epsilon=1.0, sigma=1.0, rc_force=None, wait=True, out=None):
         """Truncated Lennard-Jones forces and per-particle energies ``(n, 4) = {fx, fy, fz, pe_i}`` from the list of
         the last build (nl_lj_forces): gather per row after a full-list build, pair-once with atomics after a half
-        build."""
+        build.  ``wait=False`` (nl_lj_forces_enqueue): no wait for the build, stream-ordered behind the last update();
+        rc_force must then be <= cut-off - skin, and a list whose build failed gives NaN.  ``out``: an (n, 4) tensor
+        to write into (graph capture)."""
         n = self._check_q(q, None)
         if n != self._n:
             raise ValueError("q must hold the particles the list was built from")
-        f = torch.empty((n, 4), dtype=self.dtype, device=self.device)
+        f = torch.empty((n, 4), dtype=self.dtype, device=self.device) if out is None else out
+        if f.shape != (n, 4) or f.dtype != self.dtype or not f.is_contiguous():
+            raise TypeError("out must be a contiguous (n, 4) tensor of the list's dtype")
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        check(self._lib.nl_lj_forces(self._h, q.data_ptr(), q.shape[1], float(epsilon), float(sigma),
-                                     float(self.search_length if rc_force is None else rc_force), f.data_ptr(), stream),
-              "nl_lj_forces")
+        if rc_force is None:
+            rc_force = self.search_length if wait else self.search_length - self.skin
+        fn = self._lib.nl_lj_forces if wait else self._lib.nl_lj_forces_enqueue
+        check(fn(self._h, q.data_ptr(), q.shape[1], float(epsilon), float(sigma), float(rc_force), f.data_ptr(), stream),
+              "nl_lj_forces" if wait else "nl_lj_forces_enqueue")
         return f
 
     # ------------------------------------------------------------------ periodic re-sorting (SORT_FREQ)

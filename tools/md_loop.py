@@ -8,7 +8,14 @@
   * forces from nl_lj_forces on the full list (one gather per row, no atomics).
 The list has no minimum image (neither has the reference): the droplet sits in the middle of an open box.
 
-usage: tools/md_loop.py [--cells 12] [--steps 400] [--dtype f64]
+The rebuild trigger (--trigger):
+  host    the displacement since the last build is reduced on the device and compared on the host: one host sync per
+          step, plus the one nl_lj_forces makes;
+  device  nl_update_list decides on the device and rebuilds only when needed, nl_lj_forces_enqueue does not wait: a step
+          is enqueued without a host sync; --graph captures one whole step (integrate, update, forces) into a
+          torch.cuda.graph and replays it.  The re-sort reads update_stats() every SORT_CHECK steps.
+
+usage: tools/md_loop.py [--cells 12] [--steps 400] [--dtype f64] [--trigger host|device] [--graph]
 """
 import argparse
 import os
@@ -22,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from md_neighbor_list_amd import NeighListGPU  # noqa: E402
 
 SORT_FREQ = 50
+SORT_CHECK = 50  # device trigger: steps between two looks at the build count (a host sync)
 
 
 def fcc_droplet(cells, a, box, dtype, seed=1):
@@ -38,7 +46,10 @@ def fcc_droplet(cells, a, box, dtype, seed=1):
 
 
 class Simulation:
-    def __init__(self, q, v, box, rc=2.5, skin=0.4, dt=0.004, device="cuda"):
+    def __init__(self, q, v, box, rc=2.5, skin=0.4, dt=0.004, device="cuda", trigger="host", graph=False):
+        if trigger not in ("host", "device") or (graph and trigger != "device"):
+            raise ValueError("trigger is 'host' or 'device'; graph needs the device trigger")
+        self.trigger, self.use_graph, self.graph, self.steps = trigger, graph, None, 0
         self.tdt = torch.float32 if q.dtype == np.float32 else torch.float64
         self.q = torch.from_numpy(q).to(device)
         self.v = torch.from_numpy(v).to(device)
@@ -48,6 +59,13 @@ class Simulation:
         self.nl.Initialize(len(q))
         self.builds = self.sorts = 0
         self.q_built = None
+        if trigger == "device":
+            self.nl.set_skin(skin)
+            self.nl.update(self.q, sync=True)
+            self.sorted_at = 0  # build count at the last re-sort
+            self.f = torch.empty((len(q), 4), dtype=self.tdt, device=device)
+            self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc, wait=False, out=self.f)
+            return
         self.rebuild()
         self.f = self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc)
 
@@ -61,6 +79,8 @@ class Simulation:
         self.builds += 1
 
     def step(self):
+        if self.trigger == "device":
+            return self.step_device()
         dt = self.dt
         self.v += 0.5 * dt * self.f[:, :3]
         self.q[:, :3] += dt * self.v
@@ -69,6 +89,38 @@ class Simulation:
             self.rebuild()
         self.f = self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc)
         self.v += 0.5 * dt * self.f[:, :3]
+
+    def _device_step(self):
+        dt = self.dt
+        self.v += 0.5 * dt * self.f[:, :3]
+        self.q[:, :3] += dt * self.v
+        self.nl.update(self.q)  # (the rebuild decision on the device, no host sync)
+        self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc, wait=False, out=self.f)
+        self.v += 0.5 * dt * self.f[:, :3]
+
+    def step_device(self):
+        if self.steps and self.steps % SORT_CHECK == 0:
+            builds = self.nl.update_stats()[1]
+            if builds - self.sorted_at >= SORT_FREQ:
+                # re-sort into the last build's cell order (f too: the next step starts from it); the update after a
+                # re-sort builds, here outside any graph
+                self.nl.resort(self.q, self.v, self.ids, self.f)
+                self.nl.update(self.q, sync=True)
+                self.sorted_at = builds + 1
+                self.sorts += 1
+        if self.use_graph and self.graph is None and self.steps >= 1:  # (the first step runs eagerly: warm-up)
+            self.nl.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._device_step()
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._device_step()
+        self.steps += 1
+
+    def build_count(self):
+        return self.nl.update_stats()[1] if self.trigger == "device" else self.builds
 
     def energy(self):
         return float(self.f[:, 3].sum() + 0.5 * self.v.square().sum())
@@ -79,10 +131,12 @@ def main():
     ap.add_argument("--cells", type=int, default=12)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--dtype", default="f64", choices=["f32", "f64"])
+    ap.add_argument("--trigger", default="host", choices=["host", "device"])
+    ap.add_argument("--graph", action="store_true", help="device trigger: replay one captured step")
     args = ap.parse_args()
     a, box = 1.56, 4.0 * args.cells
     q, v = fcc_droplet(args.cells, a, box, np.float32 if args.dtype == "f32" else np.float64)
-    sim = Simulation(q, v, box)
+    sim = Simulation(q, v, box, trigger=args.trigger, graph=args.graph)
     e0 = sim.energy()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -91,7 +145,8 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     e1 = sim.energy()
-    print(f"N={len(q)} steps={args.steps} builds={sim.builds} re-sorts={sim.sorts} E0={e0:.6f} E1={e1:.6f} "
+    print(f"N={len(q)} trigger={args.trigger}{'+graph' if args.graph else ''} steps={args.steps} builds={sim.build_count()} "
+          f"re-sorts={sim.sorts} E0={e0:.6f} E1={e1:.6f} "
           f"drift={(e1 - e0) / abs(e0):.2e} {1e3 * dt / args.steps:.3f} ms/step")
 
 
