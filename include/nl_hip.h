@@ -111,8 +111,26 @@ int nl_set_graph(nl_handle_t h, int on);
  * at its image next to that cell.  The pair is decided once, by the row that stores it (the smaller id); with
  * NL_LIST_FULL both rows decide on their own and may differ for a pair within one ulp of the cut-off across a face.
  * Slab builds: the two ghost layers of the box-end ranks are the periodic images (the caller sends the layers
- * unshifted, as for the open box).  Takes effect at the next build. */
+ * unshifted, as for the open box).  Takes effect at the next build.
+ * nl_set_periodic(h, m) is nl_set_periodic_axes(h, m ? 7 : 0). */
 int nl_set_periodic(nl_handle_t h, int minimum_image);
+
+/* The minimum image on chosen axes only (a film or an interface: periodic in x and y, open in z).  mask: bit 0 = x,
+ * bit 1 = y, bit 2 = z; 0 = the open box (default), 7 = nl_set_periodic(1); outside 0..7 is NL_ERR_ARG.
+ *   On an axis in the mask: a stencil cell reached through that axis's face is tested at its image (coordinate -+ L,
+ *   rounded to the position type first), and a particle whose cell index was wrapped on that axis is itself stored at
+ *   its image, its cell index taken as the floor of q * ims.
+ *   On an axis not in the mask neither happens: the coordinate is used as given and the cell index is the reference's
+ *   truncation plus one wrap.  The stencil still wraps, so a particle slightly outside [0, L) on an open axis still
+ *   finds its neighbours; a pair across an open face is as far apart as its raw coordinates say.
+ * Any mask but 0 runs the minimum-image kernels (the cost of mask 7).  Every axis still needs 3 cells (NL_ERR_MESH).
+ * Slab builds: the box-end ranks' ghost layers are z-images only with bit 2 set.  With z open they are taken as given
+ * and hold partners only of particles whose z lies outside [0, L) (filed into the wrapped layer); where every z lies
+ * in [0, L) the caller may send them empty.  Side effects as nl_set_periodic: a pending
+ * build is finished, the next nl_update_list builds, and a changed mask drops the list.  Takes effect at the next
+ * build; nl_get_periodic_axes returns the mask that the next build will use. */
+int nl_set_periodic_axes(nl_handle_t h, int mask);
+int nl_get_periodic_axes(nl_handle_t h, int* mask);
 
 int nl_destroy(nl_handle_t h);
 
@@ -209,11 +227,12 @@ int nl_synchronize(nl_handle_t h);
  *   nl_set_skin: skin >= 0 (default 0: every particle that moved at all triggers a build); forces the next update to build.
  *   nl_update_list: builds as nl_make_list does (the same list) exactly when
  *     (a) the host knows a reason: no list of an update to keep (first update; nl_initialize, nl_set_list_kind,
- *         nl_set_periodic, nl_set_offset_width, nl_set_capacity, nl_set_skin or nl_resort called, or a build other than
+ *         nl_set_periodic(_axes), nl_set_offset_width, nl_set_capacity, nl_set_skin or nl_resort called, or a build other than
  *         an update's run, since; the host has seen the last build fail) or q_dev, q_stride or n differ from that build's;
  *     (b) the status word of the last performed build is not OK (an asynchronous build that overflowed its capacity);
  *     (c) for some particle i < n, with d = q_now - snap per component in the position type (round to nearest, no
- *         contraction), dd = (double)d, folded to the minimum image after nl_set_periodic(1) (dd -= L rint(dd / L)),
+ *         contraction), dd = (double)d, folded to the minimum image on every axis of the nl_set_periodic_axes mask
+ *         (dd -= L rint(dd / L), that component only),
  *         r2 = (ddx^2 + ddy^2) + ddz^2 in double without FMA is NaN or > (skin / 2)^2.  snap = the caller's positions
  *         at the last build an update performed, in input order.
  *   Otherwise nothing changes, on the device or the host: the getters, nl_lj_forces and nl_resort see the last build.
@@ -292,7 +311,7 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream);
  * list was built from (or moved by less than the skin), same dtype and stride; f_dev: n x 4 values of that dtype,
  * {fx, fy, fz, pe_i} with pe_i = half the pair energies of particle i; pairs beyond rc_force (<= the list's cut-off)
  * are skipped; distances are taken as the list took them: between the coordinates as given (open box, the reference's
- * rule) or, after nl_set_periodic(1), at the minimum image.  After a NL_LIST_FULL build every row gathers its partners and
+ * rule) or at the minimum image on the axes of the build's nl_set_periodic_axes mask, each component on its own.  After a NL_LIST_FULL build every row gathers its partners and
  * writes its force once; after a NL_LIST_HALF build every pair is evaluated once and the reaction is added to the
  * partner with floating-point atomics (f_dev is zeroed first).  Enqueued on `stream` (NULL = the null stream);
  * waits for the build first. */

@@ -49,7 +49,7 @@ struct nl_handle_s {
   int64_t capacity = 0;      // list entries (half pairs, or twice as many for a full list)
   bool capacity_user = false;
   int list_kind = NL_LIST_HALF;
-  bool pbc = false;          // minimum-image mode (nl_set_periodic)
+  int pbc = 0;               // axes of the minimum image, bit d = axis d (nl_set_periodic_axes); 0 = the open box
 
   // device buffers
   int32_t* rank = nullptr;
@@ -128,7 +128,7 @@ struct nl_handle_s {
   struct GraphKey {
     const void* q = nullptr;
     const int32_t* gid = nullptr;
-    int32_t stride = 0, n_rows = 0, n = 0, z_lo = 0, mzl = 0, slab = 0, list_kind = 0, pbc = 0, offset_width = 0;
+    int32_t stride = 0, n_rows = 0, n = 0, z_lo = 0, mzl = 0, slab = 0, list_kind = 0, pbc_mask = 0, offset_width = 0;
     int32_t cap_row = 0, list = 0;  // the captured binning and search launches (b_cap_row, b_list)
     int32_t update = 0;             // 1: nl_update_list's chain (check, gated build, snapshot, result copy)
     double skin = 0;                // ... and the skin its check was captured with
@@ -136,7 +136,7 @@ struct nl_handle_s {
     uint64_t epoch = 0;
     bool operator==(const GraphKey& o) const {
       return q == o.q && gid == o.gid && stride == o.stride && n_rows == o.n_rows && n == o.n && z_lo == o.z_lo &&
-             mzl == o.mzl && slab == o.slab && list_kind == o.list_kind && pbc == o.pbc && offset_width == o.offset_width &&
+             mzl == o.mzl && slab == o.slab && list_kind == o.list_kind && pbc_mask == o.pbc_mask && offset_width == o.offset_width &&
              cap_row == o.cap_row && list == o.list && update == o.update && skin == o.skin && capacity == o.capacity &&
              epoch == o.epoch;
     }
@@ -162,7 +162,7 @@ struct nl_handle_s {
   bool b_use_masks = false;  // this build: COUNT keeps hit masks and the list is expanded from them
   bool b_wide = false;       // this build: key_pointer / base_sorted hold int64 (the list may exceed INT32_MAX entries)
   bool b_full = false;       // this build: full list (both directions), nl_set_list_kind
-  bool b_pbc = false;        // this build: minimum-image distances (nl_set_periodic)
+  int b_pbc = 0;             // this build: axes of the minimum image (nl_set_periodic_axes)
   int b_variant = 3;         // sweep variant of this build (a full build uses 1 or 3 only)
   const void* b_q = nullptr;
   const int32_t* b_gid = nullptr;
@@ -237,7 +237,7 @@ template <typename T> Grid<T> make_grid(nl_handle_t h, int32_t n_rows, int32_t z
   g.slab = slab;
   g.z_origin = slab ? ((z_lo - 1) % h->m[2] + h->m[2]) % h->m[2] : 0;
   g.n_rows = n_rows;
-  g.pbc = h->pbc ? 1 : 0;
+  g.pbc = h->pbc;
   g.dbg = h->dbg_flags;
   g.z_first = slab ? z_lo - 1 : 0;
   for (int d = 0; d < 3; d++) g.L[d] = (T)h->L[d];
@@ -302,7 +302,7 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.full27_list = h->full27_list;
   a.full27_count = reinterpret_cast<int32_t*>(h->status) + META_FULL27;
   a.fill_list_count = reinterpret_cast<int32_t*>(h->status) + META_FILL_LIST;
-  a.pbc = h->pbc ? 1 : 0;
+  a.pbc = h->pbc;
   for (int d = 0; d < 3; d++) a.ms[d] = (T)(h->L[d] / h->m[d]);
   for (int d = 0; d < 3; d++) a.L[d] = (T)h->L[d];
   a.z_origin = h->b_slab ? h->b_zlo - 1 : 0;
@@ -428,10 +428,10 @@ template <typename T, bool FULL, bool PBC> void launch_sweep_kind(nl_handle_t h,
 
 template <typename T> void launch_sweep(nl_handle_t h, int mode, hipStream_t s) {
   if (h->b_full) {
-    if (h->pbc) launch_sweep_kind<T, true, true>(h, mode, s);
+    if (h->pbc != 0) launch_sweep_kind<T, true, true>(h, mode, s);
     else launch_sweep_kind<T, true, false>(h, mode, s);
   } else {
-    if (h->pbc) launch_sweep_kind<T, false, true>(h, mode, s);
+    if (h->pbc != 0) launch_sweep_kind<T, false, true>(h, mode, s);
     else launch_sweep_kind<T, false, false>(h, mode, s);
   }
 }
@@ -522,7 +522,7 @@ void set_build_state(nl_handle_t h, const void* q_dev, int32_t stride, const int
   // along z by more than the rounding of the cell hash can hide (rows_margin_ok).  RowsCfg by the mean stencil
   // stream m = 27 <N/cell>: m + 5 sigma within the LDS buffer, the piece a wave walks + 6 sigma within its hit word.
   h->b_rows = false;
-  if (sizeof(T) == 4 && h->b_variant >= 3 && !h->pbc && h->rows_env != 0 && rows_layout_ok(h, mzl) && rows_margin_ok(h)) {
+  if (sizeof(T) == 4 && h->b_variant >= 3 && h->pbc == 0 && h->rows_env != 0 && rows_layout_ok(h, mzl) && rows_margin_ok(h)) {
     int v = -1;
     if (h->rows_env > 0 && h->rows_env <= 3) {
       v = h->rows_env - 1;
@@ -1084,16 +1084,25 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   return NL_OK;
 }
 
-int nl_set_periodic(nl_handle_t h, int minimum_image) {
+int nl_set_periodic_axes(nl_handle_t h, int mask) {
   if (!h) return NL_ERR_ARG;
+  if (mask < 0 || mask > 7) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (h->pending) (void)finish(h, false);
   h->upd_valid = false;
-  if ((minimum_image != 0) != h->pbc) {
-    h->pbc = minimum_image != 0;
+  if (mask != h->pbc) {
+    h->pbc = mask;
     h->built = false;
     h->t_valid = false;
   }
+  return NL_OK;
+}
+
+int nl_set_periodic(nl_handle_t h, int minimum_image) { return nl_set_periodic_axes(h, minimum_image ? 7 : 0); }
+
+int nl_get_periodic_axes(nl_handle_t h, int* mask) {
+  if (!h || !mask) return fail(h, NL_ERR_ARG);
+  *mask = h->pbc;
   return NL_OK;
 }
 
@@ -1196,7 +1205,7 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
     else set_build_state<double>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
     nl_handle_s::GraphKey key;
     key.q = q_dev, key.gid = gid_dev, key.stride = q_stride, key.n_rows = n_rows, key.n = n, key.z_lo = z_lo, key.mzl = mzl;
-    key.slab = slab, key.list_kind = h->list_kind, key.pbc = h->pbc ? 1 : 0, key.capacity = h->capacity;
+    key.slab = slab, key.list_kind = h->list_kind, key.pbc_mask = h->pbc, key.capacity = h->capacity;
     key.epoch = h->buffers_epoch, key.offset_width = h->offset_width;
     key.cap_row = h->b_cap_row, key.list = h->b_list ? 1 : 0;
     if (!h->graph_exec || !(key == h->graph_key)) {
@@ -1426,7 +1435,7 @@ int nl_get_build_info(nl_handle_t h, int32_t info[8]) {
   info[4] = h->b_wide ? 64 : 32;
   info[5] = h->b_mask_nb;
   info[6] = h->b_rows ? 1 + h->b_rows_v : 0;  // fine-row search: the cell table of nl_get_sorted is the fine-row table
-  info[7] = h->b_use_masks && !h->b_rows && h->b_mask_nb == 1 && h->dtype == NL_F32 && !h->b_pbc && h->b_lean_small ? 1 : 0;
+  info[7] = h->b_use_masks && !h->b_rows && h->b_mask_nb == 1 && h->dtype == NL_F32 && h->b_pbc == 0 && h->b_lean_small ? 1 : 0;
   info[0] = h->b_use_masks ? 1 : 0;
   info[1] = h->sweep_variant;
   info[2] = h->dtype == NL_F32 ? SweepCfg<float>::CAP : SweepCfg<double>::CAP;

@@ -50,12 +50,11 @@ __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t str
     T fx, fy, fz, pe;
     bool in;
     T dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    if (Lx > (T)0) {  // minimum-image list (nl_set_periodic): the pair is taken at the image the list found it at
-      const T hx = (T)0.5 * Lx, hy = (T)0.5 * Ly, hz = (T)0.5 * Lz;
-      dx = dx > hx ? dx - Lx : dx < -hx ? dx + Lx : dx;
-      dy = dy > hy ? dy - Ly : dy < -hy ? dy + Ly : dy;
-      dz = dz > hz ? dz - Lz : dz < -hz ? dz + Lz : dz;
-    }
+    // minimum-image list (nl_set_periodic_axes): on a periodic axis (L > 0) the pair is taken at the image the list
+    // found it at
+    if (Lx > (T)0) dx = dx > (T)0.5 * Lx ? dx - Lx : dx < (T)-0.5 * Lx ? dx + Lx : dx;
+    if (Ly > (T)0) dy = dy > (T)0.5 * Ly ? dy - Ly : dy < (T)-0.5 * Ly ? dy + Ly : dy;
+    if (Lz > (T)0) dz = dz > (T)0.5 * Lz ? dz - Lz : dz < (T)-0.5 * Lz ? dz + Lz : dz;
     lj_pair<T>(dx, dy, dz, eps4, sig2, rcf2, fx, fy, fz, pe, in);
     ax += fx, ay += fy, az += fz, ae += (T)0.5 * pe;
     if (HALF && in) {  // Newton's third law: the partner's share
@@ -85,8 +84,9 @@ int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, double eps, doub
   const T eps4 = (T)(4.0 * eps), sig2 = (T)(sigma * sigma), rcf2 = (T)(rc_force * rc_force);
   const int32_t nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
   if (n == 0) return NL_OK;
-  // box lengths for the minimum image; 0 = open box (the reference's distances, neighlist_cpu.hpp:219-223)
-  const T Lx = h->b_pbc ? (T)h->L[0] : (T)0, Ly = h->b_pbc ? (T)h->L[1] : (T)0, Lz = h->b_pbc ? (T)h->L[2] : (T)0;
+  // box lengths for the minimum image on the axes of the list's build; 0 = open axis (the reference's distances,
+  // neighlist_cpu.hpp:219-223)
+  const T Lx = (h->b_pbc & 1) ? (T)h->L[0] : (T)0, Ly = (h->b_pbc & 2) ? (T)h->L[1] : (T)0, Lz = (h->b_pbc & 4) ? (T)h->L[2] : (T)0;
   if (h->b_full) {
     hipLaunchKernelGGL((k_lj<T, false, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer),
                        h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz, status);

@@ -49,8 +49,9 @@ template <typename T> struct Grid {
   int32_t n_rows;    // particles [0, n_rows) are owned (get rows), [n_rows, n) are ghosts
   // minimum-image mode (nl_set_periodic; not in the reference, which wraps cells but never distances):
   int32_t dbg;       // diagnostics (NL_DEBUG_FLAGS): 512 = binning kernels without the keep_in_flight of their loads
-  int32_t pbc;       // 1: a particle whose cell index was wrapped (or that sits in a slab's wrapped ghost layer) is
-                     //    stored at its periodic image next to that cell: coordinate -+ L
+  int32_t pbc;       // axis mask (nl_set_periodic_axes, bit d = axis d): on an axis in the mask, a particle whose cell
+                     //    index was wrapped (or that sits in a slab's wrapped ghost layer, bit 2) is stored at its
+                     //    periodic image next to that cell: coordinate -+ L.  Other axes: the reference's rule
   int32_t z_first;   // slab: global layer that local layer 0 stands for, z_lo - 1 (may be -1)
   T L[3];            // box lengths rounded to T
   const uint32_t* gate = nullptr;  // nl_update_list: the `go` word of k_skin_check (gate_closed); nullptr in plain builds
@@ -81,15 +82,17 @@ __device__ __forceinline__ int32_t local_cell(const Grid<T>& g, T x, T y, T z, i
                                               int32_t* row_out = nullptr, T* shift_out = nullptr) {
   const T t[3] = {mul_rn(x, g.ims[0]), mul_rn(y, g.ims[1]), mul_rn(z, g.ims[2])};
   int32_t idx[3];
-  T sh[3] = {0, 0, 0};  // minimum-image mode: what to add to the coordinate so that it lies in / next to its cell
+  T sh[3] = {0, 0, 0};  // what to add to the coordinate so that it lies in / next to its cell (the callers apply it on
+                        // the axes of the minimum-image mask only)
   bool bad = false;
 #pragma unroll
   for (int d = 0; d < 3; d++) {
     if (!(t[d] > (T)-2147483000.0 && t[d] < (T)2147483000.0)) bad = true;  // NaN / overflow: UB in the reference
     int32_t v = (int32_t)t[d];
-    // (minimum-image mode takes the floor: the reference's truncation files a particle at -0.3 cells into cell 0,
-    // harmless in its open box, wrong for images)
-    if (g.pbc && t[d] < (T)0 && (T)v != t[d]) v -= 1;
+    // (a periodic axis takes the floor: the reference's truncation files a particle at -0.3 cells into cell 0,
+    // harmless in its open box, wrong for images; an open axis keeps the truncation and the coordinate)
+    const bool per = (g.pbc >> d) & 1;
+    if (per && t[d] < (T)0 && (T)v != t[d]) v -= 1;
     if (v < 0) v += g.m[d], sh[d] = g.L[d];
     if (v >= g.m[d]) v -= g.m[d], sh[d] = -g.L[d];
     if (v < 0 || v >= g.m[d]) bad = true;
@@ -178,7 +181,9 @@ __global__ void __launch_bounds__(256) k_reorder(const T* __restrict__ q, int32_
   const int32_t dst = cell_start[c] + r;
   Pos<T> p;
   p.x = x, p.y = y, p.z = z;
-  if (g.pbc) p.x = add_rn(x, sh[0]), p.y = add_rn(y, sh[1]), p.z = add_rn(z, sh[2]);
+  if (g.pbc & 1) p.x = add_rn(x, sh[0]);
+  if (g.pbc & 2) p.y = add_rn(y, sh[1]);
+  if (g.pbc & 4) p.z = add_rn(z, sh[2]);
   if (gid == reinterpret_cast<const int32_t*>(1)) {  // NL_GID_IN_W: the id travels in the w component of the Vec
     if constexpr (sizeof(T) == 4) p.gid = __float_as_int(q[(size_t)i * 4 + 3]);
     else p.gid = (int32_t)__double_as_longlong(q[(size_t)i * 4 + 3]);
@@ -587,7 +592,8 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(const T* __restrict
       Pos<T> p;
       p.x = x[u], p.y = y[u], p.z = z[u];
       // (minimum-image mode: x keeps its value until k_bin_cells has derived the x-cell from it)
-      if (g.pbc) p.y = add_rn(y[u], sh[1]), p.z = add_rn(z[u], sh[2]);
+      if (g.pbc & 2) p.y = add_rn(y[u], sh[1]);
+      if (g.pbc & 4) p.z = add_rn(z[u], sh[2]);
       p.gid = id[u];
       if constexpr (sizeof(T) == 8) p.row = i;
       tmp[dst] = p;
@@ -646,7 +652,8 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
       const bool in_owned_layer = lz >= 1 && lz < g.mzl - 1;
       if (in_owned_layer != (i < g.n_rows)) fl |= ST_DOMAIN;
     }
-    if (g.pbc) yi = add_rn(yi, sh[1]), zi = add_rn(zi, sh[2]);
+    if (g.pbc & 2) yi = add_rn(yi, sh[1]);
+    if (g.pbc & 4) zi = add_rn(zi, sh[2]);
     return r;
   };
   uint32_t fl = 0;
@@ -769,7 +776,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
   auto xcell1 = [&](T x) {
     const T tx = mul_rn(x, g.ims[0]);
     int32_t v = (int32_t)tx;
-    if (g.pbc && tx < (T)0 && (T)v != tx) v -= 1;
+    if ((g.pbc & 1) && tx < (T)0 && (T)v != tx) v -= 1;
     if (v < 0) v += mx;
     if (v >= mx) v -= mx;
     return v;
@@ -833,7 +840,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
   if (r == nrows - 1 && tid == 0) cell_start[(size_t)nrows * nb] = end;
   auto place = [&](Pos<T> p, int32_t row_of) {
     const int32_t dst = beg + atomicAdd(&cnt[bin_of(p)], 1);
-    if (g.pbc) {  // minimum-image mode: a wrapped x index means the particle is stored at its image
+    if (g.pbc & 1) {  // periodic x: a wrapped x index means the particle is stored at its image
       const T tx = mul_rn(p.x, g.ims[0]);
       int32_t v = (int32_t)tx;
       if (tx < (T)0 && (T)v != tx) v -= 1;
@@ -896,8 +903,9 @@ template <typename T> struct SweepArgs {
   int64_t capacity;
   uint32_t* __restrict__ status;
   T L[3];                         // box lengths rounded to T (minimum-image mode)
-  int32_t pbc;                    // minimum-image mode: stencil cells reached through the periodic wrap are staged
-                                  // at their image, coordinate -+ L (nl_set_periodic; not in the reference)
+  int32_t pbc;                    // axis mask of the minimum image (nl_set_periodic_axes; not in the reference):
+                                  // stencil cells reached through a face of an axis in it are staged at their image,
+                                  // coordinate -+ L (the PBC kernels; segment_cells names only those faces)
   T ms[3];                        // cell edge (screened fp64 search: origin of the relative coordinates)
   int32_t z_origin;               // global z layer of local layer 0
   int32_t isplit;                          // two-sweep path: workgroups per cell (each a part of the cell's i-particles)
@@ -1355,10 +1363,11 @@ __device__ __forceinline__ void segment_cells(const SweepArgs<T>& a, int lane, i
   }
   const int32_t rowbase = (y + z * a.my) * a.mx;
   i0 = rowbase + x0, i1 = rowbase + x1;
-  // through which periodic faces this segment is reached (used in minimum-image mode only)
-  const int32_t wx = (cx == 0 && part == 0) ? -1 : (cx == a.mx - 1 && part == 1) ? 1 : 0;
-  const int32_t wy = cy + dy < 0 ? -1 : cy + dy >= a.my ? 1 : 0;
-  const int32_t wz = a.slab ? 0 : cz + dz < 0 ? -1 : cz + dz >= a.mzl ? 1 : 0;
+  // through which periodic faces this segment is reached (used by the minimum-image kernels only): a face of an axis
+  // outside the mask is "no face", so that a segment that crosses open faces only is staged unshifted
+  const int32_t wx = !(a.pbc & 1) ? 0 : (cx == 0 && part == 0) ? -1 : (cx == a.mx - 1 && part == 1) ? 1 : 0;
+  const int32_t wy = !(a.pbc & 2) ? 0 : cy + dy < 0 ? -1 : cy + dy >= a.my ? 1 : 0;
+  const int32_t wz = a.slab || !(a.pbc & 4) ? 0 : cz + dz < 0 ? -1 : cz + dz >= a.mzl ? 1 : 0;
   wrap = (wx + 1) | (wy + 1) << 2 | (wz + 1) << 4;
 }
 

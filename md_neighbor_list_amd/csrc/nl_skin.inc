@@ -22,7 +22,7 @@ constexpr int SKIN_WORDS = 8;
 constexpr int SKIN_THREADS = 256;
 
 // Rule (c) of nl_update_list, per particle: d = q - snap per component in T (round to nearest, no contraction), widened
-// to double, folded to the minimum image in that mode (d -= L rint(d / L)), r2 = (dx^2 + dy^2) + dz^2 in double without
+// to double, folded to the minimum image on the axes of the mask (d -= L rint(d / L)), r2 = (dx^2 + dy^2) + dz^2 in double without
 // FMA; the particle is past the skin where !(r2 <= (skin/2)^2), which also holds for NaN.  The OR of that flag over all
 // particles decides exactly what "max_i r2 > (skin/2)^2 or any r2 NaN" decides, so no maximum is formed: a block
 // ORs its waves' flags and adds at most one atomic.  The last block through (ticket, as in k_bin_bucket) adds the
@@ -31,7 +31,7 @@ constexpr int SKIN_THREADS = 256;
 // two-pass binning, which a plain build clears with a memset node).
 template <typename T, bool PBC>
 __global__ void __launch_bounds__(SKIN_THREADS) k_skin_check(const T* __restrict__ q, const T* __restrict__ snap, int32_t stride,
-                                                             int32_t n, double thr, double Lx, double Ly, double Lz, int32_t force,
+                                                             int32_t n, double thr, double Lx, double Ly, double Lz, int32_t mask, int32_t force,
                                                              uint32_t* __restrict__ words, const uint32_t* status, int32_t* zero,
                                                              int32_t nzero) {
   __shared__ int32_t last_s;
@@ -42,10 +42,10 @@ __global__ void __launch_bounds__(SKIN_THREADS) k_skin_check(const T* __restrict
     load_xyz(q, stride, i, x, y, z);
     load_xyz(snap, stride, i, sx, sy, sz);
     double dx = (double)sub_rn(x, sx), dy = (double)sub_rn(y, sy), dz = (double)sub_rn(z, sz);
-    if (PBC) {
-      dx = __dsub_rn(dx, __dmul_rn(Lx, rint(dx / Lx)));
-      dy = __dsub_rn(dy, __dmul_rn(Ly, rint(dy / Ly)));
-      dz = __dsub_rn(dz, __dmul_rn(Lz, rint(dz / Lz)));
+    if (PBC) {  // (mask: the axes of the minimum image, nl_set_periodic_axes)
+      if (mask & 1) dx = __dsub_rn(dx, __dmul_rn(Lx, rint(dx / Lx)));
+      if (mask & 2) dy = __dsub_rn(dy, __dmul_rn(Ly, rint(dy / Ly)));
+      if (mask & 4) dz = __dsub_rn(dz, __dmul_rn(Lz, rint(dz / Lz)));
     }
     const double r2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
     past |= !(r2 <= thr);
@@ -97,12 +97,12 @@ int enqueue_update(nl_handle_t h, const void* q_dev, int32_t stride, int32_t n, 
   T* snap = static_cast<T*>(h->snap);
   int32_t* zero = reinterpret_cast<int32_t*>(h->status);
   const int32_t nzero = two_level ? 32 + nrows : 0;
-  if (h->pbc)
+  if (h->pbc != 0)
     hipLaunchKernelGGL((k_skin_check<T, true>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, h->L[0], h->L[1],
-                       h->L[2], force ? 1 : 0, h->skin_words, h->status, zero, nzero);
+                       h->L[2], h->pbc, force ? 1 : 0, h->skin_words, h->status, zero, nzero);
   else
     hipLaunchKernelGGL((k_skin_check<T, false>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, h->L[0], h->L[1],
-                       h->L[2], force ? 1 : 0, h->skin_words, h->status, zero, nzero);
+                       h->L[2], 0, force ? 1 : 0, h->skin_words, h->status, zero, nzero);
   h->gate = h->skin_words + SKIN_GO;
   h->rerun = true;
   int rc = enqueue_build<T>(h, q_dev, stride, nullptr, n, n, 0, mz, 0, s, nullptr);
@@ -179,7 +179,7 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
     h->rerun = false;
     nl_handle_s::GraphKey key;
     key.q = q_dev, key.gid = nullptr, key.stride = q_stride, key.n_rows = n, key.n = n, key.z_lo = 0, key.mzl = mz;
-    key.slab = 0, key.list_kind = h->list_kind, key.pbc = h->pbc ? 1 : 0, key.capacity = h->capacity;
+    key.slab = 0, key.list_kind = h->list_kind, key.pbc_mask = h->pbc, key.capacity = h->capacity;
     key.epoch = h->buffers_epoch, key.offset_width = h->offset_width;
     key.cap_row = h->b_cap_row, key.list = h->b_list ? 1 : 0;
     key.update = 1, key.skin = h->skin;

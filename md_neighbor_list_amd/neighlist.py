@@ -45,7 +45,8 @@ class NeighListGPU:
     """Verlet neighbour-list builder on one MI355X.
 
     Parameters follow neighlist_gpu.hpp:236-255: ``search_length`` (cut-off rc) and the box edges.  ``dtype``
-    plays the role of the reference's compile-time ``Dtype``/``Vec`` choice (make_list.cu:6-12).
+    plays the role of the reference's compile-time ``Dtype``/``Vec`` choice (make_list.cu:6-12).  ``minimum_image``:
+    False (the reference's open box), True (every axis periodic), or the periodic axes as in ``set_periodic(axes=)``.
     """
 
     def __init__(self, search_length, Lx, Ly, Lz, dtype=torch.float32, device=None, full_list=False,
@@ -73,10 +74,11 @@ class NeighListGPU:
         self._n_rows = 0
         self.full_list = False
         self.minimum_image = False
+        self.periodic_axes = (False, False, False)
         if full_list:
             self.set_full_list(True)
         if minimum_image:
-            self.set_periodic(True)
+            self.set_periodic(axes=minimum_image)
         self._q = None  # keeps the positions of an asynchronous build alive
         self.skin = 0.0
 
@@ -105,11 +107,21 @@ class NeighListGPU:
         """Replay asynchronous builds from a captured hipGraph (nl_set_graph): saves launch overhead on small systems."""
         check(self._lib.nl_set_graph(self._h, 1 if on else 0), "nl_set_graph")
 
-    def set_periodic(self, minimum_image=True):
-        """Minimum-image distances across the periodic faces (nl_set_periodic).  The reference, and the default here,
-        wrap the cell stencil but measure distances in an open box."""
-        check(self._lib.nl_set_periodic(self._h, 1 if minimum_image else 0), "nl_set_periodic")
-        self.minimum_image = bool(minimum_image)
+    def set_periodic(self, minimum_image=True, axes=None):
+        """Minimum-image distances across the periodic faces (nl_set_periodic_axes).  The reference, and the default
+        here, wrap the cell stencil but measure distances in an open box.  ``axes`` picks the periodic axes: a 3-tuple
+        of bools or a string drawn from "xyz" (``axes="xy"``: a film, open in z); ``None`` = all three when
+        ``minimum_image`` is true, none otherwise.  ``minimum_image`` is True only for a fully periodic box."""
+        mask = axes_mask(bool(minimum_image) if axes is None else axes)
+        check(self._lib.nl_set_periodic_axes(self._h, mask), "nl_set_periodic_axes")
+        self.periodic_axes = tuple(bool(mask >> d & 1) for d in range(3))
+        self.minimum_image = mask == 7
+
+    def periodic_mask(self):
+        """The axis mask the next build uses (nl_get_periodic_axes): bit 0 = x, bit 1 = y, bit 2 = z."""
+        m = C.c_int()
+        check(self._lib.nl_get_periodic_axes(self._h, C.byref(m)), "nl_get_periodic_axes")
+        return int(m.value)
 
     def set_full_list(self, full=True):
         """Builds produce the FULL list (every pair in both rows: the reference GPU kernels' contract,
@@ -371,6 +383,21 @@ class NeighListGPU:
         ms = (C.c_double * _lib.NL_NUM_STAGES)()
         check(self._lib.nl_profile_last_build(self._h, int(reps), C.byref(ms)), "nl_profile_last_build")
         return dict(zip(_lib.STAGE_NAMES, (float(v) for v in ms)))
+
+
+def axes_mask(axes) -> int:
+    """nl_set_periodic_axes mask of ``axes``: a 3-tuple of bools, a string drawn from "xyz", or a truth value (all
+    axes or none)."""
+    if isinstance(axes, str):
+        if any(c not in "xyz" for c in axes.lower()):
+            raise ValueError(f"periodic axes {axes!r}: use letters from 'xyz'")
+        return sum(1 << "xyz".index(c) for c in set(axes.lower()))
+    if not hasattr(axes, "__len__"):
+        return 7 if axes else 0
+    axes = tuple(axes)
+    if len(axes) != 3:
+        raise ValueError(f"periodic axes {axes!r}: a 3-tuple of bools or a string from 'xyz'")
+    return sum(1 << d for d in range(3) if axes[d])
 
 
 def npairs_exceeds_int32(nl) -> bool:

@@ -6,7 +6,11 @@
     particle arrays are permuted into the build's cell order (nl_resort), which speeds up both the next builds
     and the force gathers (profiles/r01_force_consumer_timing.txt);
   * forces from nl_lj_forces on the full list (one gather per row, no atomics).
-The list has no minimum image (neither has the reference): the droplet sits in the middle of an open box.
+The list has no minimum image by default (neither has the reference): the droplet sits in the middle of an open box.
+--periodic xyz fills the whole box with the crystal and takes the minimum image on every axis; --periodic xy is a film
+that fills x and y (minimum image there, nl_set_periodic_axes) and is finite in z, in the middle of an open z range.
+On the periodic axes the positions are wrapped back into [0, L) after every drift; the displacement since the last
+build is taken at the minimum image there (the host trigger as rule (c) of nl_update_list does).
 
 The rebuild trigger (--trigger):
   host    the displacement since the last build is reduced on the device and compared on the host: one host sync per
@@ -16,6 +20,7 @@ The rebuild trigger (--trigger):
           torch.cuda.graph and replays it.  The re-sort reads update_stats() every SORT_CHECK steps.
 
 usage: tools/md_loop.py [--cells 12] [--steps 400] [--dtype f64] [--trigger host|device] [--graph]
+                        [--periodic none|xyz|xy]
 """
 import argparse
 import os
@@ -45,8 +50,23 @@ def fcc_droplet(cells, a, box, dtype, seed=1):
     return q, vel.astype(dtype)
 
 
+def fcc_slab(cells, a, box, dtype, seed=1):
+    """An FCC crystal of cells[0] x cells[1] x cells[2] unit cells (edge a) centred in a box of edges box[0..2]: with
+    cells[d] * a == box[d] it fills that axis (periodic), with fewer cells it leaves a gap (an open axis)."""
+    base = np.array([[0, 0, 0], [0.5, 0.5, 0], [0.5, 0, 0.5], [0, 0.5, 0.5]])
+    g = np.stack(np.meshgrid(*[np.arange(c) for c in cells], indexing="ij"), -1).reshape(-1, 1, 3)
+    pos = ((g + base).reshape(-1, 3) * a + 0.25 * a).astype(np.float64)
+    pos += 0.5 * (np.array(box, dtype=np.float64) - np.array(cells) * a)
+    rng = np.random.default_rng(seed)
+    vel = rng.normal(0.0, 0.3, size=pos.shape)
+    vel -= vel.mean(axis=0)
+    q = np.zeros((len(pos), 4), dtype=dtype)
+    q[:, :3] = pos
+    return q, vel.astype(dtype)
+
+
 class Simulation:
-    def __init__(self, q, v, box, rc=2.5, skin=0.4, dt=0.004, device="cuda", trigger="host", graph=False):
+    def __init__(self, q, v, box, rc=2.5, skin=0.4, dt=0.004, device="cuda", trigger="host", graph=False, periodic=""):
         if trigger not in ("host", "device") or (graph and trigger != "device"):
             raise ValueError("trigger is 'host' or 'device'; graph needs the device trigger")
         self.trigger, self.use_graph, self.graph, self.steps = trigger, graph, None, 0
@@ -55,7 +75,12 @@ class Simulation:
         self.v = torch.from_numpy(v).to(device)
         self.ids = torch.arange(len(q), device=device)  # original identity of every slot (changes when re-sorted)
         self.rc, self.skin, self.dt, self.box = rc, skin, dt, box
-        self.nl = NeighListGPU(rc + skin, box, box, box, dtype=self.tdt, full_list=True)
+        # periodic: the axes of the minimum image ("" = the open box); box: one edge, or three
+        self.edges = tuple(box) if np.ndim(box) else (box, box, box)
+        self.axes = [d for d in range(3) if "xyz"[d] in periodic]
+        self.nl = NeighListGPU(rc + skin, *self.edges, dtype=self.tdt, full_list=True)
+        if self.axes:
+            self.nl.set_periodic(axes=periodic)
         self.nl.Initialize(len(q))
         self.builds = self.sorts = 0
         self.q_built = None
@@ -84,16 +109,26 @@ class Simulation:
         dt = self.dt
         self.v += 0.5 * dt * self.f[:, :3]
         self.q[:, :3] += dt * self.v
-        moved = (self.q[:, :3] - self.q_built[:, :3]).square().sum(dim=1).max()
+        self.wrap()
+        d = self.q[:, :3] - self.q_built[:, :3]
+        for a in self.axes:  # (minimum image on the periodic axes)
+            d[:, a] -= self.edges[a] * torch.round(d[:, a] / self.edges[a])
+        moved = d.square().sum(dim=1).max()
         if float(moved) > (0.5 * self.skin) ** 2:  # (one host sync per step: the rebuild decision)
             self.rebuild()
         self.f = self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc)
         self.v += 0.5 * dt * self.f[:, :3]
 
+    def wrap(self):
+        """Periodic axes: positions back into [0, L) (the list takes every pair at its minimum image)."""
+        for a in self.axes:
+            self.q[:, a] -= self.edges[a] * torch.floor(self.q[:, a] / self.edges[a])
+
     def _device_step(self):
         dt = self.dt
         self.v += 0.5 * dt * self.f[:, :3]
         self.q[:, :3] += dt * self.v
+        self.wrap()
         self.nl.update(self.q)  # (the rebuild decision on the device, no host sync)
         self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc, wait=False, out=self.f)
         self.v += 0.5 * dt * self.f[:, :3]
@@ -133,10 +168,20 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f32", "f64"])
     ap.add_argument("--trigger", default="host", choices=["host", "device"])
     ap.add_argument("--graph", action="store_true", help="device trigger: replay one captured step")
+    ap.add_argument("--periodic", default="none", choices=["none", "xyz", "xy"],
+                    help="minimum image: none (a droplet in an open box), xyz (a crystal filling the box), xy (a film)")
     args = ap.parse_args()
     a, box = 1.56, 4.0 * args.cells
-    q, v = fcc_droplet(args.cells, a, box, np.float32 if args.dtype == "f32" else np.float64)
-    sim = Simulation(q, v, box, trigger=args.trigger, graph=args.graph)
+    dt_np = np.float32 if args.dtype == "f32" else np.float64
+    if args.periodic == "none":
+        q, v = fcc_droplet(args.cells, a, box, dt_np)
+        sim = Simulation(q, v, box, trigger=args.trigger, graph=args.graph)
+    else:
+        c = args.cells
+        cells = (c, c, c) if args.periodic == "xyz" else (c, c, max(c // 2, 2))
+        edges = (c * a, c * a, c * a if args.periodic == "xyz" else box)
+        q, v = fcc_slab(cells, a, edges, dt_np)
+        sim = Simulation(q, v, edges, trigger=args.trigger, graph=args.graph, periodic=args.periodic)
     e0 = sim.energy()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -145,7 +190,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     e1 = sim.energy()
-    print(f"N={len(q)} trigger={args.trigger}{'+graph' if args.graph else ''} steps={args.steps} builds={sim.build_count()} "
+    print(f"N={len(q)} periodic={args.periodic} trigger={args.trigger}{'+graph' if args.graph else ''} steps={args.steps} builds={sim.build_count()} "
           f"re-sorts={sim.sorts} E0={e0:.6f} E1={e1:.6f} "
           f"drift={(e1 - e0) / abs(e0):.2e} {1e3 * dt / args.steps:.3f} ms/step")
 
