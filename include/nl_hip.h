@@ -247,6 +247,44 @@ int nl_set_skin(nl_handle_t h, double skin);
 int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, void* stream, int sync);
 int nl_get_update_stats(nl_handle_t h, int64_t stats[2]);
 
+/* ------------------------------------------------------------------------------------------------ exclusions */
+
+/* Excluded pairs (no reference counterpart): the bonded partners of a molecular model -- 1-2 and 1-3 pairs of a
+ * bead-spring polymer, of water, of any force field with a topology -- left out of the non-bonded list when it is built,
+ * as LAMMPS special lists, HOOMD and GROMACS do.  The list is filtered once per build, and every consumer sees it filtered.
+ *   The rule: a build with a table leaves out exactly the pairs {i, j} of the table, in either order, and changes nothing
+ *     else.  Half list: row min(i, j) loses j; full list: both rows lose the partner.  An excluded pair beyond the cut-off
+ *     has no effect.  number_of_partners, key_pointer, npairs / nentries, nl_number_of_pairs, nl_list_checksum,
+ *     nl_get_full_transposed and nl_lj_forces(_enqueue) all describe the filtered list.  Holds for F32 and F64, every
+ *     periodic mask, 32- and 64-bit offsets and every search path.
+ *   nl_set_exclusions: pairs_dev = device int32 [n_pairs][2] of input-order particle indices; n = the particle count of
+ *     the builds the table applies to.  The pairs are copied (the caller may free them) and checked on the device:
+ *     0 <= i, j < n, i != j, and n <= n_max, else NL_ERR_ARG and the old table is kept.  Duplicates and both orders
+ *     are allowed.  The symmetric, sorted, deduplicated table is built on the device; set-up time grows with the square
+ *     of the longest row (a wave ranks a row of m ids in m^2 / 64 steps: bonded topologies of a few to a few hundred
+ *     partners per particle cost milliseconds, a row of 10^5 ids seconds).  A table that fits the buffers of the one it
+ *     replaces is written into them.  Synchronous: waits for the device, finishes a pending build, and forces the next
+ *     nl_update_list to build (its reason (a)).  NL_ERR_NOMEM (no room for the pre-exclusion buffers) leaves no table.
+ *     n_pairs == 0 or pairs_dev == NULL clears the table: builds are the plain ones again.
+ *   nl_get_exclusions: the handle's table as a device CSR, symmetric, per-row ascending, without duplicates:
+ *     offsets[n + 1], ids[offsets[n]]; *n_unique = distinct unordered pairs.  NL_ERR_STATE when no table is set.
+ *     The pointers stay valid until the table is set, cleared or relabelled.
+ *   Builds: a build whose n differs from the table's is NL_ERR_ARG.  Slab builds (nl_make_list_slab with a slab, ids
+ *     or the _begin / _finish pair) and distributed builds are NL_ERR_STATE while a table is set.
+ *   Capacity is counted BEFORE exclusion: the build writes the unfiltered list first (into a buffer of its own, then a
+ *     stage compacts it into the list the getters return), so NL_ERR_CAPACITY and the growth of a synchronous build
+ *     follow the unfiltered total.  While a table is set the handle holds a second list of the same capacity and a
+ *     second offset array.
+ *   Re-sorting: the first nl_resort after a build relabels the table by that build's cell order, once:
+ *     (a, b) -> (inv[a], inv[b]) with inv[order[s]] = s, so that the next build excludes the same physical pairs.  This
+ *     holds for whatever table is set at that call, also one set after the build (in the order the build was given).
+ *     The relabelled table stays in the same device buffers, so a graph the caller captured keeps reading it.  A
+ *     caller who permutes its arrays with nl_get_cell_order itself must set the table again.
+ *   Builds refuse with NL_ERR_NOMEM while the pre-exclusion buffers could not be (re)allocated.
+ *   Graph replays (nl_set_graph, nl_update_list): setting, clearing or relabelling the table captures again. */
+int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n);
+int nl_get_exclusions(nl_handle_t h, const int32_t** offsets_dev, const int32_t** ids_dev, int32_t* n, int64_t* n_unique);
+
 /* ------------------------------------------------------------------------------------------------- results */
 
 /* The CPU class's accessors (neighlist_cpu.hpp:437-463): key_pointer()[N+1], sorted_list()[P],

@@ -55,6 +55,8 @@ PROTOTYPES = {
     "nl_set_skin": (C.c_int, [_P, _D]),
     "nl_update_list": (C.c_int, [_P, _P, _I32, _I32, _P, C.c_int]),
     "nl_get_update_stats": (C.c_int, [_P, C.POINTER(_I64 * 2)]),
+    "nl_set_exclusions": (C.c_int, [_P, _P, _I64, _I32]),
+    "nl_get_exclusions": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I32), C.POINTER(_I64)]),
     "nl_get_full_transposed": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I32)]),
     "nl_number_of_pairs": (C.c_int, [_P, C.POINTER(_I64)]),
     "nl_get_mesh": (C.c_int, [_P, C.POINTER(_I32 * 3), C.POINTER(_I64)]),

@@ -23,12 +23,17 @@ struct HostResult {
   uint32_t status;
   uint32_t tickets[17];
   uint32_t total_lo, total_hi;
+  uint32_t bin_words[2];      // (k_bin_bucket's META_BIN_STATUS / META_BIN_DONE; zero between builds)
+  uint32_t kept_lo, kept_hi;  // (copied only by builds with an exclusion table: the list total after the stage)
   int64_t total() const { return (int64_t)(((uint64_t)total_hi << 32) | total_lo); }
+  int64_t kept() const { return (int64_t)(((uint64_t)kept_hi << 32) | kept_lo); }
 };
 constexpr int META_TOTAL = 18;  // int32 offset of total_lo from the status word
 constexpr int META_FULL27 = 1;  // number of cells the COUNT sweep hands to the batched search (first "ticket" word)
 constexpr int META_FILL_LIST = 10;  // number of cells k_fill_masks hands to k_fill_list ("ticket" word 10)
 constexpr int META_WORDS = 20;
+constexpr int META_KEPT = 22;        // the list total after the exclusion stage (nl_exclude.inc), in the same copy
+constexpr int META_WORDS_EXCL = 24;  // (words 20, 21: k_bin_bucket's, META_BIN_STATUS / META_BIN_DONE)
 // k_sweep_list_f32 / k_fill_list are launched until this many builds in a row have been enqueued since one was seen to
 // hand them cells (and always by a build that runs one again)
 constexpr int32_t LIST_QUIET_BUILDS = 4;
@@ -134,11 +139,12 @@ struct nl_handle_s {
     double skin = 0;                // ... and the skin its check was captured with
     int64_t capacity = 0;
     uint64_t epoch = 0;
+    uint64_t excl = 0;              // generation of the exclusion table (nl_set_exclusions)
     bool operator==(const GraphKey& o) const {
       return q == o.q && gid == o.gid && stride == o.stride && n_rows == o.n_rows && n == o.n && z_lo == o.z_lo &&
              mzl == o.mzl && slab == o.slab && list_kind == o.list_kind && pbc_mask == o.pbc_mask && offset_width == o.offset_width &&
              cap_row == o.cap_row && list == o.list && update == o.update && skin == o.skin && capacity == o.capacity &&
-             epoch == o.epoch;
+             epoch == o.epoch && excl == o.excl;
     }
   } graph_key;
   uint64_t buffers_epoch = 1;  // bumped by every (re)allocation
@@ -182,6 +188,19 @@ struct nl_handle_s {
   bool last_update = false;        // the build enqueued last is an update's (complete without finish())
   const void* upd_q = nullptr;     // positions, stride and n of that build
   int32_t upd_stride = 0, upd_n = 0;
+
+  // nl_set_exclusions (nl_exclude.inc): pairs left out of the list by a stage behind the search
+  int32_t* ex_off = nullptr;       // the table: [ex_n + 1] row offsets, symmetric, per-row ascending, no duplicates
+  int32_t* ex_ids = nullptr;       // (nullptr: no table)
+  int32_t ex_n = 0;                // particle count of the builds it applies to
+  int64_t ex_unique = 0;           // distinct unordered pairs
+  uint64_t ex_gen = 0;             // bumped by a set, a clear or a relabel (part of the graph key)
+  int64_t ex_off_cap = 0, ex_ids_cap = 0;  // entries the table's two buffers hold (a table that fits is written in place)
+  bool ex_relabel = false;         // a build ran since the last nl_resort: the next one relabels the table, if any
+  void* kp_pre = nullptr;          // with a table: the offsets and the list the search writes, before the stage
+  int32_t* list_pre = nullptr;     // (one offset array and one list capacity, allocated only while a table is set)
+  int64_t pre_capacity = -1, pre_rows = -1;
+  bool b_excl = false;             // this build runs the exclusion stage
 };
 
 namespace {
@@ -200,6 +219,19 @@ int fail(nl_handle_t h, int code) {
   if (h) h->last_error = code;
   return code;
 }
+
+// nl_exclude.inc
+int excl_reserve(nl_handle_t h);
+bool excl_ready(nl_handle_t h);
+int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s);
+int excl_relabel(nl_handle_t h);
+
+// Where the search kernels write the offsets and the list: the getters' buffers, or with an exclusion table the
+// pre-exclusion ones that the stage compacts from.
+void* search_kp(nl_handle_t h) { return h->b_excl ? h->kp_pre : h->key_pointer; }
+int32_t* search_list(nl_handle_t h) { return h->b_excl ? h->list_pre : h->list; }
+// Entries of the last build's list (after the stage, if it ran); growth keeps using the unfiltered total.
+int64_t list_total(nl_handle_t h) { return h->b_excl ? h->host->kept() : h->host->total(); }
 
 template <typename P> int dev_alloc(nl_handle_t h, P** p, size_t bytes) {
   h->buffers_epoch++;  // a captured graph holds the old pointers
@@ -287,10 +319,10 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.rc2 = sizeof(T) == 4 ? (T)h->rc2_f : (T)h->rc2;
   a.count = h->count;
   a.progress = h->progress;
-  a.key_pointer = h->key_pointer;
+  a.key_pointer = search_kp(h);
   a.wide = h->b_wide ? 1 : 0;
   a.n_rows = h->n_rows;
-  a.list = h->list;
+  a.list = search_list(h);
   a.total = h->totals + 1;
   a.capacity = h->capacity;
   a.status = h->status;
@@ -322,8 +354,8 @@ RowsArgs rows_args(nl_handle_t h) {
   a.rc2 = h->rc2_f;
   a.count = h->count;
   a.masks = h->masks;
-  a.key_pointer = h->key_pointer;
-  a.list = h->list;
+  a.key_pointer = search_kp(h);
+  a.list = search_list(h);
   a.total = h->totals + 1;
   a.capacity = h->capacity;
   a.status = h->status;
@@ -358,7 +390,7 @@ template <typename T, bool FULL, bool PBC, typename OFF> void launch_fill_masks(
   if (h->b_mask_nb > 1) {  // dense build: mask rows per (slot, LDS batch); list offsets gathered into cell order first
     const int32_t nbp = (h->n + 255) / 256;
     if (h->n > 0)
-      hipLaunchKernelGGL(k_row_base<OFF>, dim3(nbp), dim3(256), 0, s, static_cast<const OFF*>(h->key_pointer), h->sorted_row,
+      hipLaunchKernelGGL(k_row_base<OFF>, dim3(nbp), dim3(256), 0, s, static_cast<const OFF*>(search_kp(h)), h->sorted_row,
                          h->n_rows, h->n, static_cast<OFF*>(h->base_sorted), h->gate);
     hipLaunchKernelGGL((k_fill_dense<T, FULL, PBC, OFF>), dim3(ncells_i), dim3(FD_WAVES * WAVE), 0, s, a,
                        static_cast<const OFF*>(h->base_sorted));
@@ -509,6 +541,8 @@ void set_build_state(nl_handle_t h, const void* q_dev, int32_t stride, const int
   h->b_full = h->list_kind == NL_LIST_FULL;
   h->b_pbc = h->pbc;
   h->b_variant = h->sweep_variant;
+  h->b_excl = h->ex_ids != nullptr;
+  h->ex_relabel = true;  // (the cell order nl_resort applies is this build's)
   // Hit masks pay off while a cell's stencil fits one LDS batch; where the mean stencil (27 cells) is close to or
   // beyond the batch size most cells would fall back to a re-search in small batches, so use two full sweeps there.
   const double mean_stream = ncl > 0 ? 27.0 * n / (double)ncl : 0.0;
@@ -578,6 +612,8 @@ int enqueue_build(nl_handle_t h, const void* q_dev, int32_t stride, const int32_
   // against an inconsistent cell table: no split there)
   const bool split = part != PART_ALL && two_level && slab;
   set_build_state<T>(h, q_dev, stride, gid, h->b_dyn ? h->b_n_est : n, z_lo, mzl, slab, !split);
+  if (h->b_excl && (n != h->ex_n || slab || gid || h->b_dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
+  if (h->b_excl && !excl_ready(h)) return fail(h, NL_ERR_NOMEM);  // (the search would write through a missing buffer)
   if (part != PART_ALL && !split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
     if (part == PART_BEGIN) return NL_OK;
     part = PART_ALL;
@@ -678,19 +714,23 @@ int enqueue_build(nl_handle_t h, const void* q_dev, int32_t stride, const int32_
   launch_sweep<T>(h, MODE_COUNT, s);
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_ROW_SCAN], s));
   if (h->b_wide) {
-    if (int rc = launch_scan(h, h->count, n_rows, static_cast<int64_t*>(h->key_pointer), h->totals + 1, s, h->status + META_TOTAL)) return rc;
+    if (int rc = launch_scan(h, h->count, n_rows, static_cast<int64_t*>(search_kp(h)), h->totals + 1, s, h->status + META_TOTAL)) return rc;
   } else {
-    if (int rc = launch_scan(h, h->count, n_rows, static_cast<int32_t*>(h->key_pointer), h->totals + 1, s, h->status + META_TOTAL)) return rc;
+    if (int rc = launch_scan(h, h->count, n_rows, static_cast<int32_t*>(search_kp(h)), h->totals + 1, s, h->status + META_TOTAL)) return rc;
   }
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_FILL], s));
   launch_sweep<T>(h, MODE_FILL, s);
+  // the exclusion table: the unfiltered list compacted into the getters' buffers (counted in the FILL stage)
+  if (h->b_excl)
+    if (int rc = launch_exclude(h, n_rows, s)) return rc;
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_TOTAL], s));
   HIPCHK(h, hipGetLastError());
   return NL_OK;
 }
 
 int enqueue_result_copy(nl_handle_t h, hipStream_t s) {
-  HIPCHK(h, hipMemcpyAsync(h->host, h->status, sizeof(uint32_t) * META_WORDS, hipMemcpyDeviceToHost, s));
+  const int words = h->b_excl ? META_WORDS_EXCL : META_WORDS;
+  HIPCHK(h, hipMemcpyAsync(h->host, h->status, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s));
   return NL_OK;
 }
 
@@ -713,7 +753,7 @@ int estimate_capacity(nl_handle_t h) {
     if (int rc = dev_alloc(h, &h->list, 4 * (size_t)want)) return rc;
     h->capacity = want;
   }
-  return NL_OK;
+  return excl_reserve(h);
 }
 
 int grow_list(nl_handle_t h, int64_t need) {
@@ -726,7 +766,7 @@ int grow_list(nl_handle_t h, int64_t need) {
     return rc;
   }
   h->capacity = cap;
-  return NL_OK;
+  return excl_reserve(h);
 }
 
 // The last build once more, from its own arguments, with the two-pass binning and every launch of its path; waits for it.
@@ -776,7 +816,8 @@ int finish(nl_handle_t h, bool may_grow) {
       launch_sweep<float>(h, MODE_FILL, h->last_stream);
     else
       launch_sweep<double>(h, MODE_FILL, h->last_stream);
-    rc = enqueue_result_copy(h, h->last_stream);
+    if (h->b_excl) rc = launch_exclude(h, h->n_rows, h->last_stream);  // (the refilled list is the unfiltered one)
+    if (!rc) rc = enqueue_result_copy(h, h->last_stream);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
     st = h->host->status;
@@ -808,7 +849,7 @@ int key_pointer_as(nl_handle_t h, int width, const void** out) {
     *out = h->key_pointer;
     return NL_OK;
   }
-  if (!want_wide && h->host->total() > 2147483647LL) return fail(h, NL_ERR_INDEX_OVERFLOW);
+  if (!want_wide && list_total(h) > 2147483647LL) return fail(h, NL_ERR_INDEX_OVERFLOW);
   const int64_t cnt = (int64_t)h->n_rows + 1;
   if (!h->kp_alt) {
     HIPCHK(h, hipSetDevice(h->device));
@@ -894,10 +935,10 @@ int get_csr(nl_handle_t h, bool full, int width, const void** key_pointer_dev, c
   if (h->b_full != full) return fail(h, NL_ERR_STATE);
   if (key_pointer_dev)
     if ((rc = key_pointer_as(h, width, key_pointer_dev))) return rc;
-  if (!key_pointer_dev && width == 32 && h->host->total() > 2147483647LL) return fail(h, NL_ERR_INDEX_OVERFLOW);
+  if (!key_pointer_dev && width == 32 && list_total(h) > 2147483647LL) return fail(h, NL_ERR_INDEX_OVERFLOW);
   if (list_dev) *list_dev = h->list;
   if (number_of_partners_dev) *number_of_partners_dev = h->count;
-  if (nentries) *nentries = h->host->total();
+  if (nentries) *nentries = list_total(h);
   return NL_OK;
 }
 }  // namespace
@@ -1003,7 +1044,8 @@ int nl_destroy(nl_handle_t h) {
   (void)hipSetDevice(h->device);
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
   void* bufs[] = {h->snap, h->skin_words, h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
-                  h->cell_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor};
+                  h->cell_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor,
+                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (h->host) (void)hipHostFree(h->host);
@@ -1081,7 +1123,7 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   h->n_max = n_max;
   if ((rc = estimate_capacity(h))) return rc;
   h->t_valid = false;
-  return NL_OK;
+  return excl_reserve(h);  // (the pre-exclusion offsets follow n_max)
 }
 
 int nl_set_periodic_axes(nl_handle_t h, int mask) {
@@ -1141,7 +1183,7 @@ int nl_set_capacity(nl_handle_t h, int64_t max_pairs) {
   }
   h->capacity = max_pairs;
   h->capacity_user = true;
-  return NL_OK;
+  return excl_reserve(h);
 }
 
 namespace {
@@ -1175,7 +1217,12 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
   } else if (mz - owned < 2) {
     return fail(h, NL_ERR_ARG);  // the two ghost layers would be the same layer
   }
+  // an exclusion table applies to whole single-device builds of its own particle count
+  if (h->ex_ids && (slab || gid_dev || h->b_dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  if (h->ex_ids && n != h->ex_n) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
+  if (h->ex_ids)  // (again, if an allocation failed since the table was set)
+    if (int rc = excl_reserve(h)) return rc;
   if (h->pending) {
     // back-to-back asynchronous builds (the reference's timing loop): errors of the previous one are dropped,
     // exactly like its results; stream order keeps the buffers consistent when the stream is the same.
@@ -1208,6 +1255,7 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
     key.slab = slab, key.list_kind = h->list_kind, key.pbc_mask = h->pbc, key.capacity = h->capacity;
     key.epoch = h->buffers_epoch, key.offset_width = h->offset_width;
     key.cap_row = h->b_cap_row, key.list = h->b_list ? 1 : 0;
+    key.excl = h->ex_gen;
     if (!h->graph_exec || !(key == h->graph_key)) {
       if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec), h->graph_exec = nullptr;
       if (h->graph) (void)hipGraphDestroy(h->graph), h->graph = nullptr;
@@ -1315,7 +1363,7 @@ int nl_list_checksum(nl_handle_t h, uint64_t* checksum, int64_t* nentries) {
   HIPCHK(h, hipMemcpyAsync(&out, acc, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   *checksum = (uint64_t)out;
-  if (nentries) *nentries = h->host->total();
+  if (nentries) *nentries = list_total(h);
   return NL_OK;
 }
 
@@ -1338,6 +1386,11 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream) {
   HIPCHK(h, hipSetDevice(h->device));
   const int32_t n = h->n;
   if (n == 0) return NL_OK;
+  if (h->ex_relabel) {  // the first re-sort after a build: the table follows the particles, once
+    if (h->ex_ids && h->ex_n == n)
+      if ((rc = excl_relabel(h))) return rc;
+    h->ex_relabel = false;
+  }
   if (!h->resort_buf) {
     void* p = nullptr;
     if (hipMalloc(&p, 32 * ((size_t)h->n_max + 16)) != hipSuccess) return fail(h, NL_ERR_NOMEM);
@@ -1378,7 +1431,7 @@ int nl_number_of_pairs(nl_handle_t h, int64_t* npairs) {
   if (!h || !npairs) return fail(h, NL_ERR_ARG);
   int rc = nl_synchronize(h);
   if (rc) return rc;
-  *npairs = h->b_full ? h->host->total() / 2 : h->host->total();
+  *npairs = h->b_full ? list_total(h) / 2 : list_total(h);
   return NL_OK;
 }
 
@@ -1545,3 +1598,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_skin.inc"
 #include "nl_consumer.inc"
 #include "nl_dist.inc"
+#include "nl_exclude.inc"

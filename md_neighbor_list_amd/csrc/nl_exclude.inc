@@ -1,0 +1,371 @@
+// nl_exclude.inc -- excluded pairs (nl_set_exclusions): the bonded partners of a molecular model (1-2, 1-3 pairs) left out of
+// the non-bonded list when it is built, so that the list is filtered once per build and every consumer sees the same list.
+//   The table   a symmetric CSR over input-order particle ids, per-row ascending, without duplicates; built on the device
+//               from the caller's pairs (k_excl_degree .. k_excl_pack), relabelled by the first nl_resort after a build.
+//   The stage   behind the search of a build, on its stream: the search writes the unfiltered offsets and list into
+//               kp_pre / list_pre (search_kp, search_list); k_excl_count counts what each row keeps into `count`, the
+//               row scan turns that into key_pointer (its total into the meta words, META_KEPT), k_excl_compact copies
+//               the kept entries into `list`.  A wave per row; the row's excluded ids are broadcast with readlane, or
+//               binary-searched where a row has more than EXCL_BCAST of them.  Every kernel takes the update's gate.
+// Builds without a table launch none of this and use the buffers they always used.
+// Included at the end of nl_api.hip.
+
+namespace {
+
+constexpr int EXCL_BCAST = 32;  // rows with up to this many excluded ids compare against registers; more: binary search
+constexpr int EXCL_THREADS = 256;
+
+// Is v (a partner of the row) one of the row's excluded ids?  exid: lane l holds ids[xb + l] for l < ne (<= EXCL_BCAST).
+__device__ __forceinline__ bool excl_hit(int32_t v, int32_t exid, int32_t ne, const int32_t* __restrict__ ids, int32_t xb) {
+  if (ne <= EXCL_BCAST) {
+    bool hit = false;
+    for (int32_t t = 0; t < ne; t++) hit |= v == __builtin_amdgcn_readlane(exid, t);  // (ne is uniform)
+    return hit;
+  }
+  int32_t lo = xb, hi = xb + ne;  // first id >= v in the sorted segment
+  while (lo < hi) {
+    const int32_t mid = (lo + hi) >> 1;
+    if (ids[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < xb + ne && ids[lo] == v;
+}
+
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// count[row] = entries of the unfiltered row that the table keeps.  Rows without exclusions do not read the list.
+// (Entries at or past the list capacity were never written: an overflowed build fails, and they are only not read.)
+template <typename OFF>
+__global__ void __launch_bounds__(EXCL_THREADS) k_excl_count(const OFF* __restrict__ kp_pre, const int32_t* __restrict__ list_pre,
+                                                            int32_t n_rows, int64_t capacity, const int32_t* __restrict__ ex_off,
+                                                            const int32_t* __restrict__ ex_ids, int32_t* __restrict__ count,
+                                                            const uint32_t* __restrict__ gate) {
+  if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
+  const int lane = threadIdx.x & 63;
+  const int32_t waves = gridDim.x * (EXCL_THREADS / WAVE);
+  for (int32_t row = blockIdx.x * (EXCL_THREADS / WAVE) + (threadIdx.x >> 6); row < n_rows; row += waves) {
+    const int64_t b = (int64_t)kp_pre[row], e = (int64_t)kp_pre[row + 1];
+    const int32_t xb = ex_off[row], ne = ex_off[row + 1] - xb;
+    int64_t kept = e - b;
+    if (ne > 0) {
+      const int32_t exid = lane < ne && ne <= EXCL_BCAST ? ex_ids[xb + lane] : -1;
+      const int64_t end = e < capacity ? e : capacity;
+      for (int64_t k = b + lane; k - lane < end; k += WAVE) {
+        const int32_t v = k < end ? list_pre[k] : -1;
+        const bool hit = excl_hit(v, exid, ne, ex_ids, xb) & (k < end);  // (no short cut: readlane below)
+        kept -= __builtin_popcountll(__ballot(hit));
+      }
+    }
+    if (lane == 0) count[row] = (int32_t)kept;
+  }
+}
+
+// list[key_pointer[row] ...] = the kept entries of the unfiltered row, in their order (ballot + mbcnt).
+template <typename OFF>
+__global__ void __launch_bounds__(EXCL_THREADS) k_excl_compact(const OFF* __restrict__ kp_pre, const int32_t* __restrict__ list_pre,
+                                                              const OFF* __restrict__ kp, int32_t n_rows, int64_t capacity,
+                                                              const int32_t* __restrict__ ex_off, const int32_t* __restrict__ ex_ids,
+                                                              int32_t* __restrict__ list, const uint32_t* __restrict__ gate) {
+  if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
+  const int lane = threadIdx.x & 63;
+  const int32_t waves = gridDim.x * (EXCL_THREADS / WAVE);
+  for (int32_t row = blockIdx.x * (EXCL_THREADS / WAVE) + (threadIdx.x >> 6); row < n_rows; row += waves) {
+    const int64_t b = (int64_t)kp_pre[row], e = (int64_t)kp_pre[row + 1];
+    const int64_t end = e < capacity ? e : capacity;
+    int64_t dst = (int64_t)kp[row];
+    const int32_t xb = ex_off[row], ne = ex_off[row + 1] - xb;
+    if (ne == 0) {
+      for (int64_t k = b + lane; k < end; k += WAVE) {
+        const int64_t d = dst + (k - b);
+        if (d < capacity) list[d] = list_pre[k];
+      }
+      continue;
+    }
+    const int32_t exid = lane < ne && ne <= EXCL_BCAST ? ex_ids[xb + lane] : -1;
+    for (int64_t k = b + lane; k - lane < end; k += WAVE) {
+      const int32_t v = k < end ? list_pre[k] : -1;
+      const bool keep = !excl_hit(v, exid, ne, ex_ids, xb) & (k < end);
+      const uint64_t mask = __ballot(keep);
+      const int64_t d = dst + lanes_below(mask);
+      if (keep && d < capacity) list[d] = v;
+      dst += __builtin_popcountll(mask);
+    }
+  }
+}
+
+template <typename OFF> int launch_exclude_w(nl_handle_t h, int32_t n_rows, hipStream_t s) {
+  const OFF* kp_pre = static_cast<const OFF*>(h->kp_pre);
+  const int32_t grid = std::max(1, std::min((n_rows + 3) / 4, 16 * h->num_cus));
+  if (n_rows > 0)
+    hipLaunchKernelGGL(k_excl_count<OFF>, dim3(grid), dim3(EXCL_THREADS), 0, s, kp_pre, h->list_pre, n_rows, h->capacity, h->ex_off,
+                       h->ex_ids, h->count, h->gate);
+  if (int rc = launch_scan(h, h->count, n_rows, static_cast<OFF*>(h->key_pointer), h->totals + 2, s, h->status + META_KEPT)) return rc;
+  if (n_rows > 0)
+    hipLaunchKernelGGL(k_excl_compact<OFF>, dim3(grid), dim3(EXCL_THREADS), 0, s, kp_pre, h->list_pre,
+                       static_cast<const OFF*>(h->key_pointer), n_rows, h->capacity, h->ex_off, h->ex_ids, h->list, h->gate);
+  HIPCHK(h, hipGetLastError());
+  return NL_OK;
+}
+
+// (declared at the top of nl_api.hip)
+int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s) {
+  return h->b_wide ? launch_exclude_w<int64_t>(h, n_rows, s) : launch_exclude_w<int32_t>(h, n_rows, s);
+}
+
+// The pre-exclusion offsets and list while a table is set (one offset array, one list capacity); nothing without one.
+int excl_reserve(nl_handle_t h) {
+  if (!h->ex_ids) return NL_OK;
+  if (h->pre_rows < (int64_t)h->n_max) {
+    h->pre_rows = -1;
+    if (int rc = dev_alloc(h, &h->kp_pre, 8 * ((size_t)h->n_max + 32))) return rc;
+    h->pre_rows = h->n_max;
+  }
+  if (h->pre_capacity < h->capacity) {
+    h->pre_capacity = -1;
+    if (int rc = dev_alloc(h, &h->list_pre, 4 * ((size_t)h->capacity + 16))) return rc;
+    h->pre_capacity = h->capacity;
+  }
+  return NL_OK;
+}
+
+bool excl_ready(nl_handle_t h) {
+  return h->kp_pre && h->list_pre && h->pre_rows >= (int64_t)h->n_max && h->pre_capacity >= h->capacity;
+}
+
+// ------------------------------------------------------------------------------------------- the table, on the device
+// deg[a]++, deg[b]++ for every valid pair; an invalid one (out of [0, n), or a == b) sets *bad.
+__global__ void __launch_bounds__(256) k_excl_degree(const int32_t* __restrict__ pairs, int64_t np, int32_t n, int32_t* __restrict__ deg,
+                                                     uint32_t* __restrict__ bad) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < np; e += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t a = pairs[2 * e], b = pairs[2 * e + 1];
+    if (a < 0 || a >= n || b < 0 || b >= n || a == b) {
+      atomicOr(bad, 1u);
+      continue;
+    }
+    atomicAdd(&deg[a], 1);
+    atomicAdd(&deg[b], 1);
+  }
+}
+
+// Both directions of every pair into the rows of off[] (cursor[] zero on entry), in no particular order.
+__global__ void __launch_bounds__(256) k_excl_scatter(const int32_t* __restrict__ pairs, int64_t np, const int32_t* __restrict__ off,
+                                                      int32_t* __restrict__ cursor, int32_t* __restrict__ ids) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < np; e += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t a = pairs[2 * e], b = pairs[2 * e + 1];
+    ids[off[a] + atomicAdd(&cursor[a], 1)] = b;
+    ids[off[b] + atomicAdd(&cursor[b], 1)] = a;
+  }
+}
+
+// A wave per row: every entry goes to its rank in the row (ties by position), so the row comes out ascending.  The rank
+// is counted against the whole row: m^2 / 64 steps, a few for bonded rows (and 625 for a hub of 200).
+__global__ void __launch_bounds__(256) k_excl_sort_rows(const int32_t* __restrict__ off, const int32_t* __restrict__ in, int32_t n,
+                                                        int32_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int32_t waves = gridDim.x * 4;
+  for (int32_t row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += waves) {
+    const int32_t b = off[row], m = off[row + 1] - b;
+    for (int32_t k = lane; k - lane < m; k += WAVE) {
+      const int32_t v = k < m ? in[b + k] : 0;
+      int32_t rank = 0;
+      for (int32_t j = 0; j < m; j++) {
+        const int32_t u = in[b + j];  // (uniform address)
+        rank += u < v || (u == v && j < k);
+      }
+      if (k < m) out[b + rank] = v;
+    }
+  }
+}
+
+// cnt[row] = distinct ids of a sorted row
+__global__ void __launch_bounds__(256) k_excl_distinct(const int32_t* __restrict__ off, const int32_t* __restrict__ ids, int32_t n,
+                                                       int32_t* __restrict__ cnt) {
+  const int lane = threadIdx.x & 63;
+  const int32_t waves = gridDim.x * 4;
+  for (int32_t row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += waves) {
+    const int32_t b = off[row], m = off[row + 1] - b;
+    int32_t c = 0;
+    for (int32_t k = lane; k - lane < m; k += WAVE) {
+      const bool first = k < m && (k == 0 || ids[b + k] != ids[b + k - 1]);
+      c += __builtin_popcountll(__ballot(first));
+    }
+    if (lane == 0) cnt[row] = c;
+  }
+}
+
+// The distinct ids of every sorted row at the row's new offset.
+__global__ void __launch_bounds__(256) k_excl_pack(const int32_t* __restrict__ off, const int32_t* __restrict__ ids, const int32_t* __restrict__ off_new,
+                                                   int32_t n, int32_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int32_t waves = gridDim.x * 4;
+  for (int32_t row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += waves) {
+    const int32_t b = off[row], m = off[row + 1] - b;
+    int32_t dst = off_new[row];
+    for (int32_t k = lane; k - lane < m; k += WAVE) {
+      const bool first = k < m && (k == 0 || ids[b + k] != ids[b + k - 1]);
+      const uint64_t mask = __ballot(first);
+      if (first) out[dst + (int32_t)lanes_below(mask)] = ids[b + k];
+      dst += __builtin_popcountll(mask);
+    }
+  }
+}
+
+// inv[order[s]] = s
+__global__ void __launch_bounds__(256) k_excl_inverse(const int32_t* __restrict__ order, int32_t n, int32_t* __restrict__ inv) {
+  const int32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n) inv[order[s]] = s;
+}
+
+// The table's entries as pairs (inv[row], inv[id]) -- both directions, which the set-up merges again.
+__global__ void __launch_bounds__(256) k_excl_relabel(const int32_t* __restrict__ off, const int32_t* __restrict__ ids, const int32_t* __restrict__ inv,
+                                                      int32_t n, int32_t* __restrict__ pairs) {
+  const int32_t row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  const int32_t r = inv[row];
+  for (int32_t k = off[row]; k < off[row + 1]; k++) {
+    pairs[2 * (int64_t)k] = r;
+    pairs[2 * (int64_t)k + 1] = inv[ids[k]];
+  }
+}
+
+uint32_t excl_grid(int64_t items, int32_t per_block, int32_t max_blocks) {
+  return (uint32_t)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, max_blocks));
+}
+
+// Builds a table from np pairs on the handle's stream and makes it the handle's; validate: pairs out of range or with
+// i == j are NL_ERR_ARG and leave the old table in place.  Synchronous.
+int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool validate) {
+  if (2 * np > 2147483000LL) return fail(h, NL_ERR_ARG);
+  hipStream_t s = h->own_stream;
+  const size_t rows = (size_t)n + 32, ents = 2 * (size_t)np + 16;
+  int32_t *deg = nullptr, *off_raw = nullptr, *raw = nullptr, *srt = nullptr, *off_new = nullptr;
+  uint32_t* bad = nullptr;
+  auto release = [&]() {
+    for (void* p : {(void*)deg, (void*)off_raw, (void*)raw, (void*)srt, (void*)off_new, (void*)bad})
+      if (p) (void)hipFree(p);
+  };
+  auto run = [&]() -> int {
+    if (hipMalloc(reinterpret_cast<void**>(&deg), 4 * rows) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&off_raw), 4 * rows) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&raw), 4 * ents) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&srt), 4 * ents) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&off_new), 4 * rows) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&bad), 16) != hipSuccess)
+      return fail(h, NL_ERR_NOMEM);
+    HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
+    HIPCHK(h, hipMemsetAsync(bad, 0, 16, s));
+    const uint32_t pgrid = excl_grid(np, 256, 8 * h->num_cus), rgrid = excl_grid(n, 4, 16 * h->num_cus);
+    if (np > 0) hipLaunchKernelGGL(k_excl_degree, dim3(pgrid), dim3(256), 0, s, pairs, np, n, deg, bad);
+    HIPCHK(h, hipGetLastError());
+    if (validate) {
+      uint32_t b = 0;
+      HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(h, hipStreamSynchronize(s));
+      if (b) return fail(h, NL_ERR_ARG);
+    }
+    if (int rc = launch_scan(h, deg, n, off_raw, h->totals + 2, s)) return rc;
+    HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
+    if (np > 0) hipLaunchKernelGGL(k_excl_scatter, dim3(pgrid), dim3(256), 0, s, pairs, np, off_raw, deg, raw);
+    if (n > 0) {
+      hipLaunchKernelGGL(k_excl_sort_rows, dim3(rgrid), dim3(256), 0, s, off_raw, raw, n, srt);
+      hipLaunchKernelGGL(k_excl_distinct, dim3(rgrid), dim3(256), 0, s, off_raw, srt, n, deg);
+    }
+    if (int rc = launch_scan(h, deg, n, off_new, h->totals + 2, s)) return rc;
+    if (n > 0) hipLaunchKernelGGL(k_excl_pack, dim3(rgrid), dim3(256), 0, s, off_raw, srt, off_new, n, raw);
+    HIPCHK(h, hipGetLastError());
+    int32_t entries = 0;
+    HIPCHK(h, hipMemcpyAsync(&entries, off_new + n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (h->ex_ids && (int64_t)n + 1 <= h->ex_off_cap && (int64_t)entries <= h->ex_ids_cap) {
+      // into the buffers the table has: a graph the caller captured (an update, forces) keeps finding it there -- a
+      // relabel always fits (same n, same entries)
+      HIPCHK(h, hipMemcpyAsync(h->ex_off, off_new, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
+      HIPCHK(h, hipMemcpyAsync(h->ex_ids, raw, 4 * (size_t)entries, hipMemcpyDeviceToDevice, s));
+      HIPCHK(h, hipStreamSynchronize(s));
+    } else {  // the new table replaces the old one
+      h->buffers_epoch++;
+      if (h->ex_off) (void)hipFree(h->ex_off);
+      if (h->ex_ids) (void)hipFree(h->ex_ids);
+      h->ex_off = off_new, h->ex_ids = raw;
+      h->ex_off_cap = (int64_t)rows, h->ex_ids_cap = (int64_t)ents;
+      off_new = raw = nullptr;
+    }
+    h->ex_n = n;
+    h->ex_unique = entries / 2;
+    h->ex_gen++;
+    return NL_OK;
+  };
+  const int rc = run();
+  release();
+  return rc;
+}
+
+void excl_clear(nl_handle_t h) {
+  void* bufs[] = {h->ex_off, h->ex_ids, h->kp_pre, h->list_pre};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  h->ex_off = h->ex_ids = nullptr;
+  h->kp_pre = nullptr, h->list_pre = nullptr;
+  h->pre_capacity = h->pre_rows = -1;
+  h->ex_n = 0, h->ex_unique = 0;
+  h->ex_off_cap = h->ex_ids_cap = 0;
+  h->ex_gen++;
+  h->buffers_epoch++;
+}
+
+// (declared at the top of nl_api.hip) The table in the cell order of the last build: (a, b) -> (inv[a], inv[b]).
+int excl_relabel(nl_handle_t h) {
+  const int32_t n = h->ex_n;
+  const int64_t entries = 2 * h->ex_unique;
+  int32_t *inv = nullptr, *pairs = nullptr;
+  hipStream_t s = h->own_stream;
+  HIPCHK(h, hipDeviceSynchronize());  // (replays of a graph the caller captured may still read the table)
+  int rc = NL_OK;
+  if (hipMalloc(reinterpret_cast<void**>(&inv), 4 * ((size_t)n + 16)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&pairs), 8 * ((size_t)entries + 16)) != hipSuccess) {
+    rc = fail(h, NL_ERR_NOMEM);
+  } else if (n > 0) {
+    hipLaunchKernelGGL(k_excl_inverse, dim3((n + 255) / 256), dim3(256), 0, s, h->sorted_row, n, inv);
+    hipLaunchKernelGGL(k_excl_relabel, dim3((n + 255) / 256), dim3(256), 0, s, h->ex_off, h->ex_ids, inv, n, pairs);
+    if (hipGetLastError() != hipSuccess) rc = fail(h, NL_ERR_HIP);
+    if (!rc) rc = excl_build(h, pairs, entries, n, false);
+  }
+  if (inv) (void)hipFree(inv);
+  if (pairs) (void)hipFree(pairs);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n) {
+  if (!h || n_pairs < 0) return fail(h, NL_ERR_ARG);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->pending) (void)finish(h, false);
+  if (n_pairs == 0 || !pairs_dev) {
+    if (h->ex_ids) excl_clear(h);
+    h->upd_valid = false;
+    return NL_OK;
+  }
+  if (n < 0 || n > h->n_max) return fail(h, NL_ERR_ARG);
+  HIPCHK(h, hipDeviceSynchronize());  // (the caller's pairs may come from any stream)
+  if (int rc = excl_build(h, pairs_dev, n_pairs, n, true)) return rc;
+  h->upd_valid = false;
+  if (int rc = excl_reserve(h)) {  // no room for the pre-exclusion buffers: no table
+    excl_clear(h);
+    return rc;
+  }
+  return NL_OK;
+}
+
+int nl_get_exclusions(nl_handle_t h, const int32_t** offsets_dev, const int32_t** ids_dev, int32_t* n, int64_t* n_unique) {
+  if (!h) return NL_ERR_ARG;
+  if (!h->ex_ids) return fail(h, NL_ERR_STATE);
+  if (offsets_dev) *offsets_dev = h->ex_off;
+  if (ids_dev) *ids_dev = h->ex_ids;
+  if (n) *n = h->ex_n;
+  if (n_unique) *n_unique = h->ex_unique;
+  return NL_OK;
+}
+
+}  // extern "C"

@@ -138,11 +138,14 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
   if (!h) return NL_ERR_ARG;
   if (h->n_max <= 0 && n > 0) return fail(h, NL_ERR_STATE);
   if (n < 0 || n > h->n_max || (q_stride != 3 && q_stride != 4) || (!q_dev && n > 0)) return fail(h, NL_ERR_ARG);
+  if (h->ex_ids && n != h->ex_n) return fail(h, NL_ERR_ARG);  // (nl_set_exclusions)
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIPCHK(h, hipStreamIsCapturing(s, &cap));
   const bool capturing = cap != hipStreamCaptureStatusNone;
+  if (h->ex_ids && !capturing)  // (again, if an allocation failed since the table was set)
+    if (int rc = excl_reserve(h)) return rc;
   // (a): what forces a build before any particle is looked at -- no list of an update to keep (a setter, nl_resort or
   // another kind of build since, the host has seen the last build fail), or other positions
   const bool force = !h->upd_valid || q_dev != h->upd_q || q_stride != h->upd_stride || n != h->upd_n || (!h->pending && !h->built);
@@ -183,6 +186,7 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
     key.epoch = h->buffers_epoch, key.offset_width = h->offset_width;
     key.cap_row = h->b_cap_row, key.list = h->b_list ? 1 : 0;
     key.update = 1, key.skin = h->skin;
+    key.excl = h->ex_gen;
     if (!h->graph_exec || !(key == h->graph_key)) {
       if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec), h->graph_exec = nullptr;
       if (h->graph) (void)hipGraphDestroy(h->graph), h->graph = nullptr;

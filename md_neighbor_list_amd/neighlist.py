@@ -172,6 +172,37 @@ class NeighListGPU:
         check(self._lib.nl_get_update_stats(self._h, C.byref(st)), "nl_get_update_stats")
         return int(st[0]), int(st[1])
 
+    # ------------------------------------------------------------------ excluded pairs
+    def set_exclusions(self, pairs, particle_number):
+        """Leaves the pairs of ``pairs`` out of every later build (nl_set_exclusions): an ``(E, 2)`` int32/int64 tensor or
+        array of input-order particle indices (duplicates and both orders allowed) for builds of ``particle_number``
+        particles.  Bonded partners of a molecular model; capacity is still counted before exclusion."""
+        if isinstance(pairs, torch.Tensor):
+            t = pairs
+        else:
+            import numpy as np
+
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(pairs)))
+        if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != 2:
+            raise TypeError("pairs must be an (E, 2) int32 or int64 tensor or array")
+        if t.dtype == torch.int64 and t.numel() and (int(t.min()) < -2**31 or int(t.max()) >= 2**31):
+            raise ValueError("pairs hold an index outside the int32 range")  # (a cast would wrap it onto a valid id)
+        t = t.to(device=self.device, dtype=torch.int32).contiguous()
+        check(self._lib.nl_set_exclusions(self._h, t.data_ptr() if t.shape[0] else None, int(t.shape[0]), int(particle_number)),
+              "nl_set_exclusions")
+
+    def clear_exclusions(self):
+        """Drops the exclusion table: later builds list every pair again."""
+        check(self._lib.nl_set_exclusions(self._h, None, 0, 0), "nl_set_exclusions")
+
+    def exclusions(self):
+        """(offsets[n + 1], ids) of the exclusion table (nl_get_exclusions): symmetric, per-row ascending, without
+        duplicates; views valid until the table is set, cleared or relabelled by resort()."""
+        off, ids, n, nu = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int64()
+        check(self._lib.nl_get_exclusions(self._h, C.byref(off), C.byref(ids), C.byref(n), C.byref(nu)), "nl_get_exclusions")
+        return (_as_tensor(off.value, (n.value + 1,), "<i4", self, self.device),
+                _as_tensor(ids.value, (2 * nu.value,), "<i4", self, self.device))
+
     GID_IN_W = "w"  # MakeNeighListSlab(gid=GID_IN_W): ids are stored in q[:, 3] as integer bit patterns (NL_GID_IN_W)
 
     def MakeNeighListSlab(self, q, gid, n_rows, z_lo, z_hi, sync=True):
