@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <tuple>
 
 #include "nl_kernels.hpp"
 
@@ -37,6 +38,67 @@ constexpr int META_WORDS_EXCL = 24;  // (words 20, 21: k_bin_bucket's, META_BIN_
 // k_sweep_list_f32 / k_fill_list are launched until this many builds in a row have been enqueued since one was seen to
 // hand them cells (and always by a build that runs one again)
 constexpr int32_t LIST_QUIET_BUILDS = 4;
+
+// What a build was called with.  A whole-box build has slab == 0, mzl == mz, z_lo == 0.
+struct BuildArgs {
+  const void* q = nullptr;
+  int32_t stride = 4;
+  const int32_t* gid = nullptr;
+  int32_t n_rows = 0, n = 0;
+  int32_t n_ghost_lo = 0;  // slab build: ghosts of the lower layer (the split binning places them in front)
+  int32_t z_lo = 0, mzl = 0, slab = 0;
+  // nl_make_list_distributed: the ghost counts of the build live on the device (dyn[0], dyn[1]; n is an upper bound);
+  // dyn_host: where their pinned copy (words 2, 3) and the exchange's error flags (word 4) arrive with the build's result
+  const int32_t* dyn = nullptr;
+  const int32_t* dyn_host = nullptr;
+  int32_t n_est = 0;  // (dyn) particles expected: owned + the previous build's ghosts; path selection only
+  auto tie() const { return std::tie(q, stride, gid, n_rows, n, n_ghost_lo, z_lo, mzl, slab, dyn, dyn_host, n_est); }
+  bool operator==(const BuildArgs& o) const { return tie() == o.tie(); }
+};
+
+enum Binning : int32_t {
+  BINNING_BUCKET,    // one pass into row buckets of cap_row slots (k_bin_bucket)
+  BINNING_TWO_PASS,  // row totals, then the scatter (k_bin_rows, k_bin_scatter); split into owned + ghosts for a split slab build
+  BINNING_ATOMIC,    // atomic ranks into the cell histogram (k_hash, k_reorder): NL_BINNING=1 and meshes beyond the row tables
+};
+enum Search : int32_t {
+  SEARCH_ROWS,    // fine rows (nl_rows.hpp): fp32, open box
+  SEARCH_MASKS,   // COUNT keeps a hit mask per sorted slot (one LDS batch), the expansion writes the list from them
+  SEARCH_DENSE,   // hit masks for mask_nb LDS batches per slot, k_fill_dense
+  SEARCH_SWEEPS,  // COUNT and FILL distance sweeps
+};
+
+// Every choice the launches of a build depend on, made by plan_build.
+struct BuildPlan {
+  int32_t binning = BINNING_ATOMIC;
+  int32_t cap_row = 0;  // BINNING_BUCKET: slots a row
+  bool split = false;   // a slab build in two parts (owned rows at PART_BEGIN, ghosts at PART_FINISH)
+  int32_t search = SEARCH_SWEEPS;
+  int32_t rows_v = 0;   // SEARCH_ROWS: RowsCfg
+  int32_t mask_nb = 1;  // mask rows per sorted slot: > 1 for SEARCH_DENSE (and in a fine-row build as dense)
+  bool small = false;   // SEARCH_MASKS, fp32 open box, sparse: the 2-wave COUNT (k_sweep_lean_f32) and 1-wave expansion
+  bool rows12 = false;  // SEARCH_MASKS: the expansion loads 12 rows a wave up front, not 24
+  bool list = true;     // k_sweep_list_f32 / k_fill_list are launched (SEARCH_MASKS: the paths with those two kernels)
+  bool full = false;    // full list (both directions), nl_set_list_kind
+  bool wide = false;    // key_pointer / base_sorted hold int64 (the list may exceed INT32_MAX entries)
+  bool excl = false;    // the exclusion stage runs (nl_exclude.inc)
+  int32_t pbc = 0;      // axes of the minimum image (nl_set_periodic_axes)
+  auto tie() const { return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, excl, pbc); }
+  bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
+};
+
+// What a captured graph was captured from (NL_GRAPH): replayed while the key is the same.
+struct GraphKey {
+  BuildArgs args;
+  BuildPlan plan;
+  int64_t capacity = 0;
+  uint64_t buffers_epoch = 0;
+  uint64_t ex_gen = 0;  // generation of the exclusion table (nl_set_exclusions)
+  int32_t update = 0;   // 1: nl_update_list's chain (check, gated build, snapshot, result copy) ...
+  double skin = 0;      // ... and the skin its check was captured with
+  auto tie() const { return std::tie(args, plan, capacity, buffers_epoch, ex_gen, update, skin); }
+  bool operator==(const GraphKey& o) const { return tie() == o.tie(); }
+};
 
 }  // namespace
 
@@ -85,19 +147,10 @@ struct nl_handle_s {
   uint32_t* masks = nullptr;       // [n][64] hit bits of every sorted slot, between COUNT_MASKS and k_fill_masks
   int32_t* full27_list = nullptr;
   void* resort_buf = nullptr;      // scratch of nl_resort (32 bytes per particle), allocated on first use
-  int32_t b_mask_nb = 1;           // this build: mask rows per sorted slot (> 1: dense build, k_fill_dense)
   size_t masks_bytes = 0;          // size of the masks allocation
-  int32_t b_isplit = 1;            // this build, two-sweep path: workgroups per cell
-  int isplit_env = 0;              // NL_ISPLIT: 0 = by density
   int rows_env = -1;               // NL_ROWS: -1 (default) = the fine-row search where the 27-cell path would need several LDS batches
                                    // per cell (denser than 40.3 particles per cell), 0 = never, 1..3 = RowsCfg<V - 1> wherever a
                                    // build qualifies (tests), 4 = wherever a build qualifies, RowsCfg by density (sweeps)
-  bool b_lean_small = false;       // this build: the 2-wave, half-buffer instance of k_sweep_lean_f32 (sparse boxes)
-  int lean_small_env = 1;          // NL_LEAN_SMALL=0: never (same-box A/B)
-  int fill_small_env = 1;          // NL_FILL_SMALL=0: the 2-wave expansion also in sparse boxes (same-box A/B)
-  bool b_rows = false;             // this build: fine rows (k_bin_cells<FINE>, k_sweep_rows_f32, k_fill_rows); the cell table is
-  int b_rows_v = 0;                // fine_start (4 M + 1 entries); RowsCfg of the build
-  bool dense_masks_off = false;    // NL_DENSE_MASKS=0: dense builds use two distance sweeps (the round-1 path)
   size_t dense_masks_limit = (size_t)64 << 30;  // most memory the mask rows of a dense build may take
   int sweep_variant = 3;           // 1: COUNT + FILL distance sweeps;
                                    // 3 (default): COUNT keeping hit masks + mask expansion
@@ -105,9 +158,7 @@ struct nl_handle_s {
                                    // in round 1 and removed)
   int num_cus = 256;
   unsigned long long* dbg_buf = nullptr;
-  int dbg_flags = 0, dbg_wg_per_cu = 4;  // diagnostics (NL_DEBUG_FLAGS, NL_DEBUG_WG_PER_CU)
-  int dbg_lds_pad = 0;                   // diagnostics (NL_DEBUG_LDS_PAD): extra dynamic LDS bytes on the COUNT_MASKS
-                                         // launch = fewer resident workgroups per CU (occupancy experiments)
+  int dbg_flags = 0;  // diagnostics (NL_DEBUG_FLAGS)
   int32_t* cell_count = nullptr;  // [ncell] followed by the status word
   int32_t* cell_start = nullptr;  // [ncell + 1]
   uint64_t* scan_look = nullptr;  // k_scan_chained: [scan_blocks] entries + the two counters; all zero between launches
@@ -130,53 +181,21 @@ struct nl_handle_s {
   bool use_graph = false;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
-  struct GraphKey {
-    const void* q = nullptr;
-    const int32_t* gid = nullptr;
-    int32_t stride = 0, n_rows = 0, n = 0, z_lo = 0, mzl = 0, slab = 0, list_kind = 0, pbc_mask = 0, offset_width = 0;
-    int32_t cap_row = 0, list = 0;  // the captured binning and search launches (b_cap_row, b_list)
-    int32_t update = 0;             // 1: nl_update_list's chain (check, gated build, snapshot, result copy)
-    double skin = 0;                // ... and the skin its check was captured with
-    int64_t capacity = 0;
-    uint64_t epoch = 0;
-    uint64_t excl = 0;              // generation of the exclusion table (nl_set_exclusions)
-    bool operator==(const GraphKey& o) const {
-      return q == o.q && gid == o.gid && stride == o.stride && n_rows == o.n_rows && n == o.n && z_lo == o.z_lo &&
-             mzl == o.mzl && slab == o.slab && list_kind == o.list_kind && pbc_mask == o.pbc_mask && offset_width == o.offset_width &&
-             cap_row == o.cap_row && list == o.list && update == o.update && skin == o.skin && capacity == o.capacity &&
-             epoch == o.epoch && excl == o.excl;
-    }
-  } graph_key;
+  GraphKey graph_key;
   uint64_t buffers_epoch = 1;  // bumped by every (re)allocation
   bool begun = false;  // nl_make_list_slab_begin has run, nl_make_list_slab_finish has not
-  int32_t begun_ghost_lo = 0, begun_zlo = 0, begun_zhi = 0;
   hipStream_t last_stream = nullptr;
   hipEvent_t ev[NL_NUM_STAGES + 1] = {};
 
-  // state of the last build
-  int32_t b_cap_row = 0;     // this build: k_bin_bucket's bucket size (0: the two-pass binning)
-  bool b_list = true;        // this build launches k_sweep_list_f32 / k_fill_list (if its path has them)
+  // the last build enqueued (adopt_build): its arguments (finish() and the profiler run it again from them) and its plan
+  // (how finish(), a refill after growth and the getters read its buffers)
+  BuildArgs args;
+  BuildPlan plan;
   int32_t list_quiet = 0;    // builds enqueued since one was seen to hand cells to k_sweep_list_f32 / k_fill_list
-  bool rerun = false;        // the build being enqueued runs one again (finish): two-pass binning, every launch
   int64_t reruns[2] = {0, 0};  // builds run again: [0] a row overflowed its bucket, [1] cells listed without the launches
   bool built = false, pending = false;
-  int32_t n = 0, n_rows = 0;
-  int64_t ncell_local = 0;
+  int32_t n = 0, n_rows = 0;  // (a distributed build: n is its upper bound until finish() reads the ghost counts)
   int last_error = NL_OK, last_hip = 0;
-  // arguments of the last build (to re-run the fill after growing the list)
-  int32_t b_mzl = 0, b_slab = 0, b_zlo = 0, b_stride = 4;
-  bool b_use_masks = false;  // this build: COUNT keeps hit masks and the list is expanded from them
-  bool b_wide = false;       // this build: key_pointer / base_sorted hold int64 (the list may exceed INT32_MAX entries)
-  bool b_full = false;       // this build: full list (both directions), nl_set_list_kind
-  int b_pbc = 0;             // this build: axes of the minimum image (nl_set_periodic_axes)
-  int b_variant = 3;         // sweep variant of this build (a full build uses 1 or 3 only)
-  const void* b_q = nullptr;
-  const int32_t* b_gid = nullptr;
-  // nl_make_list_distributed: the ghost counts of the build live on the device (b_dyn[0], b_dyn[1]; n is an upper bound);
-  // dyn_host: where their pinned copy (words 2, 3) and the exchange's error flags (word 4) arrive with the build's result
-  const int32_t* b_dyn = nullptr;
-  int32_t b_n_est = 0;             // particles expected (owned + the previous build's ghosts): path selection only
-  const int32_t* dyn_host = nullptr;
 
   // nl_update_list (nl_skin.inc): the Verlet-skin rebuild decision on the device
   double skin = 0;                 // nl_set_skin
@@ -200,7 +219,6 @@ struct nl_handle_s {
   void* kp_pre = nullptr;          // with a table: the offsets and the list the search writes, before the stage
   int32_t* list_pre = nullptr;     // (one offset array and one list capacity, allocated only while a table is set)
   int64_t pre_capacity = -1, pre_rows = -1;
-  bool b_excl = false;             // this build runs the exclusion stage
 };
 
 namespace {
@@ -228,10 +246,10 @@ int excl_relabel(nl_handle_t h);
 
 // Where the search kernels write the offsets and the list: the getters' buffers, or with an exclusion table the
 // pre-exclusion ones that the stage compacts from.
-void* search_kp(nl_handle_t h) { return h->b_excl ? h->kp_pre : h->key_pointer; }
-int32_t* search_list(nl_handle_t h) { return h->b_excl ? h->list_pre : h->list; }
+void* search_kp(nl_handle_t h) { return h->plan.excl ? h->kp_pre : h->key_pointer; }
+int32_t* search_list(nl_handle_t h) { return h->plan.excl ? h->list_pre : h->list; }
 // Entries of the last build's list (after the stage, if it ran); growth keeps using the unfiltered total.
-int64_t list_total(nl_handle_t h) { return h->b_excl ? h->host->kept() : h->host->total(); }
+int64_t list_total(nl_handle_t h) { return h->plan.excl ? h->host->kept() : h->host->total(); }
 
 template <typename P> int dev_alloc(nl_handle_t h, P** p, size_t bytes) {
   h->buffers_epoch++;  // a captured graph holds the old pointers
@@ -259,19 +277,19 @@ int status_to_error(uint32_t st) {
   return NL_OK;
 }
 
-template <typename T> Grid<T> make_grid(nl_handle_t h, int32_t n_rows, int32_t z_lo, int32_t mzl, int32_t slab) {
+template <typename T> Grid<T> make_grid(nl_handle_t h, const BuildArgs& a, int pbc) {
   Grid<T> g;
   for (int d = 0; d < 3; d++) {
     g.ims[d] = sizeof(T) == 4 ? (T)h->ims_f[d] : (T)h->ims_d[d];
     g.m[d] = h->m[d];
   }
-  g.mzl = mzl;
-  g.slab = slab;
-  g.z_origin = slab ? ((z_lo - 1) % h->m[2] + h->m[2]) % h->m[2] : 0;
-  g.n_rows = n_rows;
-  g.pbc = h->pbc;
+  g.mzl = a.mzl;
+  g.slab = a.slab;
+  g.z_origin = a.slab ? ((a.z_lo - 1) % h->m[2] + h->m[2]) % h->m[2] : 0;
+  g.n_rows = a.n_rows;
+  g.pbc = pbc;
   g.dbg = h->dbg_flags;
-  g.z_first = slab ? z_lo - 1 : 0;
+  g.z_first = a.slab ? a.z_lo - 1 : 0;
   for (int d = 0; d < 3; d++) g.L[d] = (T)h->L[d];
   g.gate = h->gate;
   return g;
@@ -314,13 +332,13 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.sorted_row = h->sorted_row;
   a.sorted_gid = h->sorted_gid;
   a.cell_start = h->cell_start;
-  a.mx = h->m[0], a.my = h->m[1], a.mzl = h->b_mzl, a.slab = h->b_slab;
+  a.mx = h->m[0], a.my = h->m[1], a.mzl = h->args.mzl, a.slab = h->args.slab;
   a.div_mx = fastdiv_make((uint32_t)h->m[0]), a.div_my = fastdiv_make((uint32_t)h->m[1]);
   a.rc2 = sizeof(T) == 4 ? (T)h->rc2_f : (T)h->rc2;
   a.count = h->count;
   a.progress = h->progress;
   a.key_pointer = search_kp(h);
-  a.wide = h->b_wide ? 1 : 0;
+  a.wide = h->plan.wide ? 1 : 0;
   a.n_rows = h->n_rows;
   a.list = search_list(h);
   a.total = h->totals + 1;
@@ -330,14 +348,14 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   // (the two planes of the hit words, one array each inside the same allocation: 128 + 64 bytes per row)
   a.masks_hi = reinterpret_cast<uint8_t*>(h->masks) + h->masks_bytes / MASK_ROW_BYTES * MASK_LO_BYTES;
   a.isplit = 1;
-  a.mask_nb = h->b_mask_nb;
+  a.mask_nb = h->plan.mask_nb;
   a.full27_list = h->full27_list;
   a.full27_count = reinterpret_cast<int32_t*>(h->status) + META_FULL27;
   a.fill_list_count = reinterpret_cast<int32_t*>(h->status) + META_FILL_LIST;
-  a.pbc = h->pbc;
+  a.pbc = h->plan.pbc;
   for (int d = 0; d < 3; d++) a.ms[d] = (T)(h->L[d] / h->m[d]);
   for (int d = 0; d < 3; d++) a.L[d] = (T)h->L[d];
-  a.z_origin = h->b_slab ? h->b_zlo - 1 : 0;
+  a.z_origin = h->args.slab ? h->args.z_lo - 1 : 0;
   a.dbg = h->dbg_flags;
   a.dbg_buf = h->dbg_buf;
   a.gate = h->gate;
@@ -349,7 +367,7 @@ RowsArgs rows_args(nl_handle_t h) {
   a.sorted = static_cast<const Pos<float>*>(h->sorted);
   a.sorted_row = h->sorted_row, a.sorted_gid = h->sorted_gid;
   a.fine_start = h->cell_start;
-  a.mx = h->m[0], a.my = h->m[1], a.mzl = h->b_mzl, a.slab = h->b_slab;
+  a.mx = h->m[0], a.my = h->m[1], a.mzl = h->args.mzl, a.slab = h->args.slab;
   a.div_mx = fastdiv_make((uint32_t)h->m[0]), a.div_my = fastdiv_make((uint32_t)h->m[1]);
   a.rc2 = h->rc2_f;
   a.count = h->count;
@@ -361,114 +379,98 @@ RowsArgs rows_args(nl_handle_t h) {
   a.status = h->status;
   a.over_list = h->full27_list;
   a.over_count = reinterpret_cast<int32_t*>(h->status) + META_FULL27;
-  a.wide = h->b_wide ? 1 : 0;
+  a.wide = h->plan.wide ? 1 : 0;
   a.dbg_buf = h->dbg_buf;
   a.gate = h->gate;
   return a;
 }
 
 // The fine-row path (nl_rows.hpp).  V: RowsCfg of the build.
-template <int V, bool FULL> void launch_rows(nl_handle_t h, int mode, int32_t ncells_i, hipStream_t s) {
+template <int V, bool FULL, typename OFF> void launch_rows(nl_handle_t h, int mode, int32_t ncells, hipStream_t s) {
   const RowsArgs a = rows_args(h);
   const int32_t over_grid = 2 * h->num_cus;
   if (mode == MODE_COUNT) {
-    hipLaunchKernelGGL((k_sweep_rows_f32<V, FULL>), dim3(ncells_i), dim3(ROWS_WAVES * WAVE), 0, s, a);
+    hipLaunchKernelGGL((k_sweep_rows_f32<V, FULL>), dim3(ncells), dim3(ROWS_WAVES * WAVE), 0, s, a);
     hipLaunchKernelGGL((k_rows_overflow<MODE_COUNT, FULL, int32_t>), dim3(over_grid), dim3(ROWS_WAVES * WAVE), 0, s, a);
     return;
   }
-  if (h->b_wide) {
-    hipLaunchKernelGGL((k_fill_rows<V, FULL, int64_t>), dim3(ncells_i), dim3(ROWS_FW * WAVE), 0, s, a);
-    hipLaunchKernelGGL((k_rows_overflow<MODE_FILL, FULL, int64_t>), dim3(over_grid), dim3(ROWS_WAVES * WAVE), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((k_fill_rows<V, FULL, int32_t>), dim3(ncells_i), dim3(ROWS_FW * WAVE), 0, s, a);
-    hipLaunchKernelGGL((k_rows_overflow<MODE_FILL, FULL, int32_t>), dim3(over_grid), dim3(ROWS_WAVES * WAVE), 0, s, a);
-  }
+  hipLaunchKernelGGL((k_fill_rows<V, FULL, OFF>), dim3(ncells), dim3(ROWS_FW * WAVE), 0, s, a);
+  hipLaunchKernelGGL((k_rows_overflow<MODE_FILL, FULL, OFF>), dim3(over_grid), dim3(ROWS_WAVES * WAVE), 0, s, a);
 }
 
-// FULL = the list keeps both directions of every pair (the reference GPU class's contract).
-template <typename T, bool FULL, bool PBC, typename OFF> void launch_fill_masks(nl_handle_t h, const SweepArgs<T>& a, int32_t ncells_i, hipStream_t s) {
-  if (h->b_mask_nb > 1) {  // dense build: mask rows per (slot, LDS batch); list offsets gathered into cell order first
-    const int32_t nbp = (h->n + 255) / 256;
-    if (h->n > 0)
-      hipLaunchKernelGGL(k_row_base<OFF>, dim3(nbp), dim3(256), 0, s, static_cast<const OFF*>(search_kp(h)), h->sorted_row,
-                         h->n_rows, h->n, static_cast<OFF*>(h->base_sorted), h->gate);
-    hipLaunchKernelGGL((k_fill_dense<T, FULL, PBC, OFF>), dim3(ncells_i), dim3(FD_WAVES * WAVE), 0, s, a,
-                       static_cast<const OFF*>(h->base_sorted));
+// The search of the handle's build (h->plan) in mode MODE_COUNT, or the list expansion behind it in MODE_FILL (which
+// finish() launches again after growing the list).  FULL = the list keeps both directions of every pair (the reference
+// GPU class's contract); OFF = the type of key_pointer.
+template <typename T, bool FULL, bool PBC, typename OFF> void launch_search(nl_handle_t h, int mode, hipStream_t s) {
+  const BuildPlan& p = h->plan;
+  const int32_t ncells = h->m[0] * h->m[1] * (h->args.slab ? h->args.mzl - 2 : h->args.mzl);  // (the owned layers)
+  constexpr bool F32_OPEN = sizeof(T) == 4 && !PBC;
+  if (p.search == SEARCH_ROWS) {
+    if constexpr (F32_OPEN) {
+      if (p.rows_v == 0) launch_rows<0, FULL, OFF>(h, mode, ncells, s);
+      else if (p.rows_v == 1) launch_rows<1, FULL, OFF>(h, mode, ncells, s);
+      else launch_rows<2, FULL, OFF>(h, mode, ncells, s);
+    }
     return;
-  }
-  // rows a wave loads up front: 24, or 12 where cells hold ~20 particles or fewer (a wave then has ~10 rows)
-  const bool few_rows = (double)h->n <= 21.0 * (double)std::max<int64_t>(1, h->ncell_local);
-  if constexpr (sizeof(T) == 4 && !PBC) {
-    if (h->b_lean_small && h->fill_small_env) {  // sparse boxes: a wave per cell (its ~19 rows in one batch), ids of half a stream
-      hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 24, 1, SweepCfg<T>::CAP / 2>), dim3(ncells_i), dim3(WAVE), 0, s, a);
-      if (h->b_list) hipLaunchKernelGGL((k_fill_list<T, FULL, PBC>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
-      return;
-    }
-  }
-  if (few_rows)
-    hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 12>), dim3(ncells_i), dim3(EXPAND_WAVES * WAVE), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 24>), dim3(ncells_i), dim3(EXPAND_WAVES * WAVE), 0, s, a);
-  // cells without masks (a stream of several LDS batches among one-batch neighbours): a second distance search
-  if (h->b_list) hipLaunchKernelGGL((k_fill_list<T, FULL, PBC>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
-}
-
-template <typename T, bool FULL, bool PBC> void launch_sweep_kind(nl_handle_t h, int mode, hipStream_t s) {
-  const int32_t owned_layers = h->b_slab ? h->b_mzl - 2 : h->b_mzl;
-  const int32_t ncells_i = h->m[0] * h->m[1] * owned_layers;
-  if constexpr (sizeof(T) == 4 && !PBC) {
-    if (h->b_rows) {
-      if (h->b_rows_v == 0) launch_rows<0, FULL>(h, mode, ncells_i, s);
-      else if (h->b_rows_v == 1) launch_rows<1, FULL>(h, mode, ncells_i, s);
-      else launch_rows<2, FULL>(h, mode, ncells_i, s);
-      return;
-    }
   }
   const SweepArgs<T> a = sweep_args<T>(h);
-  if (h->b_use_masks) {
-    if (mode == MODE_COUNT) {
-      if constexpr (sizeof(T) == 4) {
-        if (!PBC && h->b_mask_nb == 1) {
+  const dim3 cells(ncells), wg(SWEEP_WAVES * WAVE), list_grid(2 * h->num_cus);
+  auto count_masks = [&] {  // the COUNT sweep keeping hit masks, for every LDS batch of a cell
+    if constexpr (sizeof(T) == 4) hipLaunchKernelGGL((k_sweep_count_masks_f32<FULL, PBC>), cells, wg, 0, s, a);
+    else hipLaunchKernelGGL((k_sweep<T, MODE_COUNT_MASKS, FULL, PBC>), cells, wg, 0, s, a);
+  };
+  switch (p.search) {
+    case SEARCH_MASKS:
+      if (mode == MODE_COUNT) {
+        if constexpr (F32_OPEN) {
           // a workgroup per cell, single-batch cells only; the others go on the hand-over list of the batched search
-          if (h->b_lean_small) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, 2, LEAN_SMALL_CAP>), dim3(ncells_i), dim3(2 * WAVE), 0, s, a);
-          else hipLaunchKernelGGL((k_sweep_lean_f32<FULL>), dim3(ncells_i), dim3(SWEEP_WAVES * WAVE), 0, s, a);
-          if (h->b_list) hipLaunchKernelGGL((k_sweep_list_f32<FULL>), dim3(2 * h->num_cus), dim3(SWEEP_WAVES * WAVE), 0, s, a);
+          if (p.small) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, 2, LEAN_SMALL_CAP>), cells, dim3(2 * WAVE), 0, s, a);
+          else hipLaunchKernelGGL((k_sweep_lean_f32<FULL>), cells, wg, 0, s, a);
+          if (p.list) hipLaunchKernelGGL((k_sweep_list_f32<FULL>), list_grid, wg, 0, s, a);
         } else {
-          hipLaunchKernelGGL((k_sweep_count_masks_f32<FULL, PBC>), dim3(ncells_i), dim3(SWEEP_WAVES * WAVE), h->dbg_lds_pad, s, a);
+          count_masks();
         }
-      } else
-        hipLaunchKernelGGL((k_sweep<T, MODE_COUNT_MASKS, FULL, PBC>), dim3(ncells_i), dim3(SWEEP_WAVES * WAVE), 0, s, a);
-    } else if (h->b_wide) {
-      launch_fill_masks<T, FULL, PBC, int64_t>(h, a, ncells_i, s);
-    } else {
-      launch_fill_masks<T, FULL, PBC, int32_t>(h, a, ncells_i, s);
-    }
-    return;
+        return;
+      }
+      if (p.small) {  // sparse boxes: a wave per cell (its ~19 rows in one batch), ids of half a stream
+        if constexpr (F32_OPEN)
+          hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 24, 1, SweepCfg<T>::CAP / 2>), cells, dim3(WAVE), 0, s, a);
+      } else if (p.rows12) {
+        hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 12>), cells, dim3(EXPAND_WAVES * WAVE), 0, s, a);
+      } else {
+        hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 24>), cells, dim3(EXPAND_WAVES * WAVE), 0, s, a);
+      }
+      // cells without masks (a stream of several LDS batches among one-batch neighbours): a second distance search
+      if (p.list) hipLaunchKernelGGL((k_fill_list<T, FULL, PBC>), list_grid, wg, 0, s, a);
+      return;
+    case SEARCH_DENSE:  // mask rows per (slot, LDS batch); list offsets gathered into cell order first
+      if (mode == MODE_COUNT) {
+        count_masks();
+        return;
+      }
+      if (h->n > 0)
+        hipLaunchKernelGGL(k_row_base<OFF>, dim3((h->n + 255) / 256), dim3(256), 0, s, static_cast<const OFF*>(search_kp(h)),
+                           h->sorted_row, h->n_rows, h->n, static_cast<OFF*>(h->base_sorted), h->gate);
+      hipLaunchKernelGGL((k_fill_dense<T, FULL, PBC, OFF>), cells, dim3(FD_WAVES * WAVE), 0, s, a, static_cast<const OFF*>(h->base_sorted));
+      return;
+    default:  // SEARCH_SWEEPS
+      if (mode == MODE_FILL) hipLaunchKernelGGL((k_sweep<T, MODE_FILL, FULL, PBC>), cells, wg, 0, s, a);
+      else if constexpr (sizeof(T) == 4) hipLaunchKernelGGL((k_sweep_count_f32<FULL, PBC>), cells, wg, 0, s, a);
+      else hipLaunchKernelGGL((k_sweep<T, MODE_COUNT, FULL, PBC>), cells, wg, 0, s, a);
   }
-  // two distance sweeps
-  SweepArgs<T> a2 = a;
-  a2.isplit = h->b_isplit;
-  const int32_t grid2 = ncells_i * h->b_isplit;
-  if (mode == MODE_COUNT) {
-    if constexpr (sizeof(T) == 4)
-      hipLaunchKernelGGL((k_sweep_count_f32<FULL, PBC>), dim3(grid2), dim3(SWEEP_WAVES * WAVE), 0, s, a2);
-    else
-      hipLaunchKernelGGL((k_sweep<T, MODE_COUNT, FULL, PBC>), dim3(grid2), dim3(SWEEP_WAVES * WAVE), 0, s, a2);
-  } else
-    hipLaunchKernelGGL((k_sweep<T, MODE_FILL, FULL, PBC>), dim3(grid2), dim3(SWEEP_WAVES * WAVE), 0, s, a2);
+}
+
+template <typename T, typename OFF> void launch_sweep_kind(nl_handle_t h, int mode, hipStream_t s) {
+  const bool pbc = h->plan.pbc != 0;
+  if (h->plan.full) pbc ? launch_search<T, true, true, OFF>(h, mode, s) : launch_search<T, true, false, OFF>(h, mode, s);
+  else pbc ? launch_search<T, false, true, OFF>(h, mode, s) : launch_search<T, false, false, OFF>(h, mode, s);
 }
 
 template <typename T> void launch_sweep(nl_handle_t h, int mode, hipStream_t s) {
-  if (h->b_full) {
-    if (h->pbc != 0) launch_sweep_kind<T, true, true>(h, mode, s);
-    else launch_sweep_kind<T, true, false>(h, mode, s);
-  } else {
-    if (h->pbc != 0) launch_sweep_kind<T, false, true>(h, mode, s);
-    else launch_sweep_kind<T, false, false>(h, mode, s);
-  }
+  if (h->plan.wide) launch_sweep_kind<T, int64_t>(h, mode, s);
+  else launch_sweep_kind<T, int32_t>(h, mode, s);
 }
 
-// Enqueues one whole build. ev != nullptr: records an event before every stage and one after the last.
 // part: PART_ALL = the whole build; PART_BEGIN = everything that needs the OWNED particles only (slab builds: memset +
 // the binning pass over [0, n_rows)); PART_FINISH = the rest (the binning pass over the ghosts, search, scan,
 // expansion).  BEGIN + FINISH = ALL for the caller; between the two the halo exchange may still be writing the ghosts.
@@ -489,6 +491,12 @@ bool mask_rows_ready(nl_handle_t h, int64_t nb, size_t row_bytes = MASK_ROW_BYTE
   return true;
 }
 
+// The two-level binning (k_bin_*): meshes of up to BIN_MAX_ROWS rows of x-cells and BIN_MAX_MX cells a row, unless
+// NL_BINNING=1 selects the atomic-rank path (k_hash / k_reorder).
+bool two_level_ok(nl_handle_t h, int32_t mzl) {
+  return h->bin_two_level && (int64_t)h->m[1] * mzl <= BIN_MAX_ROWS && h->m[0] <= BIN_MAX_MX;
+}
+
 // The fine-row layout needs the two-level binning (k_bin_cells<FINE>) and a fine table that an int32 can index.
 bool rows_layout_ok(nl_handle_t h, int32_t mzl) {
   const int64_t nrows = (int64_t)h->m[1] * mzl;
@@ -506,8 +514,8 @@ bool rows_margin_ok(nl_handle_t h) {
 // the two-pass binning.  The mean row plus a Poisson-safe margin (BASELINE config 2: 1165 particles a row, sigma 34:
 // 1712 slots), times bucket_scale; the buckets (re)allocated on first need, at most 4 n_max + 512 slots a row.
 template <typename T> int32_t bucket_cap(nl_handle_t h, int32_t n, int32_t mzl) {
+  if (!h->bucket_env || h->bucket_off || !two_level_ok(h, mzl)) return 0;
   const int64_t nrows = (int64_t)h->m[1] * mzl;
-  if (!h->bucket_env || h->bucket_off || !h->bin_two_level || nrows > BIN_MAX_ROWS || h->m[0] > BIN_MAX_MX) return 0;
   const int64_t cap = (int64_t)h->bucket_scale * ((int64_t)(1.25 * (double)n / (double)nrows) + 256);
   const size_t slots = (size_t)(nrows * cap) + 16;
   if (slots > 4 * ((size_t)h->n_max + 16) + 512 * (size_t)nrows) {
@@ -529,34 +537,33 @@ template <typename T> int32_t bucket_cap(nl_handle_t h, int32_t n, int32_t mzl) 
   return (int32_t)cap;
 }
 
-// What the handle remembers about the build being enqueued (also set when a captured graph of it is replayed): how the
-// later stages, the getters and a refill after growth have to read the buffers.  whole: a build that finish() can run
-// again (not the two passes of a split slab build, not a distributed one).
-template <typename T>
-void set_build_state(nl_handle_t h, const void* q_dev, int32_t stride, const int32_t* gid, int32_t n, int32_t z_lo,
-                     int32_t mzl, int32_t slab, bool whole = true) {
-  const int64_t ncl = (int64_t)h->m[0] * h->m[1] * mzl;
-  h->ncell_local = ncl;
-  h->b_mzl = mzl, h->b_slab = slab, h->b_zlo = z_lo, h->b_stride = stride, h->b_q = q_dev, h->b_gid = gid;
-  h->b_full = h->list_kind == NL_LIST_FULL;
-  h->b_pbc = h->pbc;
-  h->b_variant = h->sweep_variant;
-  h->b_excl = h->ex_ids != nullptr;
-  h->ex_relabel = true;  // (the cell order nl_resort applies is this build's)
+// Every choice of a build (BuildPlan) from its arguments and the handle's settings, with the allocations they need (mask
+// rows, row buckets; a failed allocation leaves that path out).  part: a slab build in two parts bins its owned rows and
+// its ghosts in separate passes.  rerun: a build that runs one again (finish(), an update's build) takes the two-pass
+// binning and every launch of its path.
+template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, int part, bool rerun) {
+  BuildPlan p;
+  p.full = h->list_kind == NL_LIST_FULL;
+  p.pbc = h->pbc;
+  p.excl = h->ex_ids != nullptr;
+  // 64-bit list offsets as soon as the list this handle can hold exceeds what an int32 key_pointer can address
+  // (the reference's own limit, neighlist_cpu.hpp:15,29); nl_set_offset_width overrides.
+  p.wide = h->offset_width == 64 || (h->offset_width == 0 && h->capacity > 2147483647LL);
+
+  // the search, by density: a distributed build's n is an upper bound, n_est what it expects
+  const int32_t n = a.dyn ? a.n_est : a.n;
+  const int64_t ncl = (int64_t)h->m[0] * h->m[1] * a.mzl;
+  const bool variant3 = h->sweep_variant >= 3;
   // Hit masks pay off while a cell's stencil fits one LDS batch; where the mean stencil (27 cells) is close to or
   // beyond the batch size most cells would fall back to a re-search in small batches, so use two full sweeps there.
   const double mean_stream = ncl > 0 ? 27.0 * n / (double)ncl : 0.0;
   const bool sparse_enough = mean_stream <= 0.85 * SweepCfg<T>::CAP;  // mean stencil <= 1088: <= 40.3 per cell
-  h->b_use_masks = h->b_variant >= 3 && sparse_enough && mask_rows_ready(h, 1);
-  h->b_mask_nb = 1;
-  // sparse boxes (mean stream + 5 sigma within half the LDS buffer: up to 19.6 particles per cell): the 2-wave instance
-  // of the lean COUNT sweep; a cell beyond it goes to the batched search like any other that does not fit
-  h->b_lean_small = h->lean_small_env != 0 && mean_stream + 5.0 * std::sqrt(mean_stream) <= (double)LEAN_SMALL_CAP;
+  bool masks = variant3 && sparse_enough && mask_rows_ready(h, 1);
   // The fine-row search (nl_rows.hpp): fp32, open box, the two-level binning, and a cell edge that exceeds the cut-off
   // along z by more than the rounding of the cell hash can hide (rows_margin_ok).  RowsCfg by the mean stencil
   // stream m = 27 <N/cell>: m + 5 sigma within the LDS buffer, the piece a wave walks + 6 sigma within its hit word.
-  h->b_rows = false;
-  if (sizeof(T) == 4 && h->b_variant >= 3 && h->pbc == 0 && h->rows_env != 0 && rows_layout_ok(h, mzl) && rows_margin_ok(h)) {
+  bool rows = false;
+  if (sizeof(T) == 4 && variant3 && p.pbc == 0 && h->rows_env != 0 && rows_layout_ok(h, a.mzl) && rows_margin_ok(h)) {
     int v = -1;
     if (h->rows_env > 0 && h->rows_env <= 3) {
       v = h->rows_env - 1;
@@ -570,175 +577,188 @@ void set_build_state(nl_handle_t h, const void* q_dev, int32_t stride, const int
       for (int k = 0; k < 3 && v < 0; k++)
         if (mean_stream + 5.0 * std::sqrt(mean_stream) <= cap[k] && span + 6.0 * std::sqrt(span) <= 64.0 * bits[k]) v = k;
     }
-    if (v >= 0 && mask_rows_ready(h, 1, v == 0 ? 128 : 256)) h->b_rows = true, h->b_rows_v = v, h->b_use_masks = true;
+    if (v >= 0 && mask_rows_ready(h, 1, v == 0 ? 128 : 256)) rows = true, p.rows_v = v, masks = true;
   }
-  if (h->b_variant >= 3 && !sparse_enough && !h->dense_masks_off) {
+  if (variant3 && !sparse_enough) {
     // Dense cells: hit masks for up to FD_NB LDS batches per slot instead of a second distance sweep, when the streams
-    // (mean + 5 sigma of a Poisson count) fit that many batches and the mask rows fit the memory set aside for them
+    // (mean + 5 sigma of a Poisson count) fit that many batches and the mask rows fit the memory set aside for them.
+    // (Also where the fine rows take the build: mask_nb is what nl_get_build_info reports.)
     const int64_t nb = (int64_t)((mean_stream + 5.0 * std::sqrt(mean_stream) + 64.0) / SweepCfg<T>::CAP) + 1;
-    if (nb <= FD_NB && mask_rows_ready(h, nb)) h->b_use_masks = true, h->b_mask_nb = (int32_t)nb;  // (allocates once)
+    if (nb <= FD_NB && mask_rows_ready(h, nb)) masks = true, p.mask_nb = (int32_t)nb;  // (allocates once)
   }
-  // 64-bit list offsets as soon as the list this handle can hold exceeds what an int32 key_pointer can address
-  // (the reference's own limit, neighlist_cpu.hpp:15,29); nl_set_offset_width overrides.
-  {  // NL_ISPLIT (diagnostics): workgroups per cell in the two-sweep path; default 1 (see sweep_cell)
-    int32_t sp = std::max(1, std::min(h->isplit_env, 32));
-    if ((int64_t)sp * ncl > 2000000000LL) sp = 1;
-    h->b_isplit = h->b_use_masks ? 1 : sp;
-  }
-  h->b_wide = h->offset_width == 64 || (h->offset_width == 0 && h->capacity > 2147483647LL);
-  h->kp_alt_valid = false;
-  // A build that can be run again bins in one pass into row buckets, and leaves out the launches for cells whose stencil
-  // exceeds the LDS buffer once LIST_QUIET_BUILDS builds in a row have been enqueued without such cells being seen;
-  // finish() runs it again without either when a row overflowed its bucket or such a cell was there after all.
-  const bool again_ok = whole && !h->b_dyn && !h->rerun;
-  h->b_list = !again_ok || h->list_quiet < LIST_QUIET_BUILDS;
-  h->b_cap_row = again_ok ? bucket_cap<T>(h, n, mzl) : 0;
+  p.search = rows ? SEARCH_ROWS : !masks ? SEARCH_SWEEPS : p.mask_nb > 1 ? SEARCH_DENSE : SEARCH_MASKS;
+  // sparse boxes (mean stream + 5 sigma within half the LDS buffer: up to 19.6 particles per cell): the 2-wave instance
+  // of the lean COUNT sweep, a wave per cell in the expansion; a cell beyond it goes to the batched search like any other
+  // that does not fit
+  p.small = sizeof(T) == 4 && p.search == SEARCH_MASKS && p.pbc == 0 &&
+            mean_stream + 5.0 * std::sqrt(mean_stream) <= (double)LEAN_SMALL_CAP;
+  // rows a wave of the expansion loads up front: 24, or 12 where cells hold ~20 particles or fewer (a wave then has ~10
+  // rows); from the build's n, which a refill after growth expands again
+  p.rows12 = (double)a.n <= 21.0 * (double)std::max<int64_t>(1, ncl);
+
+  // the binning.  A build that can be run again bins in one pass into row buckets, and leaves out the launches for
+  // cells whose stencil exceeds the LDS buffer once LIST_QUIET_BUILDS builds in a row have been enqueued without such
+  // cells being seen; finish() runs it again without either when a row overflowed its bucket or such a cell was there
+  // after all.
+  const bool two_level = two_level_ok(h, a.mzl);
+  p.split = part != PART_ALL && two_level && a.slab;
+  const bool again_ok = !p.split && !a.dyn && !rerun;
+  p.list = !again_ok || h->list_quiet < LIST_QUIET_BUILDS;
+  p.cap_row = again_ok ? bucket_cap<T>(h, n, a.mzl) : 0;
+  p.binning = !two_level ? BINNING_ATOMIC : p.cap_row > 0 ? BINNING_BUCKET : BINNING_TWO_PASS;
+  return p;
 }
 
-template <typename T>
-int enqueue_build(nl_handle_t h, const void* q_dev, int32_t stride, const int32_t* gid, int32_t n_rows, int32_t n,
-                  int32_t z_lo, int32_t mzl, int32_t slab, hipStream_t s, hipEvent_t* ev, int part = PART_ALL,
-                  int32_t n_ghost_lo = 0) {
-  const Grid<T> g = make_grid<T>(h, n_rows, z_lo, mzl, slab);
-  const int64_t ncl = (int64_t)h->m[0] * h->m[1] * mzl;
-  const int32_t nbp = (n + 255) / 256;
-  const T* q = static_cast<const T*>(q_dev);
+BuildPlan plan_for(nl_handle_t h, const BuildArgs& a, int part, bool rerun) {
+  return h->dtype == NL_F32 ? plan_build<float>(h, a, part, rerun) : plan_build<double>(h, a, part, rerun);
+}
 
-  const int32_t nrows = h->m[1] * mzl;
-  const bool two_level = h->bin_two_level && nrows <= BIN_MAX_ROWS && h->m[0] <= BIN_MAX_MX;
-  // One allocation = [cell histogram | status, tickets, total (32 words) | row totals]: one memset node clears
-  // what this build's path needs (histogram + meta, or meta + row totals); the one-pass binning needs none.
-  // two binning passes: owned, then ghosts (the persistent sweep, variant 2, has its own cell walk without the guard
-  // against an inconsistent cell table: no split there)
-  const bool split = part != PART_ALL && two_level && slab;
-  set_build_state<T>(h, q_dev, stride, gid, h->b_dyn ? h->b_n_est : n, z_lo, mzl, slab, !split);
-  if (h->b_excl && (n != h->ex_n || slab || gid || h->b_dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
-  if (h->b_excl && !excl_ready(h)) return fail(h, NL_ERR_NOMEM);  // (the search would write through a missing buffer)
-  if (part != PART_ALL && !split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
+// The build being enqueued, or replayed from a graph, becomes the handle's: finish(), a refill after growth and the
+// getters read its buffers by its arguments and plan.
+void adopt_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p) {
+  h->args = a;
+  h->plan = p;
+  h->ex_relabel = true;  // (the cell order nl_resort applies is this build's)
+  h->kp_alt_valid = false;
+}
+
+// k_bin_bucket / k_bin_scatter keep 8 particles a thread in flight where a chunk is 8 per thread, else 4.  (k_bin_bucket
+// in fp32 only: 127 VGPRs; fp64 would spill, and reads its chunk twice instead.)
+template <typename T, bool BUCKET, typename L> void launch_unrolled(nl_handle_t h, L&& launch) {
+  if constexpr (sizeof(T) == 4 || !BUCKET) {
+    if (h->bin_chunk >= 8 * BIN_THREADS) return launch(std::integral_constant<int, 8>());
+  }
+  launch(std::integral_constant<int, 4>());
+}
+
+// k_bin_cells: the particles of the rows into cell order, with the fine-row table (FINE) for the fine-row search
+template <typename T>
+void launch_bin_cells(nl_handle_t h, const Grid<T>& g, int32_t grid, int32_t nrows, const int32_t* row_start, const BinPhase& ph,
+                      int32_t cap_row, hipStream_t s) {
+  auto launch = [&](auto fine) {
+    hipLaunchKernelGGL((k_bin_cells<T, decltype(fine)::value>), dim3(grid), dim3(256), 0, s, g, nrows, row_start,
+                       static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
+                       h->sorted_row, h->sorted_gid, ph, cap_row);
+  };
+  if constexpr (sizeof(T) == 4) {
+    if (h->plan.search == SEARCH_ROWS) return launch(std::true_type());
+  }
+  launch(std::false_type());
+}
+
+// Enqueues build a along plan p (made by plan_build for these arguments), which becomes the handle's build.
+// ev != nullptr: records an event before every stage and one after the last.
+template <typename T>
+int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStream_t s, hipEvent_t* ev, int part = PART_ALL) {
+  adopt_build(h, a, p);
+  if (p.excl && (a.n != h->ex_n || a.slab || a.gid || a.dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
+  if (p.excl && !excl_ready(h)) return fail(h, NL_ERR_NOMEM);  // (the search would write through a missing buffer)
+  if (part != PART_ALL && !p.split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
     if (part == PART_BEGIN) return NL_OK;
     part = PART_ALL;
   }
-  if (two_level) {
-    const int32_t my = h->m[1];
-    // the three launches of one pass; rc_arr / rs_arr: the pass's own row totals and row starts
-    auto run_pass = [&](const BinPhase& ph, int32_t* rc_arr, int32_t* rs_arr, int32_t cells_grid, bool events) {
-      const int32_t np = ph.i_end - ph.i_beg;
-      const int32_t blocks = std::max(1, (np + h->bin_chunk - 1) / h->bin_chunk);  // (an empty pass still publishes its row starts)
-      hipLaunchKernelGGL((k_bin_rows<T>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, stride, n, h->bin_chunk, g, nrows, rc_arr,
-                         h->blk_base, h->status, ph);
-      if (events) (void)hipEventRecord(ev[NL_STAGE_CELL_SCAN], s);
-      // (no scan launch: every block of k_bin_scatter scans the row totals itself and block 0 publishes the row starts)
-      if (events) (void)hipEventRecord(ev[NL_STAGE_REORDER], s);
-      if (h->bin_chunk >= 8 * BIN_THREADS)
-        hipLaunchKernelGGL((k_bin_scatter<T, 8>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, stride, gid, n, h->bin_chunk, g, nrows,
-                           rc_arr, rs_arr, h->blk_base, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row, h->status, ph);
-      else
-        hipLaunchKernelGGL((k_bin_scatter<T, 4>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, stride, gid, n, h->bin_chunk, g, nrows,
-                           rc_arr, rs_arr, h->blk_base, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row, h->status, ph);
-      if constexpr (sizeof(T) == 4) {
-        if (h->b_rows) {
-          hipLaunchKernelGGL((k_bin_cells<T, true>), dim3(cells_grid), dim3(256), 0, s, g, nrows, rs_arr,
-                             static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
-                             h->sorted_row, h->sorted_gid, ph);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((k_bin_cells<T, false>), dim3(cells_grid), dim3(256), 0, s, g, nrows, rs_arr,
-                         static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
-                         h->sorted_row, h->sorted_gid, ph);
-    };
-    if (!split && h->b_cap_row > 0) {
+  const Grid<T> g = make_grid<T>(h, a, p.pbc);
+  const int32_t n = a.n, nrows = h->m[1] * a.mzl, my = h->m[1];
+  const T* q = static_cast<const T*>(a.q);
+  // the three launches of one pass of the two-pass binning; rc_arr / rs_arr: the pass's own row totals and row starts
+  auto run_pass = [&](const BinPhase& ph, int32_t* rc_arr, int32_t* rs_arr, int32_t cells_grid, bool events) {
+    const int32_t np = ph.i_end - ph.i_beg;
+    const int32_t blocks = std::max(1, (np + h->bin_chunk - 1) / h->bin_chunk);  // (an empty pass still publishes its row starts)
+    hipLaunchKernelGGL((k_bin_rows<T>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, a.stride, n, h->bin_chunk, g, nrows, rc_arr,
+                       h->blk_base, h->status, ph);
+    if (events) (void)hipEventRecord(ev[NL_STAGE_CELL_SCAN], s);
+    // (no scan launch: every block of k_bin_scatter scans the row totals itself and block 0 publishes the row starts)
+    if (events) (void)hipEventRecord(ev[NL_STAGE_REORDER], s);
+    launch_unrolled<T, false>(h, [&](auto u) {
+      hipLaunchKernelGGL((k_bin_scatter<T, decltype(u)::value>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, a.stride, a.gid, n,
+                         h->bin_chunk, g, nrows, rc_arr, rs_arr, h->blk_base, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row,
+                         h->status, ph);
+    });
+    launch_bin_cells<T>(h, g, cells_grid, nrows, rs_arr, ph, 0, s);
+  };
+  // One allocation = [cell histogram | status, tickets, total (32 words) | row totals]: one memset node clears
+  // what this build's path needs (histogram + meta, or meta + row totals); the one-pass binning needs none.
+  switch (p.binning) {
+    case BINNING_BUCKET: {
       // one pass into the row buckets; k_bin_bucket also starts the meta words and leaves its cursors at zero
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
       const int32_t blocks = std::max(1, (n + h->bin_chunk - 1) / h->bin_chunk);
-      // (8 particles a thread in registers: 127 VGPRs in fp32; fp64 would spill, and reads its chunk twice instead)
-      bool wide = false;
-      if constexpr (sizeof(T) == 4) {
-        if ((wide = h->bin_chunk >= 8 * BIN_THREADS))
-          hipLaunchKernelGGL((k_bin_bucket<T, 8>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, stride, gid, n, h->bin_chunk, g, nrows,
-                             h->b_cap_row, h->row_cursor, h->row_start, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row, h->status);
-      }
-      if (!wide)
-        hipLaunchKernelGGL((k_bin_bucket<T, 4>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, stride, gid, n, h->bin_chunk, g, nrows,
-                           h->b_cap_row, h->row_cursor, h->row_start, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row, h->status);
+      launch_unrolled<T, true>(h, [&](auto u) {
+        hipLaunchKernelGGL((k_bin_bucket<T, decltype(u)::value>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, a.stride, a.gid, n,
+                           h->bin_chunk, g, nrows, p.cap_row, h->row_cursor, h->row_start, static_cast<Pos<T>*>(h->tmp_pos),
+                           h->tmp_row, h->status);
+      });
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_CELL_SCAN], s));
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_REORDER], s));
       const BinPhase all = {0, n, nrows, 0, 0, 0, nrows, nrows, -1, nullptr};
-      bool fine = false;
-      if constexpr (sizeof(T) == 4) {
-        if ((fine = h->b_rows))
-          hipLaunchKernelGGL((k_bin_cells<T, true>), dim3(nrows), dim3(256), 0, s, g, nrows, h->row_start,
-                             static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
-                             h->sorted_row, h->sorted_gid, all, h->b_cap_row);
+      launch_bin_cells<T>(h, g, nrows, nrows, h->row_start, all, p.cap_row, s);
+      break;
+    }
+    case BINNING_TWO_PASS:
+      if (part == PART_ALL) {
+        // (an update's build: k_skin_check has cleared these words where it decided on a build)
+        if (!h->gate) HIPCHK(h, hipMemsetAsync(h->cell_count + h->ncell, 0, sizeof(int32_t) * (size_t)(32 + nrows), s));
+        if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
+        const BinPhase all = {0, n, nrows, 0, 0, 0, nrows, nrows, -1, a.dyn};
+        run_pass(all, h->row_count, h->row_start, nrows, ev != nullptr);
+      } else if (part == PART_BEGIN) {
+        // owned particles: rows of the layers 1 .. mzl-2, placed behind the n_ghost_lo particles of ghost layer 0
+        HIPCHK(h, hipMemsetAsync(h->cell_count + h->ncell, 0, sizeof(int32_t) * (size_t)(32 + 2 * (size_t)nrows), s));
+        const BinPhase owned = {0, a.n_rows, nrows, a.n_ghost_lo, a.n_ghost_lo, my, nrows - 2 * my, nrows, -1};
+        run_pass(owned, h->row_count, h->row_start, nrows - 2 * my, false);
+        HIPCHK(h, hipGetLastError());
+        return NL_OK;
+      } else {
+        // ghosts: layer 0 at the front of the sorted array, layer mzl-1 behind the owned particles
+        const BinPhase ghosts = {a.n_rows, n, nrows - my, 0, a.n_rows, 0, my, nrows - my, a.n_ghost_lo};
+        run_pass(ghosts, h->row_count + nrows, h->row_start + nrows + 16, 2 * my, false);
       }
-      if (!fine)
-        hipLaunchKernelGGL((k_bin_cells<T, false>), dim3(nrows), dim3(256), 0, s, g, nrows, h->row_start,
-                           static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
-                           h->sorted_row, h->sorted_gid, all, h->b_cap_row);
-    } else if (!split) {
-      // (an update's build: k_skin_check has cleared these words where it decided on a build)
-      if (!h->gate) HIPCHK(h, hipMemsetAsync(h->cell_count + h->ncell, 0, sizeof(int32_t) * (size_t)(32 + nrows), s));
+      break;
+    default: {  // BINNING_ATOMIC
+      const int32_t nbp = (n + 255) / 256;
+      if (h->gate) {  // an update's build: no memset node, a launch that waits on the decision like the others
+        const int64_t words = h->ncell + 32;
+        hipLaunchKernelGGL(k_zero_words, dim3((uint32_t)std::min<int64_t>((words + 1023) / 1024, 2048)), dim3(256), 0, s, h->cell_count, words, h->gate);
+      } else {
+        HIPCHK(h, hipMemsetAsync(h->cell_count, 0, sizeof(int32_t) * (size_t)(h->ncell + 32), s));
+      }
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
-      const BinPhase all = {0, n, nrows, 0, 0, 0, nrows, nrows, -1, h->b_dyn};
-      run_pass(all, h->row_count, h->row_start, nrows, ev != nullptr);
-    } else if (part == PART_BEGIN) {
-      // owned particles: rows of the layers 1 .. mzl-2, placed behind the n_ghost_lo particles of ghost layer 0
-      HIPCHK(h, hipMemsetAsync(h->cell_count + h->ncell, 0, sizeof(int32_t) * (size_t)(32 + 2 * (size_t)nrows), s));
-      const BinPhase owned = {0, n_rows, nrows, n_ghost_lo, n_ghost_lo, my, nrows - 2 * my, nrows, -1};
-      run_pass(owned, h->row_count, h->row_start, nrows - 2 * my, false);
-      HIPCHK(h, hipGetLastError());
-      return NL_OK;
-    } else {
-      // ghosts: layer 0 at the front of the sorted array, layer mzl-1 behind the owned particles
-      const BinPhase ghosts = {n_rows, n, nrows - my, 0, n_rows, 0, my, nrows - my, n_ghost_lo};
-      run_pass(ghosts, h->row_count + nrows, h->row_start + nrows + 16, 2 * my, false);
+      if (n > 0) hipLaunchKernelGGL((k_hash<T>), dim3(nbp), dim3(256), 0, s, q, a.stride, n, g, h->cell_count, h->rank, h->status);
+      if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_CELL_SCAN], s));
+      if (int rc = launch_scan(h, h->cell_count, (int64_t)h->m[0] * h->m[1] * a.mzl, h->cell_start, h->totals, s)) return rc;
+      if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_REORDER], s));
+      if (n > 0)
+        hipLaunchKernelGGL((k_reorder<T>), dim3(nbp), dim3(256), 0, s, q, a.stride, a.gid, n, g, h->cell_start, h->rank,
+                           static_cast<Pos<T>*>(h->sorted), h->sorted_row, h->sorted_gid);
     }
-  } else {
-    if (h->gate) {  // an update's build: no memset node, a launch that waits on the decision like the others
-      const int64_t words = h->ncell + 32;
-      hipLaunchKernelGGL(k_zero_words, dim3((uint32_t)std::min<int64_t>((words + 1023) / 1024, 2048)), dim3(256), 0, s, h->cell_count, words, h->gate);
-    } else {
-      HIPCHK(h, hipMemsetAsync(h->cell_count, 0, sizeof(int32_t) * (size_t)(h->ncell + 32), s));
-    }
-    if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
-    if (n > 0) hipLaunchKernelGGL((k_hash<T>), dim3(nbp), dim3(256), 0, s, q, stride, n, g, h->cell_count, h->rank, h->status);
-    if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_CELL_SCAN], s));
-    if (int rc = launch_scan(h, h->cell_count, ncl, h->cell_start, h->totals, s)) return rc;
-    if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_REORDER], s));
-    if (n > 0)
-      hipLaunchKernelGGL((k_reorder<T>), dim3(nbp), dim3(256), 0, s, q, stride, gid, n, g, h->cell_start, h->rank,
-                         static_cast<Pos<T>*>(h->sorted), h->sorted_row, h->sorted_gid);
   }
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_COUNT], s));
   // (rows of particles rejected by the hash keep a stale count: such a build fails with its status anyway)
   launch_sweep<T>(h, MODE_COUNT, s);
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_ROW_SCAN], s));
-  if (h->b_wide) {
-    if (int rc = launch_scan(h, h->count, n_rows, static_cast<int64_t*>(search_kp(h)), h->totals + 1, s, h->status + META_TOTAL)) return rc;
+  if (p.wide) {
+    if (int rc = launch_scan(h, h->count, a.n_rows, static_cast<int64_t*>(search_kp(h)), h->totals + 1, s, h->status + META_TOTAL)) return rc;
   } else {
-    if (int rc = launch_scan(h, h->count, n_rows, static_cast<int32_t*>(search_kp(h)), h->totals + 1, s, h->status + META_TOTAL)) return rc;
+    if (int rc = launch_scan(h, h->count, a.n_rows, static_cast<int32_t*>(search_kp(h)), h->totals + 1, s, h->status + META_TOTAL)) return rc;
   }
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_FILL], s));
   launch_sweep<T>(h, MODE_FILL, s);
   // the exclusion table: the unfiltered list compacted into the getters' buffers (counted in the FILL stage)
-  if (h->b_excl)
-    if (int rc = launch_exclude(h, n_rows, s)) return rc;
+  if (p.excl)
+    if (int rc = launch_exclude(h, a.n_rows, s)) return rc;
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_TOTAL], s));
   HIPCHK(h, hipGetLastError());
   return NL_OK;
 }
 
 int enqueue_result_copy(nl_handle_t h, hipStream_t s) {
-  const int words = h->b_excl ? META_WORDS_EXCL : META_WORDS;
+  const int words = h->plan.excl ? META_WORDS_EXCL : META_WORDS;
   HIPCHK(h, hipMemcpyAsync(h->host, h->status, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s));
   return NL_OK;
 }
 
-int dispatch_build(nl_handle_t h, const void* q, int32_t stride, const int32_t* gid, int32_t n_rows, int32_t n,
-                   int32_t z_lo, int32_t mzl, int32_t slab, hipStream_t s, hipEvent_t* ev, int part = PART_ALL,
-                   int32_t n_ghost_lo = 0) {
-  return h->dtype == NL_F32 ? enqueue_build<float>(h, q, stride, gid, n_rows, n, z_lo, mzl, slab, s, ev, part, n_ghost_lo)
-                            : enqueue_build<double>(h, q, stride, gid, n_rows, n, z_lo, mzl, slab, s, ev, part, n_ghost_lo);
+int dispatch_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStream_t s, hipEvent_t* ev, int part = PART_ALL) {
+  return h->dtype == NL_F32 ? enqueue_build<float>(h, a, p, s, ev, part) : enqueue_build<double>(h, a, p, s, ev, part);
 }
 
 // Default list capacity (unless the caller fixed it): ideal-gas estimate of the half-pair count
@@ -771,9 +791,8 @@ int grow_list(nl_handle_t h, int64_t need) {
 
 // The last build once more, from its own arguments, with the two-pass binning and every launch of its path; waits for it.
 int run_again(nl_handle_t h) {
-  h->rerun = true;
-  int rc = dispatch_build(h, h->b_q, h->b_stride, h->b_gid, h->n_rows, h->n, h->b_zlo, h->b_mzl, h->b_slab, h->last_stream, nullptr);
-  h->rerun = false;
+  const BuildArgs a = h->args;
+  int rc = dispatch_build(h, a, plan_for(h, a, PART_ALL, true), h->last_stream, nullptr);
   if (!rc) rc = enqueue_result_copy(h, h->last_stream);
   if (rc) return rc;
   HIPCHK(h, hipStreamSynchronize(h->last_stream));
@@ -790,18 +809,18 @@ int finish(nl_handle_t h, bool may_grow) {
     // A row past its bucket, or cells handed to k_sweep_list_f32 / k_fill_list by a build that did not launch them: the
     // build is incomplete (whatever else its status says) and runs again without either shortcut.  An overflowed row
     // doubles the buckets of later builds, once; a second overflow ends the one-pass binning for this handle.
-    const bool lean = h->b_use_masks && !h->b_rows && h->b_mask_nb == 1;  // (the paths with those two kernels)
-    const bool listed = lean && (h->host->tickets[META_FULL27 - 1] | h->host->tickets[META_FILL_LIST - 1]) != 0;
-    const bool overflow = h->b_cap_row > 0 && (st & ST_ROW_OVERFLOW);
+    const bool listed = h->plan.search == SEARCH_MASKS &&  // (the path with those two kernels)
+                        (h->host->tickets[META_FULL27 - 1] | h->host->tickets[META_FILL_LIST - 1]) != 0;
+    const bool overflow = h->plan.cap_row > 0 && (st & ST_ROW_OVERFLOW);
     if (listed) h->list_quiet = 0;
-    if (overflow || (listed && !h->b_list)) {
+    if (overflow || (listed && !h->plan.list)) {
       if (overflow) h->reruns[0]++, h->bucket_scale *= 2;
       else h->reruns[1]++;
       if (int rc = run_again(h)) return rc;
       st = h->host->status;
     }
   }
-  if ((st & ST_INDEX_OVERFLOW) && !(st & ~(ST_CAPACITY | ST_INDEX_OVERFLOW)) && may_grow && !h->b_wide && h->offset_width == 0) {
+  if ((st & ST_INDEX_OVERFLOW) && !(st & ~(ST_CAPACITY | ST_INDEX_OVERFLOW)) && may_grow && !h->plan.wide && h->offset_width == 0) {
     // more than INT32_MAX entries in a build with 32-bit offsets: the list grows past that size, which makes builds of
     // this handle wide (64-bit key_pointer), and the whole build runs again
     int rc = grow_list(h, h->host->total());
@@ -811,24 +830,49 @@ int finish(nl_handle_t h, bool may_grow) {
   } else if ((st & ST_CAPACITY) && !(st & ~ST_CAPACITY) && may_grow) {
     int rc = grow_list(h, h->host->total());
     if (rc) return rc;
+    // the FILL stage of the build's plan once more (ungated: an update's build is complete by now)
     HIPCHK(h, hipMemsetAsync(h->status, 0, sizeof(uint32_t), h->last_stream));
     if (h->dtype == NL_F32)
       launch_sweep<float>(h, MODE_FILL, h->last_stream);
     else
       launch_sweep<double>(h, MODE_FILL, h->last_stream);
-    if (h->b_excl) rc = launch_exclude(h, h->n_rows, h->last_stream);  // (the refilled list is the unfiltered one)
+    if (h->plan.excl) rc = launch_exclude(h, h->n_rows, h->last_stream);  // (the refilled list is the unfiltered one)
     if (!rc) rc = enqueue_result_copy(h, h->last_stream);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
     st = h->host->status;
   }
   int err = status_to_error(st);
-  if (h->b_dyn && h->dyn_host) {  // a decomposed build: its ghost counts, and whether the exchange held what was sent
-    h->n = h->n_rows + h->dyn_host[2] + h->dyn_host[3];
-    if (!err && h->dyn_host[4]) err = NL_ERR_CAPACITY;
+  if (h->args.dyn && h->args.dyn_host) {  // a decomposed build: its ghost counts, and whether the exchange held what was sent
+    const int32_t* dh = h->args.dyn_host;
+    h->n = h->n_rows + dh[2] + dh[3];
+    if (!err && dh[4]) err = NL_ERR_CAPACITY;
   }
   h->built = err == NL_OK;
   if (err) return fail(h, err);
+  return NL_OK;
+}
+
+// The graph of the handle on stream s, captured first (on the private stream: the null stream cannot be captured) from
+// what enqueue(stream) enqueues wherever key differs from the key of the graph it holds.
+template <typename F> int graph_launch(nl_handle_t h, const GraphKey& key, hipStream_t s, F&& enqueue) {
+  if (!h->graph_exec || !(key == h->graph_key)) {
+    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec), h->graph_exec = nullptr;
+    if (h->graph) (void)hipGraphDestroy(h->graph), h->graph = nullptr;
+    HIPCHK(h, hipStreamBeginCapture(h->own_stream, hipStreamCaptureModeRelaxed));
+    const int rc = enqueue(h->own_stream);
+    hipGraph_t g = nullptr;
+    const hipError_t e = hipStreamEndCapture(h->own_stream, &g);
+    if (rc) {
+      if (g) (void)hipGraphDestroy(g);
+      return rc;
+    }
+    HIPCHK(h, e);
+    h->graph = g;
+    HIPCHK(h, hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
+    h->graph_key = key;
+  }
+  HIPCHK(h, hipGraphLaunch(h->graph_exec, s));
   return NL_OK;
 }
 
@@ -845,7 +889,7 @@ __global__ void __launch_bounds__(256) k_convert_offsets(const SRC* __restrict__
 // else a converted copy made once per build.  A wide list that an int32 cannot address is NL_ERR_INDEX_OVERFLOW.
 int key_pointer_as(nl_handle_t h, int width, const void** out) {
   const bool want_wide = width == 64;
-  if (want_wide == h->b_wide) {
+  if (want_wide == h->plan.wide) {
     *out = h->key_pointer;
     return NL_OK;
   }
@@ -932,7 +976,7 @@ int get_csr(nl_handle_t h, bool full, int width, const void** key_pointer_dev, c
   if (!h) return NL_ERR_ARG;
   int rc = nl_synchronize(h);
   if (rc) return rc;
-  if (h->b_full != full) return fail(h, NL_ERR_STATE);
+  if (h->plan.full != full) return fail(h, NL_ERR_STATE);
   if (key_pointer_dev)
     if ((rc = key_pointer_as(h, width, key_pointer_dev))) return rc;
   if (!key_pointer_dev && width == 32 && list_total(h) > 2147483647LL) return fail(h, NL_ERR_INDEX_OVERFLOW);
@@ -1022,18 +1066,12 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
     if (const char* v = getenv("NL_SWEEP_VARIANT")) h->sweep_variant = atoi(v) <= 1 ? 1 : 3;
-    if (const char* v = getenv("NL_ISPLIT")) h->isplit_env = std::max(0, atoi(v));
-    if (const char* v = getenv("NL_DENSE_MASKS")) h->dense_masks_off = atoi(v) == 0;
     if (const char* v = getenv("NL_ROWS")) h->rows_env = std::max(-1, std::min(atoi(v), 4));
-    if (const char* v = getenv("NL_LEAN_SMALL")) h->lean_small_env = atoi(v) != 0;
-    if (const char* v = getenv("NL_FILL_SMALL")) h->fill_small_env = atoi(v) != 0;
     if (const char* v = getenv("NL_OFFSET_WIDTH")) h->offset_width = atoi(v) == 64 ? 64 : atoi(v) == 32 ? 32 : 0;
     if (const char* v = getenv("NL_BINNING")) h->bin_two_level = atoi(v) != 1;
     if (const char* v = getenv("NL_BIN_BUCKETS")) h->bucket_env = atoi(v) != 0;
     if (const char* v = getenv("NL_GRAPH")) h->use_graph = atoi(v) != 0;
     if (const char* v = getenv("NL_DEBUG_FLAGS")) h->dbg_flags = atoi(v);
-    if (const char* v = getenv("NL_DEBUG_WG_PER_CU")) h->dbg_wg_per_cu = std::max(1, atoi(v));
-    if (const char* v = getenv("NL_DEBUG_LDS_PAD")) h->dbg_lds_pad = std::max(0, atoi(v));
   }
   *out = h;
   return NL_OK;
@@ -1078,7 +1116,7 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   // (zero once: a build that leaves out k_sweep_list_f32 -- and then runs again -- scans the stale counts of the cells it
   // listed, which must be counts of earlier builds, never garbage)
   HIPCHK(h, hipMemset(h->count, 0, 4 * (n + 32)));
-  if ((rc = dev_alloc(h, &h->key_pointer, 8 * (n + 32)))) return rc;  // int32 or int64 offsets (b_wide)
+  if ((rc = dev_alloc(h, &h->key_pointer, 8 * (n + 32)))) return rc;  // int32 or int64 offsets (BuildPlan::wide)
   if (h->kp_alt) (void)hipFree(h->kp_alt), h->kp_alt = nullptr;
   h->kp_alt_valid = false;
   if (h->resort_buf) (void)hipFree(h->resort_buf), h->resort_buf = nullptr;
@@ -1188,37 +1226,38 @@ int nl_set_capacity(nl_handle_t h, int64_t max_pairs) {
 
 namespace {
 // part = PART_ALL: the whole build.  PART_BEGIN: validate, remember the arguments, enqueue what needs only the owned
-// particles.  PART_FINISH: enqueue the rest with the remembered arguments.
-int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, const int32_t* gid_dev, int32_t n_rows,
-                        int32_t n, int32_t n_ghost_lo, int32_t z_lo, int32_t z_hi, void* stream, int sync, int part) {
+// particles.  PART_FINISH: enqueue the rest with the remembered arguments.  a: without mzl and slab, which follow from
+// z_lo and z_hi.
+int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, int sync, int part) {
   if (!h) return NL_ERR_ARG;
   if (part == PART_FINISH) {
     if (!h->begun) return fail(h, NL_ERR_STATE);
     // the second half reuses what the first half is still writing (row totals, the owned region of the sorted array):
     // it must be ordered behind it, i.e. enqueued on the same stream
     if ((hipStream_t)stream != h->last_stream) return fail(h, NL_ERR_STATE);
-    q_dev = h->b_q, q_stride = h->b_stride, gid_dev = h->b_gid, n_rows = h->n_rows, n = h->n, n_ghost_lo = h->begun_ghost_lo;
-    z_lo = h->begun_zlo, z_hi = h->begun_zhi;
+    a = h->args;
+    z_hi = a.z_lo + a.mzl - 2 * a.slab;
   }
   h->begun = false;
   h->upd_valid = false, h->last_update = false;  // (only an update's build writes the snapshot)
+  const int32_t n = a.n, n_rows = a.n_rows, z_lo = a.z_lo;
   if (h->n_max <= 0 && n > 0) return fail(h, NL_ERR_STATE);
-  if (n < 0 || n_rows < 0 || n_rows > n || n > h->n_max || (q_stride != 3 && q_stride != 4) || (!q_dev && n > 0))
+  if (n < 0 || n_rows < 0 || n_rows > n || n > h->n_max || (a.stride != 3 && a.stride != 4) || (!a.q && n > 0))
     return fail(h, NL_ERR_ARG);
-  if (n_ghost_lo < 0 || n_ghost_lo > n - n_rows) return fail(h, NL_ERR_ARG);
-  if (gid_dev == NL_GID_IN_W && q_stride != 4) return fail(h, NL_ERR_ARG);
+  if (a.n_ghost_lo < 0 || a.n_ghost_lo > n - n_rows) return fail(h, NL_ERR_ARG);
+  if (a.gid == NL_GID_IN_W && a.stride != 4) return fail(h, NL_ERR_ARG);
   const int32_t mz = h->m[2];
   if (z_lo < 0 || z_hi > mz || z_lo >= z_hi) return fail(h, NL_ERR_ARG);
   const int32_t owned = z_hi - z_lo;
-  int32_t slab = 1, mzl = owned + 2;
+  a.slab = 1, a.mzl = owned + 2;
   if (owned == mz) {
-    slab = 0, mzl = mz;
+    a.slab = 0, a.mzl = mz;
     if (n_rows != n) return fail(h, NL_ERR_ARG);
   } else if (mz - owned < 2) {
     return fail(h, NL_ERR_ARG);  // the two ghost layers would be the same layer
   }
   // an exclusion table applies to whole single-device builds of its own particle count
-  if (h->ex_ids && (slab || gid_dev || h->b_dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  if (h->ex_ids && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
   if (h->ex_ids && n != h->ex_n) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (h->ex_ids)  // (again, if an allocation failed since the table was set)
@@ -1236,51 +1275,26 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
   h->built = false;
   h->t_valid = false;
   h->n = n, h->n_rows = n_rows;
+  // (planned before a graph key is formed: the plan's allocations bump buffers_epoch; a graph replays this plan)
+  const BuildPlan p = plan_for(h, a, part, false);
   int rc;
   if (part == PART_BEGIN) {
-    rc = dispatch_build(h, q_dev, q_stride, gid_dev, n_rows, n, z_lo, mzl, slab, s, nullptr, PART_BEGIN, n_ghost_lo);
-    if (rc) return rc;
-    h->begun = true, h->begun_ghost_lo = n_ghost_lo, h->begun_zlo = z_lo, h->begun_zhi = z_hi;
+    if ((rc = dispatch_build(h, a, p, s, nullptr, PART_BEGIN))) return rc;
+    h->begun = true;
     h->last_stream = s;
     return NL_OK;
   }
   if (h->use_graph && part == PART_ALL) {
-    // The handle's per-build state first (on replay: the captured build's, whatever ran in between): it picks the
-    // launches the graph holds.  Whatever the build has to allocate -- the mask rows of a first dense build, the row
-    // buckets -- is allocated here, before a capture.
-    if (h->dtype == NL_F32) set_build_state<float>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
-    else set_build_state<double>(h, q_dev, q_stride, gid_dev, n, z_lo, mzl, slab);
-    nl_handle_s::GraphKey key;
-    key.q = q_dev, key.gid = gid_dev, key.stride = q_stride, key.n_rows = n_rows, key.n = n, key.z_lo = z_lo, key.mzl = mzl;
-    key.slab = slab, key.list_kind = h->list_kind, key.pbc_mask = h->pbc, key.capacity = h->capacity;
-    key.epoch = h->buffers_epoch, key.offset_width = h->offset_width;
-    key.cap_row = h->b_cap_row, key.list = h->b_list ? 1 : 0;
-    key.excl = h->ex_gen;
-    if (!h->graph_exec || !(key == h->graph_key)) {
-      if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec), h->graph_exec = nullptr;
-      if (h->graph) (void)hipGraphDestroy(h->graph), h->graph = nullptr;
-      // captured on the private stream (the null stream cannot be captured); replayed on the caller's stream
-      HIPCHK(h, hipStreamBeginCapture(h->own_stream, hipStreamCaptureModeRelaxed));
-      rc = dispatch_build(h, q_dev, q_stride, gid_dev, n_rows, n, z_lo, mzl, slab, h->own_stream, nullptr);
-      if (!rc) rc = enqueue_result_copy(h, h->own_stream);
-      hipGraph_t g = nullptr;
-      const hipError_t e = hipStreamEndCapture(h->own_stream, &g);
-      if (rc) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-      }
-      HIPCHK(h, e);
-      h->graph = g;
-      HIPCHK(h, hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
-      h->graph_key = key;
-    }
-    HIPCHK(h, hipGraphLaunch(h->graph_exec, s));
+    adopt_build(h, a, p);  // (on replay: the captured build's arguments and plan, whatever ran in between)
+    rc = graph_launch(h, GraphKey{a, p, h->capacity, h->buffers_epoch, h->ex_gen}, s, [&](hipStream_t cs) {
+      const int rc = dispatch_build(h, a, p, cs, nullptr);
+      return rc ? rc : enqueue_result_copy(h, cs);
+    });
   } else {
-    rc = dispatch_build(h, q_dev, q_stride, gid_dev, n_rows, n, z_lo, mzl, slab, s, nullptr, part, n_ghost_lo);
-    if (rc) return rc;
-    rc = enqueue_result_copy(h, s);
-    if (rc) return rc;
+    rc = dispatch_build(h, a, p, s, nullptr, part);
+    if (!rc) rc = enqueue_result_copy(h, s);
   }
+  if (rc) return rc;
   h->last_stream = s;
   h->pending = true;
   if (h->list_quiet < LIST_QUIET_BUILDS) h->list_quiet++;
@@ -1291,18 +1305,16 @@ int make_list_slab_part(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
 
 int nl_make_list_slab(nl_handle_t h, const void* q_dev, int32_t q_stride, const int32_t* gid_dev, int32_t n_rows,
                       int32_t n, int32_t z_lo, int32_t z_hi, void* stream, int sync) {
-  if (h) h->b_dyn = nullptr, h->dyn_host = nullptr;
-  return make_list_slab_part(h, q_dev, q_stride, gid_dev, n_rows, n, 0, z_lo, z_hi, stream, sync, PART_ALL);
+  return make_list_slab_part(h, BuildArgs{q_dev, q_stride, gid_dev, n_rows, n, 0, z_lo}, z_hi, stream, sync, PART_ALL);
 }
 
 int nl_make_list_slab_begin(nl_handle_t h, const void* q_dev, int32_t q_stride, const int32_t* gid_dev, int32_t n_rows,
                             int32_t n, int32_t n_ghost_lo, int32_t z_lo, int32_t z_hi, void* stream) {
-  if (h) h->b_dyn = nullptr, h->dyn_host = nullptr;
-  return make_list_slab_part(h, q_dev, q_stride, gid_dev, n_rows, n, n_ghost_lo, z_lo, z_hi, stream, 0, PART_BEGIN);
+  return make_list_slab_part(h, BuildArgs{q_dev, q_stride, gid_dev, n_rows, n, n_ghost_lo, z_lo}, z_hi, stream, 0, PART_BEGIN);
 }
 
 int nl_make_list_slab_finish(nl_handle_t h, void* stream, int sync) {
-  return make_list_slab_part(h, nullptr, 0, nullptr, 0, 0, 0, 0, 0, stream, sync, PART_FINISH);
+  return make_list_slab_part(h, BuildArgs{}, 0, stream, sync, PART_FINISH);
 }
 
 int nl_make_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, void* stream, int sync) {
@@ -1348,15 +1360,17 @@ int nl_list_checksum(nl_handle_t h, uint64_t* checksum, int64_t* nentries) {
   const int32_t n = h->n_rows;
   if (n > 0) {
     const int32_t grid = std::max(1, std::min((n + 3) / 4, 8 * h->num_cus));
-    const bool w = h->b_wide, f32 = h->dtype == NL_F32;
+    const bool w = h->plan.wide, f32 = h->dtype == NL_F32;
+    const int32_t* gid = h->args.gid;
+    const void* q = h->args.q;
     if (f32 && !w)
-      hipLaunchKernelGGL((k_list_checksum<float, int32_t>), dim3(grid), dim3(256), 0, s, static_cast<const int32_t*>(h->key_pointer), h->list, n, h->b_gid, static_cast<const float*>(h->b_q), acc);
+      hipLaunchKernelGGL((k_list_checksum<float, int32_t>), dim3(grid), dim3(256), 0, s, static_cast<const int32_t*>(h->key_pointer), h->list, n, gid, static_cast<const float*>(q), acc);
     else if (f32)
-      hipLaunchKernelGGL((k_list_checksum<float, int64_t>), dim3(grid), dim3(256), 0, s, static_cast<const int64_t*>(h->key_pointer), h->list, n, h->b_gid, static_cast<const float*>(h->b_q), acc);
+      hipLaunchKernelGGL((k_list_checksum<float, int64_t>), dim3(grid), dim3(256), 0, s, static_cast<const int64_t*>(h->key_pointer), h->list, n, gid, static_cast<const float*>(q), acc);
     else if (!w)
-      hipLaunchKernelGGL((k_list_checksum<double, int32_t>), dim3(grid), dim3(256), 0, s, static_cast<const int32_t*>(h->key_pointer), h->list, n, h->b_gid, static_cast<const double*>(h->b_q), acc);
+      hipLaunchKernelGGL((k_list_checksum<double, int32_t>), dim3(grid), dim3(256), 0, s, static_cast<const int32_t*>(h->key_pointer), h->list, n, gid, static_cast<const double*>(q), acc);
     else
-      hipLaunchKernelGGL((k_list_checksum<double, int64_t>), dim3(grid), dim3(256), 0, s, static_cast<const int64_t*>(h->key_pointer), h->list, n, h->b_gid, static_cast<const double*>(h->b_q), acc);
+      hipLaunchKernelGGL((k_list_checksum<double, int64_t>), dim3(grid), dim3(256), 0, s, static_cast<const int64_t*>(h->key_pointer), h->list, n, gid, static_cast<const double*>(q), acc);
     HIPCHK(h, hipGetLastError());
   }
   unsigned long long out = 0;
@@ -1381,7 +1395,7 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream) {
     return fail(h, NL_ERR_ARG);
   int rc = nl_synchronize(h);  // the permutation is the last build's
   if (rc) return rc;
-  if (h->b_slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // a permutation of the caller's own particles
+  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // a permutation of the caller's own particles
   h->upd_valid = false;  // (the snapshot holds the old order)
   HIPCHK(h, hipSetDevice(h->device));
   const int32_t n = h->n;
@@ -1431,7 +1445,7 @@ int nl_number_of_pairs(nl_handle_t h, int64_t* npairs) {
   if (!h || !npairs) return fail(h, NL_ERR_ARG);
   int rc = nl_synchronize(h);
   if (rc) return rc;
-  *npairs = h->b_full ? list_total(h) / 2 : list_total(h);
+  *npairs = h->plan.full ? list_total(h) / 2 : list_total(h);
   return NL_OK;
 }
 
@@ -1451,7 +1465,7 @@ int nl_get_sorted(nl_handle_t h, const int32_t** cell_start_dev, const void** so
   if (cell_start_dev) *cell_start_dev = h->cell_start;
   if (sorted_pos_dev) *sorted_pos_dev = h->sorted;
   if (sorted_row_dev) *sorted_row_dev = h->sorted_row;
-  if (ncell_local) *ncell_local = h->ncell_local;
+  if (ncell_local) *ncell_local = (int64_t)h->m[0] * h->m[1] * h->args.mzl;
   return NL_OK;
 }
 
@@ -1485,11 +1499,12 @@ int nl_debug_occupancy(int32_t out[8]) {
 int nl_get_build_info(nl_handle_t h, int32_t info[8]) {
   if (!h || !info) return NL_ERR_ARG;
   for (int k = 4; k < 8; k++) info[k] = 0;
-  info[4] = h->b_wide ? 64 : 32;
-  info[5] = h->b_mask_nb;
-  info[6] = h->b_rows ? 1 + h->b_rows_v : 0;  // fine-row search: the cell table of nl_get_sorted is the fine-row table
-  info[7] = h->b_use_masks && !h->b_rows && h->b_mask_nb == 1 && h->dtype == NL_F32 && h->b_pbc == 0 && h->b_lean_small ? 1 : 0;
-  info[0] = h->b_use_masks ? 1 : 0;
+  const BuildPlan& p = h->plan;
+  info[4] = p.wide ? 64 : 32;
+  info[5] = p.mask_nb;
+  info[6] = p.search == SEARCH_ROWS ? 1 + p.rows_v : 0;  // fine-row search: the cell table of nl_get_sorted is the fine-row table
+  info[7] = p.small ? 1 : 0;
+  info[0] = p.search != SEARCH_SWEEPS ? 1 : 0;
   info[1] = h->sweep_variant;
   info[2] = h->dtype == NL_F32 ? SweepCfg<float>::CAP : SweepCfg<double>::CAP;
   info[3] = h->num_cus;
@@ -1500,8 +1515,8 @@ int nl_get_build_stats(nl_handle_t h, int64_t stats[4]) {
   if (!h || !stats) return NL_ERR_ARG;
   stats[0] = h->reruns[0];
   stats[1] = h->reruns[1];
-  stats[2] = h->b_cap_row;
-  stats[3] = h->b_list ? 1 : 0;
+  stats[2] = h->plan.cap_row;
+  stats[3] = h->plan.list ? 1 : 0;
   return NL_OK;
 }
 
@@ -1516,8 +1531,11 @@ int nl_profile_last_build(nl_handle_t h, int32_t reps, double ms[NL_NUM_STAGES])
   for (int k = 0; k < NL_NUM_STAGES; k++) ms[k] = 0;
   hipStream_t s = h->own_stream;
   HIPCHK(h, hipStreamSynchronize(h->last_stream));
+  BuildArgs a = h->args;
+  a.n = h->n;  // (a distributed build: the particles finish() has counted)
+  const BuildPlan p = plan_for(h, a, PART_ALL, false);
   for (int r = 0; r < reps; r++) {
-    rc = dispatch_build(h, h->b_q, h->b_stride, h->b_gid, h->n_rows, h->n, h->b_zlo, h->b_mzl, h->b_slab, s, h->ev);
+    rc = dispatch_build(h, a, p, s, h->ev);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(s));
     for (int k = 0; k < NL_STAGE_TOTAL; k++) {

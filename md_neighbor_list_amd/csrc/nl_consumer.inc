@@ -86,8 +86,8 @@ int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, double eps, doub
   if (n == 0) return NL_OK;
   // box lengths for the minimum image on the axes of the list's build; 0 = open axis (the reference's distances,
   // neighlist_cpu.hpp:219-223)
-  const T Lx = (h->b_pbc & 1) ? (T)h->L[0] : (T)0, Ly = (h->b_pbc & 2) ? (T)h->L[1] : (T)0, Lz = (h->b_pbc & 4) ? (T)h->L[2] : (T)0;
-  if (h->b_full) {
+  const T Lx = (h->plan.pbc & 1) ? (T)h->L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)h->L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)h->L[2] : (T)0;
+  if (h->plan.full) {
     hipLaunchKernelGGL((k_lj<T, false, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer),
                        h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz, status);
   } else {
@@ -106,11 +106,11 @@ extern "C" int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, 
   if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4) || !(rc_force > 0) || !(sigma > 0)) return fail(h, NL_ERR_ARG);
   int rc = nl_synchronize(h);  // the list must be complete (and its build must have succeeded)
   if (rc) return rc;
-  if (h->b_slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
+  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
   if (rc_force > h->rc) return fail(h, NL_ERR_ARG);                   // the list does not reach that far
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
-  if (h->b_wide)
+  if (h->plan.wide)
     return h->dtype == NL_F32 ? lj_launch<float, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s)
                               : lj_launch<double, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s);
   return h->dtype == NL_F32 ? lj_launch<float, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s)
@@ -127,9 +127,9 @@ extern "C" int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_
   // a pending build must be an update's (a plain asynchronous build may still need finish() to complete its list) and
   // enqueued on this stream
   if (h->pending && (!h->last_update || s != h->last_stream)) return fail(h, NL_ERR_STATE);
-  if (h->b_slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
+  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->b_wide)
+  if (h->plan.wide)
     return h->dtype == NL_F32 ? lj_launch<float, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status)
                               : lj_launch<double, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status);
   return h->dtype == NL_F32 ? lj_launch<float, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status)

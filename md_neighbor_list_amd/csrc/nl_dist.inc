@@ -243,7 +243,7 @@ int nl_comm_destroy(nl_comm_t c) {
   (void)hipSetDevice(c->device);
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->comm && c->p_CommDestroy) (void)c->p_CommDestroy(c->comm);
-  if (c->last_h && c->last_h->dyn_host == c->counts_host) c->last_h->dyn_host = nullptr, c->last_h->b_dyn = nullptr;
+  if (c->last_h && c->last_h->args.dyn_host == c->counts_host) c->last_h->args.dyn_host = nullptr, c->last_h->args.dyn = nullptr;
   for (int k = 0; k < 2; k++) {
     if (c->send_buf[k]) (void)hipFree(c->send_buf[k]);
     if (c->recv_buf[k]) (void)hipFree(c->recv_buf[k]);
@@ -341,8 +341,10 @@ namespace {
 template <typename T> void launch_pack(nl_handle_t h, nl_comm_t c, const void* q_dev, int32_t n_owned, int32_t z_lo, int32_t mzl, int32_t cap_lo,
                                        int32_t cap_hi, hipStream_t s) {
   if (n_owned <= 0) return;
+  BuildArgs a;  // (the owned rows of a slab build)
+  a.n_rows = n_owned, a.z_lo = z_lo, a.mzl = mzl, a.slab = 1;
   hipLaunchKernelGGL(k_pack_layers<T>, dim3((n_owned + 255) / 256), dim3(256), 0, s, static_cast<const T*>(q_dev), n_owned,
-                     make_grid<T>(h, n_owned, z_lo, mzl, 1), static_cast<T*>(c->send_buf[0]), static_cast<T*>(c->send_buf[1]), cap_lo, cap_hi,
+                     make_grid<T>(h, a, h->pbc), static_cast<T*>(c->send_buf[0]), static_cast<T*>(c->send_buf[1]), cap_lo, cap_hi,
                      c->counts_dev);
 }
 
@@ -390,7 +392,8 @@ int nl_make_list_distributed(nl_handle_t h, nl_comm_t c, void* q_dev, int32_t q_
   int32_t z_lo = 0, z_hi = 0;
   if (!split_layers(h->m[2], c->world, c->rank, &z_lo, &z_hi)) return fail(h, NL_ERR_ARG);
   c->z_lo = z_lo, c->z_hi = z_hi;
-  if (c->last_h && c->last_h != h && c->last_h->dyn_host == c->counts_host) c->last_h->dyn_host = nullptr, c->last_h->b_dyn = nullptr;
+  if (c->last_h && c->last_h != h && c->last_h->args.dyn_host == c->counts_host)
+    c->last_h->args.dyn_host = nullptr, c->last_h->args.dyn = nullptr;
   c->last_h = h;
   if (c->world == 1) {  // the whole box: the periodic wrap stays inside the build
     return nl_make_list_slab(h, q_dev, 4, NL_GID_IN_W, n_owned, n_owned, 0, h->m[2], stream, sync);
@@ -402,7 +405,7 @@ int nl_make_list_distributed(nl_handle_t h, nl_comm_t c, void* q_dev, int32_t q_
   int32_t* cnt = c->counts_host;
   // the device-side ghost counts need the two-level binning (BinPhase::dyn); meshes beyond its tables take the atomic-rank
   // path, which wants the particle count on the host: there the counts are read back (one wait per build)
-  const bool dyn_ok = h->bin_two_level && (int64_t)h->m[1] * mzl <= BIN_MAX_ROWS && h->m[0] <= BIN_MAX_MX;
+  const bool dyn_ok = two_level_ok(h, mzl);
   // an earlier asynchronous build whose result has arrived: did its messages hold what was sent?
   if (c->check_pending && hipEventQuery(c->ev_result) == hipSuccess) {
     c->check_pending = false;
@@ -475,9 +478,10 @@ int nl_make_list_distributed(nl_handle_t h, nl_comm_t c, void* q_dev, int32_t q_
     if (dyn_ok) {
       // the build: as many rows as the messages can bring at most; how many ghosts there are it reads on the device
       const int32_t n_upper = (int32_t)std::min<int64_t>((int64_t)n_owned + rcap_lo + rcap_hi, room);
-      h->b_dyn = c->counts_dev + 2, h->dyn_host = cnt;
-      h->b_n_est = (int32_t)std::min<int64_t>(n_upper, (int64_t)n_owned + (c->rcap[0] - 1024) * 4 / 5 + (c->rcap[1] - 1024) * 4 / 5);
-      rc = make_list_slab_part(h, q_dev, 4, NL_GID_IN_W, n_owned, n_upper, 0, z_lo, z_hi, stream, sync, PART_ALL);
+      BuildArgs a{q_dev, 4, NL_GID_IN_W, n_owned, n_upper, 0, z_lo};
+      a.dyn = c->counts_dev + 2, a.dyn_host = cnt;
+      a.n_est = (int32_t)std::min<int64_t>(n_upper, (int64_t)n_owned + (c->rcap[0] - 1024) * 4 / 5 + (c->rcap[1] - 1024) * 4 / 5);
+      rc = make_list_slab_part(h, a, z_hi, stream, sync, PART_ALL);
     } else {
       HIPCHK(h, hipStreamSynchronize(s));
       rc = cnt[4] ? NL_ERR_CAPACITY : nl_make_list_slab(h, q_dev, 4, NL_GID_IN_W, n_owned, n_owned + cnt[2] + cnt[3], z_lo, z_hi, stream, sync);

@@ -111,7 +111,7 @@ template <typename OFF> int launch_exclude_w(nl_handle_t h, int32_t n_rows, hipS
 
 // (declared at the top of nl_api.hip)
 int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s) {
-  return h->b_wide ? launch_exclude_w<int64_t>(h, n_rows, s) : launch_exclude_w<int32_t>(h, n_rows, s);
+  return h->plan.wide ? launch_exclude_w<int64_t>(h, n_rows, s) : launch_exclude_w<int32_t>(h, n_rows, s);
 }
 
 // The pre-exclusion offsets and list while a table is set (one offset array, one list capacity); nothing without one.

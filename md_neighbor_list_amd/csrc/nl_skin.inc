@@ -7,7 +7,7 @@
 //   the build      the build of nl_make_list, every launch of which leaves at entry while go == 0 (gate_closed)
 //   k_skin_snap    go == 1: snapshot <- q
 //   result copy    the meta words, as after any build (after a skipped update: the last build's, again)
-// The build is the one finish() would run again (h->rerun): two-pass binning and every launch of its path, because an
+// The build is the one finish() would run again (plan_build's rerun): two-pass binning and every launch of its path, because an
 // asynchronous MD loop never calls finish().
 // Included at the end of nl_api.hip.
 
@@ -84,19 +84,19 @@ __global__ void __launch_bounds__(256) k_skin_snap(const T* __restrict__ q, T* _
   for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += (int64_t)gridDim.x * blockDim.x) snap[k] = q[k];
 }
 
-// The launches of one update on stream s (see the top of this file).  force: a reason the host knows (rule (a)).
+// The launches of one update on stream s (see the top of this file): the build of arguments a along plan p (made with
+// rerun).  force: a reason the host knows (rule (a)).
 template <typename T>
-int enqueue_update(nl_handle_t h, const void* q_dev, int32_t stride, int32_t n, bool force, hipStream_t s) {
-  const int32_t mz = h->m[2], nrows = h->m[1] * mz;
-  // (enqueue_build's choice for a whole build: the two-pass binning clears meta words + row totals, which k_skin_check
-  // does here; the atomic-rank binning clears histogram + meta words with a gated launch of its own)
-  const bool two_level = h->bin_two_level && nrows <= BIN_MAX_ROWS && h->m[0] <= BIN_MAX_MX;
+int enqueue_update(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, bool force, hipStream_t s) {
+  const int32_t n = a.n, stride = a.stride, nrows = h->m[1] * a.mzl;
   const double half = 0.5 * h->skin, thr = half * half;
   const int32_t grid = std::max(1, std::min((n + 4 * SKIN_THREADS - 1) / (4 * SKIN_THREADS), 4 * h->num_cus));
-  const T* q = static_cast<const T*>(q_dev);
+  const T* q = static_cast<const T*>(a.q);
   T* snap = static_cast<T*>(h->snap);
+  // (the two-pass binning of the build clears meta words + row totals, which k_skin_check does here; the atomic-rank
+  // binning clears histogram + meta words with a gated launch of its own)
   int32_t* zero = reinterpret_cast<int32_t*>(h->status);
-  const int32_t nzero = two_level ? 32 + nrows : 0;
+  const int32_t nzero = p.binning == BINNING_TWO_PASS ? 32 + nrows : 0;
   if (h->pbc != 0)
     hipLaunchKernelGGL((k_skin_check<T, true>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, h->L[0], h->L[1],
                        h->L[2], h->pbc, force ? 1 : 0, h->skin_words, h->status, zero, nzero);
@@ -104,9 +104,7 @@ int enqueue_update(nl_handle_t h, const void* q_dev, int32_t stride, int32_t n, 
     hipLaunchKernelGGL((k_skin_check<T, false>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, h->L[0], h->L[1],
                        h->L[2], 0, force ? 1 : 0, h->skin_words, h->status, zero, nzero);
   h->gate = h->skin_words + SKIN_GO;
-  h->rerun = true;
-  int rc = enqueue_build<T>(h, q_dev, stride, nullptr, n, n, 0, mz, 0, s, nullptr);
-  h->rerun = false;
+  int rc = enqueue_build<T>(h, a, p, s, nullptr);
   if (!rc) {
     const int64_t count = (int64_t)n * stride;
     const uint32_t sgrid = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((count + 1023) / 1024, 1024));
@@ -118,9 +116,8 @@ int enqueue_update(nl_handle_t h, const void* q_dev, int32_t stride, int32_t n, 
   return rc;
 }
 
-int dispatch_update(nl_handle_t h, const void* q_dev, int32_t stride, int32_t n, bool force, hipStream_t s) {
-  return h->dtype == NL_F32 ? enqueue_update<float>(h, q_dev, stride, n, force, s)
-                            : enqueue_update<double>(h, q_dev, stride, n, force, s);
+int dispatch_update(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, bool force, hipStream_t s) {
+  return h->dtype == NL_F32 ? enqueue_update<float>(h, a, p, force, s) : enqueue_update<double>(h, a, p, force, s);
 }
 
 }  // namespace
@@ -168,44 +165,19 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
       HIPCHK(h, hipMemset(h->skin_words, 0, sizeof(uint32_t) * SKIN_WORDS));
     }
   }
-  h->b_dyn = nullptr, h->dyn_host = nullptr;
   h->built = false;
   h->t_valid = false;
   h->n = n, h->n_rows = n;
-  const int32_t mz = h->m[2];
+  const BuildArgs a{q_dev, q_stride, nullptr, n, n, 0, 0, h->m[2], 0};
+  const BuildPlan p = plan_for(h, a, PART_ALL, true);  // (an update's build: two-pass binning, every launch)
   if (h->use_graph && !capturing && !force) {
     // the same graph as nl_make_list's (one per argument set), keyed also on the update and its skin; a forced update
     // runs as plain launches and the next one captures
-    h->rerun = true;  // (the build state of an update's build: two-pass binning, every launch)
-    if (h->dtype == NL_F32) set_build_state<float>(h, q_dev, q_stride, nullptr, n, 0, mz, 0);
-    else set_build_state<double>(h, q_dev, q_stride, nullptr, n, 0, mz, 0);
-    h->rerun = false;
-    nl_handle_s::GraphKey key;
-    key.q = q_dev, key.gid = nullptr, key.stride = q_stride, key.n_rows = n, key.n = n, key.z_lo = 0, key.mzl = mz;
-    key.slab = 0, key.list_kind = h->list_kind, key.pbc_mask = h->pbc, key.capacity = h->capacity;
-    key.epoch = h->buffers_epoch, key.offset_width = h->offset_width;
-    key.cap_row = h->b_cap_row, key.list = h->b_list ? 1 : 0;
-    key.update = 1, key.skin = h->skin;
-    key.excl = h->ex_gen;
-    if (!h->graph_exec || !(key == h->graph_key)) {
-      if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec), h->graph_exec = nullptr;
-      if (h->graph) (void)hipGraphDestroy(h->graph), h->graph = nullptr;
-      HIPCHK(h, hipStreamBeginCapture(h->own_stream, hipStreamCaptureModeRelaxed));
-      const int rc = dispatch_update(h, q_dev, q_stride, n, false, h->own_stream);
-      hipGraph_t g = nullptr;
-      const hipError_t e = hipStreamEndCapture(h->own_stream, &g);
-      if (rc) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-      }
-      HIPCHK(h, e);
-      h->graph = g;
-      HIPCHK(h, hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
-      h->graph_key = key;
-    }
-    HIPCHK(h, hipGraphLaunch(h->graph_exec, s));
+    adopt_build(h, a, p);
+    const GraphKey key{a, p, h->capacity, h->buffers_epoch, h->ex_gen, 1, h->skin};
+    if (int rc = graph_launch(h, key, s, [&](hipStream_t cs) { return dispatch_update(h, a, p, false, cs); })) return rc;
   } else {
-    if (int rc = dispatch_update(h, q_dev, q_stride, n, force, s)) return rc;
+    if (int rc = dispatch_update(h, a, p, force, s)) return rc;
   }
   h->upd_valid = true, h->last_update = true;
   h->upd_q = q_dev, h->upd_stride = q_stride, h->upd_n = n;

@@ -135,14 +135,14 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
   if (!h) return NL_ERR_ARG;
   int rc = nl_synchronize(h);
   if (rc) return rc;
-  if (h->b_slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must be row indices
+  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must be row indices
   const int32_t n = h->n;
   // this layout is the reference GPU class's (int32 throughout, neighlist_gpu.hpp:468-487): a list that an int32
   // key_pointer cannot address has no transposed form
   const void* kp_any = nullptr;
   if (!h->t_valid && (rc = key_pointer_as(h, 32, &kp_any))) return rc;
   const int32_t* const kp32 = static_cast<const int32_t*>(kp_any);
-  if (!h->t_valid && h->b_full) {
+  if (!h->t_valid && h->plan.full) {
     // the build produced the full CSR: counts are the full counts already, one coalesced conversion pass
     hipStream_t s = h->own_stream;
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
@@ -214,7 +214,7 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
     h->t_valid = true;
   }
   if (list_dev) *list_dev = h->t_list;
-  if (count_dev) *count_dev = h->b_full ? h->count : h->t_count;
+  if (count_dev) *count_dev = h->plan.full ? h->count : h->t_count;
   if (row_stride) *row_stride = n;
   if (max_partners) *max_partners = h->t_max;
   return NL_OK;
