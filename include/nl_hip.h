@@ -285,6 +285,35 @@ int nl_get_update_stats(nl_handle_t h, int64_t stats[2]);
 int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n);
 int nl_get_exclusions(nl_handle_t h, const int32_t** offsets_dev, const int32_t** ids_dev, int32_t* n, int64_t* n_unique);
 
+/* ---------------------------------------------------------------------------------------------- type cut-offs */
+
+/* Per-type cut-offs (no reference counterpart): mixtures whose model sets a cut-off per pair of types (the Kob-Andersen
+ * binary glass, coarse-grained beads of several sizes, solvent around solutes), as LAMMPS pair_coeff and HOOMD r_cut do.
+ * The search still runs at the handle's rc; a stage behind it (the one of the exclusions) keeps what the table allows.
+ *   The rule: with a table set, a build keeps an entry (row i, partner j) of the list it would build without the table
+ *     iff !(r2 > rc2[t_i][t_j]).  r2 is the value the search tested for that entry: (dx*dx + dy*dy) + dz*dz in the
+ *     position type T without FMA, at the image the search used (a wrapped particle's stored image, the -+L shift of a
+ *     periodic face rounded to T first); rc2[a][b] is the largest T <= rc_ab * rc_ab in double (the rounding of rc).
+ *     So all rc_ab == rc is the plain list, and rc_ab == 0 keeps only coincident pairs of that type pair.  Half list:
+ *     the row min(i, j) decides; full list: each row decides with its own r2 (across a periodic face the two rows may
+ *     disagree within one ulp, as the full list itself may).  With an exclusion table as well, one stage applies both:
+ *     an entry is kept if it is not excluded and within its rc_ab.  number_of_partners, key_pointer, npairs / nentries,
+ *     nl_number_of_pairs, nl_list_checksum, nl_get_full_transposed and nl_lj_forces(_enqueue) describe the filtered list.
+ *   nl_set_type_cutoffs: types_dev = device int32 [n] in input order (copied: the caller may free it), checked on the
+ *     device, 0 <= t < ntypes, and n <= n_max; ntypes = 1 .. NL_MAX_TYPES; rc_host = ntypes x ntypes doubles,
+ *     row-major, exactly symmetric, each in [0, rc] (the skin included, as in rc).  Anything else, NaN included, is
+ *     NL_ERR_ARG and the old table is kept.  types_dev == NULL or ntypes == 0 clears the table.  Synchronous: waits for
+ *     the device, finishes a pending build, and forces the next nl_update_list to build (its reason (a)).
+ *   nl_get_types: the handle's copy of the types (relabelled by a re-sort), n and ntypes; NL_ERR_STATE without a table.
+ *   As with the exclusion table: a build whose n differs from the table's is NL_ERR_ARG; slab and distributed builds are
+ *     NL_ERR_STATE while a table is set; capacity is counted before filtering (NL_ERR_CAPACITY and growth follow the
+ *     unfiltered total); the first nl_resort after a build permutes the types by that build's cell order,
+ *     types[s] <- types[order[s]], in the same buffer; setting, clearing or relabelling captures graphs again.
+ *     Builds without a table launch nothing of this. */
+#define NL_MAX_TYPES 32
+int nl_set_type_cutoffs(nl_handle_t h, const int32_t* types_dev, int32_t n, int32_t ntypes, const double* rc_host);
+int nl_get_types(nl_handle_t h, const int32_t** types_dev, int32_t* n, int32_t* ntypes);
+
 /* ------------------------------------------------------------------------------------------------- results */
 
 /* The CPU class's accessors (neighlist_cpu.hpp:437-463): key_pointer()[N+1], sorted_list()[P],
@@ -361,6 +390,16 @@ int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsi
  * says the list is invalid the forces are NaN; the error itself surfaces at the next nl_synchronize. */
 int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
                          void* f_dev, void* stream);
+/* Typed Lennard-Jones for a list built with a type table: epsilon, sigma and rc_force of a pair are [t_i][t_j] of
+ * ntypes x ntypes row-major, exactly symmetric matrices (sigma > 0, rc_force > 0, rc_force_ab <= rc_ab, finite
+ * epsilon; else NL_ERR_ARG).  nl_set_lj_type_params copies them to the device synchronously; its ntypes must be the type
+ * table's (NL_ERR_STATE without a table).  nl_lj_forces_typed(_enqueue) compute what nl_lj_forces(_enqueue) compute,
+ * with the same lists, masks, NaN rule and ordering, from those parameters; NL_ERR_STATE while the table or the
+ * parameters are missing, NL_ERR_ARG when they no longer match (ntypes, rc_force_ab > rc_ab), and the enqueue variant
+ * also needs rc_force_ab <= rc_ab - skin.  The enqueue variant copies nothing from the host: it can be captured. */
+int nl_set_lj_type_params(nl_handle_t h, int32_t ntypes, const double* epsilon, const double* sigma, const double* rc_force);
+int nl_lj_forces_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_lj_forces_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------- introspection */
 

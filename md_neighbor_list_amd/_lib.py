@@ -13,6 +13,7 @@ NL_OK = 0
 (NL_ERR_ARG, NL_ERR_NOMEM, NL_ERR_OUT_OF_BOX, NL_ERR_CAPACITY, NL_ERR_HIP, NL_ERR_STATE, NL_ERR_MESH,
  NL_ERR_INDEX_OVERFLOW, NL_ERR_NO_DEVICE, NL_ERR_DOMAIN, NL_ERR_COMM) = range(1, 12)
 NL_UNIQUE_ID_BYTES = 128
+NL_MAX_TYPES = 32
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t)
 _P, _I32, _I64, _SZ, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_double
 NL_NUM_STAGES = 7
@@ -57,6 +58,11 @@ PROTOTYPES = {
     "nl_get_update_stats": (C.c_int, [_P, C.POINTER(_I64 * 2)]),
     "nl_set_exclusions": (C.c_int, [_P, _P, _I64, _I32]),
     "nl_get_exclusions": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I32), C.POINTER(_I64)]),
+    "nl_set_type_cutoffs": (C.c_int, [_P, _P, _I32, _I32, C.POINTER(_D)]),
+    "nl_get_types": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I32), C.POINTER(_I32)]),
+    "nl_set_lj_type_params": (C.c_int, [_P, _I32, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
+    "nl_lj_forces_typed": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_lj_forces_typed_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_get_full_transposed": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I32)]),
     "nl_number_of_pairs": (C.c_int, [_P, C.POINTER(_I64)]),
     "nl_get_mesh": (C.c_int, [_P, C.POINTER(_I32 * 3), C.POINTER(_I64)]),

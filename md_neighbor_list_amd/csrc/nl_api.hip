@@ -25,7 +25,7 @@ struct HostResult {
   uint32_t tickets[17];
   uint32_t total_lo, total_hi;
   uint32_t bin_words[2];      // (k_bin_bucket's META_BIN_STATUS / META_BIN_DONE; zero between builds)
-  uint32_t kept_lo, kept_hi;  // (copied only by builds with an exclusion table: the list total after the stage)
+  uint32_t kept_lo, kept_hi;  // (copied only by builds that filter: the list total after the stage)
   int64_t total() const { return (int64_t)(((uint64_t)total_hi << 32) | total_lo); }
   int64_t kept() const { return (int64_t)(((uint64_t)kept_hi << 32) | kept_lo); }
 };
@@ -33,7 +33,7 @@ constexpr int META_TOTAL = 18;  // int32 offset of total_lo from the status word
 constexpr int META_FULL27 = 1;  // number of cells the COUNT sweep hands to the batched search (first "ticket" word)
 constexpr int META_FILL_LIST = 10;  // number of cells k_fill_masks hands to k_fill_list ("ticket" word 10)
 constexpr int META_WORDS = 20;
-constexpr int META_KEPT = 22;        // the list total after the exclusion stage (nl_exclude.inc), in the same copy
+constexpr int META_KEPT = 22;        // the list total after the filter stage (nl_exclude.inc, nl_types.inc), in the same copy
 constexpr int META_WORDS_EXCL = 24;  // (words 20, 21: k_bin_bucket's, META_BIN_STATUS / META_BIN_DONE)
 // k_sweep_list_f32 / k_fill_list are launched until this many builds in a row have been enqueued since one was seen to
 // hand them cells (and always by a build that runs one again)
@@ -81,9 +81,9 @@ struct BuildPlan {
   bool list = true;     // k_sweep_list_f32 / k_fill_list are launched (SEARCH_MASKS: the paths with those two kernels)
   bool full = false;    // full list (both directions), nl_set_list_kind
   bool wide = false;    // key_pointer / base_sorted hold int64 (the list may exceed INT32_MAX entries)
-  bool excl = false;    // the exclusion stage runs (nl_exclude.inc)
+  bool filter = false;  // the filter stage runs: an exclusion table (nl_exclude.inc), a type table (nl_types.inc) or both
   int32_t pbc = 0;      // axes of the minimum image (nl_set_periodic_axes)
-  auto tie() const { return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, excl, pbc); }
+  auto tie() const { return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, pbc); }
   bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
 };
 
@@ -94,9 +94,10 @@ struct GraphKey {
   int64_t capacity = 0;
   uint64_t buffers_epoch = 0;
   uint64_t ex_gen = 0;  // generation of the exclusion table (nl_set_exclusions)
+  uint64_t ty_gen = 0;  // generation of the type table (nl_set_type_cutoffs)
   int32_t update = 0;   // 1: nl_update_list's chain (check, gated build, snapshot, result copy) ...
   double skin = 0;      // ... and the skin its check was captured with
-  auto tie() const { return std::tie(args, plan, capacity, buffers_epoch, ex_gen, update, skin); }
+  auto tie() const { return std::tie(args, plan, capacity, buffers_epoch, ex_gen, ty_gen, update, skin); }
   bool operator==(const GraphKey& o) const { return tie() == o.tie(); }
 };
 
@@ -215,10 +216,21 @@ struct nl_handle_s {
   int64_t ex_unique = 0;           // distinct unordered pairs
   uint64_t ex_gen = 0;             // bumped by a set, a clear or a relabel (part of the graph key)
   int64_t ex_off_cap = 0, ex_ids_cap = 0;  // entries the table's two buffers hold (a table that fits is written in place)
-  bool ex_relabel = false;         // a build ran since the last nl_resort: the next one relabels the table, if any
-  void* kp_pre = nullptr;          // with a table: the offsets and the list the search writes, before the stage
+  bool ex_relabel = false;         // a build ran since the last nl_resort: the next one relabels the tables, if any
+  void* kp_pre = nullptr;          // with a table (either): the offsets and the list the search writes, before the stage
   int32_t* list_pre = nullptr;     // (one offset array and one list capacity, allocated only while a table is set)
   int64_t pre_capacity = -1, pre_rows = -1;
+
+  // nl_set_type_cutoffs (nl_types.inc): the cut-off of a pair from the types of its particles, in the same stage
+  int32_t* ty_types = nullptr;     // [ty_n] types in input order (nullptr: no table)
+  void* ty_rc2 = nullptr;          // [NL_MAX_TYPES][NL_MAX_TYPES] thresholds in the position type
+  int32_t ty_n = 0, ty_ntypes = 0;
+  int64_t ty_cap = 0;              // entries ty_types holds (a table that fits is written in place)
+  double ty_rc[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // the caller's rc_ab, [ty_ntypes][ty_ntypes]
+  uint64_t ty_gen = 0;             // bumped by a set, a clear or a relabel (part of the graph key)
+  void* lj_par = nullptr;          // nl_set_lj_type_params: [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2 in T
+  int32_t lj_ntypes = 0;
+  double lj_rcf[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // rc_force_ab, [lj_ntypes][lj_ntypes]
 };
 
 namespace {
@@ -243,13 +255,19 @@ int excl_reserve(nl_handle_t h);
 bool excl_ready(nl_handle_t h);
 int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s);
 int excl_relabel(nl_handle_t h);
+void filter_release(nl_handle_t h);
+// nl_types.inc
+int launch_filter(nl_handle_t h, int32_t n_rows, hipStream_t s);
+int types_relabel(nl_handle_t h);
 
-// Where the search kernels write the offsets and the list: the getters' buffers, or with an exclusion table the
-// pre-exclusion ones that the stage compacts from.
-void* search_kp(nl_handle_t h) { return h->plan.excl ? h->kp_pre : h->key_pointer; }
-int32_t* search_list(nl_handle_t h) { return h->plan.excl ? h->list_pre : h->list; }
+// A table that filters builds is set (exclusions, types or both): builds run the filter stage.
+bool filter_tables(nl_handle_t h) { return h->ex_ids || h->ty_types; }
+// Where the search kernels write the offsets and the list: the getters' buffers, or with a filter table the unfiltered
+// ones that the stage compacts from.
+void* search_kp(nl_handle_t h) { return h->plan.filter ? h->kp_pre : h->key_pointer; }
+int32_t* search_list(nl_handle_t h) { return h->plan.filter ? h->list_pre : h->list; }
 // Entries of the last build's list (after the stage, if it ran); growth keeps using the unfiltered total.
-int64_t list_total(nl_handle_t h) { return h->plan.excl ? h->host->kept() : h->host->total(); }
+int64_t list_total(nl_handle_t h) { return h->plan.filter ? h->host->kept() : h->host->total(); }
 
 template <typename P> int dev_alloc(nl_handle_t h, P** p, size_t bytes) {
   h->buffers_epoch++;  // a captured graph holds the old pointers
@@ -545,7 +563,7 @@ template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, in
   BuildPlan p;
   p.full = h->list_kind == NL_LIST_FULL;
   p.pbc = h->pbc;
-  p.excl = h->ex_ids != nullptr;
+  p.filter = filter_tables(h);
   // 64-bit list offsets as soon as the list this handle can hold exceeds what an int32 key_pointer can address
   // (the reference's own limit, neighlist_cpu.hpp:15,29); nl_set_offset_width overrides.
   p.wide = h->offset_width == 64 || (h->offset_width == 0 && h->capacity > 2147483647LL);
@@ -651,8 +669,9 @@ void launch_bin_cells(nl_handle_t h, const Grid<T>& g, int32_t grid, int32_t nro
 template <typename T>
 int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStream_t s, hipEvent_t* ev, int part = PART_ALL) {
   adopt_build(h, a, p);
-  if (p.excl && (a.n != h->ex_n || a.slab || a.gid || a.dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
-  if (p.excl && !excl_ready(h)) return fail(h, NL_ERR_NOMEM);  // (the search would write through a missing buffer)
+  if (p.filter && ((h->ex_ids && a.n != h->ex_n) || (h->ty_types && a.n != h->ty_n) || a.slab || a.gid || a.dyn))
+    return fail(h, NL_ERR_STATE);  // (checked by the entry points)
+  if (p.filter && !excl_ready(h)) return fail(h, NL_ERR_NOMEM);  // (the search would write through a missing buffer)
   if (part != PART_ALL && !p.split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
     if (part == PART_BEGIN) return NL_OK;
     part = PART_ALL;
@@ -743,16 +762,16 @@ int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStre
   }
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_FILL], s));
   launch_sweep<T>(h, MODE_FILL, s);
-  // the exclusion table: the unfiltered list compacted into the getters' buffers (counted in the FILL stage)
-  if (p.excl)
-    if (int rc = launch_exclude(h, a.n_rows, s)) return rc;
+  // the filter tables: the unfiltered list compacted into the getters' buffers (counted in the FILL stage)
+  if (p.filter)
+    if (int rc = launch_filter(h, a.n_rows, s)) return rc;
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_TOTAL], s));
   HIPCHK(h, hipGetLastError());
   return NL_OK;
 }
 
 int enqueue_result_copy(nl_handle_t h, hipStream_t s) {
-  const int words = h->plan.excl ? META_WORDS_EXCL : META_WORDS;
+  const int words = h->plan.filter ? META_WORDS_EXCL : META_WORDS;
   HIPCHK(h, hipMemcpyAsync(h->host, h->status, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s));
   return NL_OK;
 }
@@ -836,7 +855,7 @@ int finish(nl_handle_t h, bool may_grow) {
       launch_sweep<float>(h, MODE_FILL, h->last_stream);
     else
       launch_sweep<double>(h, MODE_FILL, h->last_stream);
-    if (h->plan.excl) rc = launch_exclude(h, h->n_rows, h->last_stream);  // (the refilled list is the unfiltered one)
+    if (h->plan.filter) rc = launch_filter(h, h->n_rows, h->last_stream);  // (the refilled list is the unfiltered one)
     if (!rc) rc = enqueue_result_copy(h, h->last_stream);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
@@ -1083,7 +1102,7 @@ int nl_destroy(nl_handle_t h) {
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
   void* bufs[] = {h->snap, h->skin_words, h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
                   h->cell_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor,
-                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre};
+                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre, h->ty_types, h->ty_rc2, h->lj_par};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (h->host) (void)hipHostFree(h->host);
@@ -1256,11 +1275,11 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
   } else if (mz - owned < 2) {
     return fail(h, NL_ERR_ARG);  // the two ghost layers would be the same layer
   }
-  // an exclusion table applies to whole single-device builds of its own particle count
-  if (h->ex_ids && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
-  if (h->ex_ids && n != h->ex_n) return fail(h, NL_ERR_ARG);
+  // an exclusion or type table applies to whole single-device builds of its own particle count
+  if (filter_tables(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->ex_ids)  // (again, if an allocation failed since the table was set)
+  if (filter_tables(h))  // (again, if an allocation failed since the table was set)
     if (int rc = excl_reserve(h)) return rc;
   if (h->pending) {
     // back-to-back asynchronous builds (the reference's timing loop): errors of the previous one are dropped,
@@ -1286,7 +1305,7 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
   }
   if (h->use_graph && part == PART_ALL) {
     adopt_build(h, a, p);  // (on replay: the captured build's arguments and plan, whatever ran in between)
-    rc = graph_launch(h, GraphKey{a, p, h->capacity, h->buffers_epoch, h->ex_gen}, s, [&](hipStream_t cs) {
+    rc = graph_launch(h, GraphKey{a, p, h->capacity, h->buffers_epoch, h->ex_gen, h->ty_gen}, s, [&](hipStream_t cs) {
       const int rc = dispatch_build(h, a, p, cs, nullptr);
       return rc ? rc : enqueue_result_copy(h, cs);
     });
@@ -1400,9 +1419,11 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream) {
   HIPCHK(h, hipSetDevice(h->device));
   const int32_t n = h->n;
   if (n == 0) return NL_OK;
-  if (h->ex_relabel) {  // the first re-sort after a build: the table follows the particles, once
+  if (h->ex_relabel) {  // the first re-sort after a build: the tables follow the particles, once
     if (h->ex_ids && h->ex_n == n)
       if ((rc = excl_relabel(h))) return rc;
+    if (h->ty_types && h->ty_n == n)
+      if ((rc = types_relabel(h))) return rc;
     h->ex_relabel = false;
   }
   if (!h->resort_buf) {
@@ -1617,3 +1638,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_consumer.inc"
 #include "nl_dist.inc"
 #include "nl_exclude.inc"
+#include "nl_types.inc"

@@ -115,8 +115,9 @@ int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s) {
 }
 
 // The pre-exclusion offsets and list while a table is set (one offset array, one list capacity); nothing without one.
+// (Shared with the type table of nl_types.inc: either table filters builds through these buffers.)
 int excl_reserve(nl_handle_t h) {
-  if (!h->ex_ids) return NL_OK;
+  if (!filter_tables(h)) return NL_OK;
   if (h->pre_rows < (int64_t)h->n_max) {
     h->pre_rows = -1;
     if (int rc = dev_alloc(h, &h->kp_pre, 8 * ((size_t)h->n_max + 32))) return rc;
@@ -299,13 +300,19 @@ int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool 
   return rc;
 }
 
-void excl_clear(nl_handle_t h) {
-  void* bufs[] = {h->ex_off, h->ex_ids, h->kp_pre, h->list_pre};
-  for (void* b : bufs)
+// (declared at the top of nl_api.hip) The unfiltered buffers, once no table needs them.
+void filter_release(nl_handle_t h) {
+  for (void* b : {h->kp_pre, (void*)h->list_pre})
     if (b) (void)hipFree(b);
-  h->ex_off = h->ex_ids = nullptr;
   h->kp_pre = nullptr, h->list_pre = nullptr;
   h->pre_capacity = h->pre_rows = -1;
+}
+
+void excl_clear(nl_handle_t h) {
+  for (void* b : {h->ex_off, h->ex_ids})
+    if (b) (void)hipFree(b);
+  h->ex_off = h->ex_ids = nullptr;
+  if (!h->ty_types) filter_release(h);
   h->ex_n = 0, h->ex_unique = 0;
   h->ex_off_cap = h->ex_ids_cap = 0;
   h->ex_gen++;

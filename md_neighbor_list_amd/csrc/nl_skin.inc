@@ -135,13 +135,13 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
   if (!h) return NL_ERR_ARG;
   if (h->n_max <= 0 && n > 0) return fail(h, NL_ERR_STATE);
   if (n < 0 || n > h->n_max || (q_stride != 3 && q_stride != 4) || (!q_dev && n > 0)) return fail(h, NL_ERR_ARG);
-  if (h->ex_ids && n != h->ex_n) return fail(h, NL_ERR_ARG);  // (nl_set_exclusions)
+  if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);  // (nl_set_exclusions, nl_set_type_cutoffs)
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIPCHK(h, hipStreamIsCapturing(s, &cap));
   const bool capturing = cap != hipStreamCaptureStatusNone;
-  if (h->ex_ids && !capturing)  // (again, if an allocation failed since the table was set)
+  if (filter_tables(h) && !capturing)  // (again, if an allocation failed since the table was set)
     if (int rc = excl_reserve(h)) return rc;
   // (a): what forces a build before any particle is looked at -- no list of an update to keep (a setter, nl_resort or
   // another kind of build since, the host has seen the last build fail), or other positions
@@ -174,7 +174,7 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
     // the same graph as nl_make_list's (one per argument set), keyed also on the update and its skin; a forced update
     // runs as plain launches and the next one captures
     adopt_build(h, a, p);
-    const GraphKey key{a, p, h->capacity, h->buffers_epoch, h->ex_gen, 1, h->skin};
+    const GraphKey key{a, p, h->capacity, h->buffers_epoch, h->ex_gen, h->ty_gen, 1, h->skin};
     if (int rc = graph_launch(h, key, s, [&](hipStream_t cs) { return dispatch_update(h, a, p, false, cs); })) return rc;
   } else {
     if (int rc = dispatch_update(h, a, p, force, s)) return rc;

@@ -203,6 +203,68 @@ class NeighListGPU:
         return (_as_tensor(off.value, (n.value + 1,), "<i4", self, self.device),
                 _as_tensor(ids.value, (2 * nu.value,), "<i4", self, self.device))
 
+    # ------------------------------------------------------------------ per-type cut-offs
+    def set_type_cutoffs(self, types, rc_matrix):
+        """Cut-offs per pair of particle types (nl_set_type_cutoffs): ``types`` an ``(n,)`` int32/int64 tensor or array in
+        input order, ``rc_matrix`` an ``(ntypes, ntypes)`` symmetric matrix with entries in [0, search_length] (skin
+        included).  Every later build keeps an entry only within the cut-off of its two types."""
+        import numpy as np
+
+        rc = np.ascontiguousarray(np.asarray(rc_matrix, dtype=np.float64))
+        if rc.ndim != 2 or rc.shape[0] != rc.shape[1]:
+            raise TypeError("rc_matrix must be a square (ntypes, ntypes) matrix")
+        t = types if isinstance(types, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(types)))
+        if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
+            raise TypeError("types must be an (n,) int32 or int64 tensor or array")
+        if t.dtype == torch.int64 and t.numel() and (int(t.min()) < -2**31 or int(t.max()) >= 2**31):
+            raise ValueError("types hold a value outside the int32 range")
+        t = t.to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(t.shape[0])
+        ptr = t.data_ptr() if n else None
+        if n == 0:  # (an empty table still needs a non-NULL pointer: NULL clears)
+            t = torch.zeros(1, dtype=torch.int32, device=self.device)
+            ptr = t.data_ptr()
+        check(self._lib.nl_set_type_cutoffs(self._h, ptr, n, int(rc.shape[0]), rc.ctypes.data_as(C.POINTER(C.c_double))),
+              "nl_set_type_cutoffs")
+
+    def clear_type_cutoffs(self):
+        """Drops the type table: later builds use the one cut-off again."""
+        check(self._lib.nl_set_type_cutoffs(self._h, None, 0, 0, None), "nl_set_type_cutoffs")
+
+    def types(self):
+        """The handle's copy of the types (nl_get_types), relabelled by resort(); a view, valid until the table is set
+        or cleared."""
+        ptr, n, nt = C.c_void_p(), C.c_int32(), C.c_int32()
+        check(self._lib.nl_get_types(self._h, C.byref(ptr), C.byref(n), C.byref(nt)), "nl_get_types")
+        return _as_tensor(ptr.value, (n.value,), "<i4", self, self.device)
+
+    def set_lj_type_params(self, epsilon, sigma, rc_force):
+        """Lennard-Jones parameters per pair of types for lj_forces_typed (nl_set_lj_type_params): three symmetric
+        ``(ntypes, ntypes)`` matrices, rc_force within the type table's cut-offs."""
+        import numpy as np
+
+        mats = [np.ascontiguousarray(np.asarray(m, dtype=np.float64)) for m in (epsilon, sigma, rc_force)]
+        nt = mats[0].shape[0] if mats[0].ndim == 2 else -1
+        if any(m.shape != (nt, nt) for m in mats):
+            raise TypeError("epsilon, sigma and rc_force must be (ntypes, ntypes) matrices")
+        ptrs = [m.ctypes.data_as(C.POINTER(C.c_double)) for m in mats]
+        check(self._lib.nl_set_lj_type_params(self._h, int(nt), *ptrs), "nl_set_lj_type_params")
+
+    def lj_forces_typed(self, q, wait=True, out=None):
+        """lj_forces with the parameters of set_lj_type_params, per pair of types (nl_lj_forces_typed); ``wait=False``:
+        nl_lj_forces_typed_enqueue (rc_force within cut-off - skin).  Returns ``(n, 4) = {fx, fy, fz, pe_i}``."""
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        f = torch.empty((n, 4), dtype=self.dtype, device=self.device) if out is None else out
+        if f.shape != (n, 4) or f.dtype != self.dtype or not f.is_contiguous():
+            raise TypeError("out must be a contiguous (n, 4) tensor of the list's dtype")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        fn = self._lib.nl_lj_forces_typed if wait else self._lib.nl_lj_forces_typed_enqueue
+        check(fn(self._h, q.data_ptr(), q.shape[1], f.data_ptr(), stream),
+              "nl_lj_forces_typed" if wait else "nl_lj_forces_typed_enqueue")
+        return f
+
     GID_IN_W = "w"  # MakeNeighListSlab(gid=GID_IN_W): ids are stored in q[:, 3] as integer bit patterns (NL_GID_IN_W)
 
     def MakeNeighListSlab(self, q, gid, n_rows, z_lo, z_hi, sync=True):
