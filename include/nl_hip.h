@@ -421,7 +421,8 @@ int nl_debug_occupancy(int32_t out[8]); /* LDS per CU/block (KiB), occupancy API
  * dense build: one per LDS batch of the stencil stream), info[6] = 0, or 1 + c when the build took the fine-row search
  * (nl_rows.hpp; c = its LDS configuration 0..2) -- the table nl_get_sorted returns is then the fine-row table,
  * info[7] = 1 when the build used the small instances of the COUNT sweep and the expansion (sparse boxes: 2 waves /
- * 1 wave per cell, half the LDS buffer), else 0. */
+ * 1 wave per cell, half the LDS buffer), else 0; bits 8.. of info[7] = C when the build took the id-class search
+ * (k_sweep_class_f32: C = 2 or 4 classes of ids; NL_IDCLASS), else 0. */
 int nl_get_build_info(nl_handle_t h, int32_t info[8]);
 /* How the builds of this handle ran: stats[0] = builds run again because a row of x-cells overflowed its bucket in the
  * one-pass binning, stats[1] = builds run again because cells whose stencil exceeds the LDS buffer were there while the

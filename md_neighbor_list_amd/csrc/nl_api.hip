@@ -83,7 +83,9 @@ struct BuildPlan {
   bool wide = false;    // key_pointer / base_sorted hold int64 (the list may exceed INT32_MAX entries)
   bool filter = false;  // the filter stage runs: an exclusion table (nl_exclude.inc), a type table (nl_types.inc) or both
   int32_t pbc = 0;      // axes of the minimum image (nl_set_periodic_axes)
-  auto tie() const { return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, pbc); }
+  int32_t idc = 0;      // SEARCH_MASKS with id classes (k_sweep_class_f32, k_fill_masks<IDC>): C = 2 or 4 classes, 0 = off
+  int32_t id_shift = 0; // class of an id: id >> id_shift
+  auto tie() const { return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, pbc, idc, id_shift); }
   bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
 };
 
@@ -162,6 +164,8 @@ struct nl_handle_s {
   int dbg_flags = 0;  // diagnostics (NL_DEBUG_FLAGS)
   int32_t* cell_count = nullptr;  // [ncell] followed by the status word
   int32_t* cell_start = nullptr;  // [ncell + 1]
+  int32_t* cls_start = nullptr;   // id-class builds: [C ncell + 1] first slot of every (cell, class) (k_bin_cells<IDC>)
+  int idclass_env = 2;            // NL_IDCLASS: classes of the id-class search where a build qualifies (2 or 4), 0 = never
   uint64_t* scan_look = nullptr;  // k_scan_chained: [scan_blocks] entries + the two counters; all zero between launches
   int32_t scan_blocks = 0;
   int64_t* totals = nullptr;  // [0] = particles (cell scan), [1] = pairs (row scan)
@@ -350,6 +354,7 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.sorted_row = h->sorted_row;
   a.sorted_gid = h->sorted_gid;
   a.cell_start = h->cell_start;
+  a.cls_start = h->cls_start;
   a.mx = h->m[0], a.my = h->m[1], a.mzl = h->args.mzl, a.slab = h->args.slab;
   a.div_mx = fastdiv_make((uint32_t)h->m[0]), a.div_my = fastdiv_make((uint32_t)h->m[1]);
   a.rc2 = sizeof(T) == 4 ? (T)h->rc2_f : (T)h->rc2;
@@ -443,6 +448,8 @@ template <typename T, bool FULL, bool PBC, typename OFF> void launch_search(nl_h
         if constexpr (F32_OPEN) {
           // a workgroup per cell, single-batch cells only; the others go on the hand-over list of the batched search
           if (p.small) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, 2, LEAN_SMALL_CAP>), cells, dim3(2 * WAVE), 0, s, a);
+          else if (!FULL && p.idc == 2) hipLaunchKernelGGL((k_sweep_class_f32<2>), cells, wg, 0, s, a);
+          else if (!FULL && p.idc == 4) hipLaunchKernelGGL((k_sweep_class_f32<4>), cells, wg, 0, s, a);
           else hipLaunchKernelGGL((k_sweep_lean_f32<FULL>), cells, wg, 0, s, a);
           if (p.list) hipLaunchKernelGGL((k_sweep_list_f32<FULL>), list_grid, wg, 0, s, a);
         } else {
@@ -453,6 +460,14 @@ template <typename T, bool FULL, bool PBC, typename OFF> void launch_search(nl_h
       if (p.small) {  // sparse boxes: a wave per cell (its ~19 rows in one batch), ids of half a stream
         if constexpr (F32_OPEN)
           hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 24, 1, SweepCfg<T>::CAP / 2>), cells, dim3(WAVE), 0, s, a);
+      } else if (F32_OPEN && !FULL && p.idc) {
+        if constexpr (F32_OPEN && !FULL) {
+          constexpr int CAP = SweepCfg<T>::CAP;
+          if (p.rows12 && p.idc == 2) hipLaunchKernelGGL((k_fill_masks<T, false, false, OFF, 12, EXPAND_WAVES, CAP, 2>), cells, dim3(EXPAND_WAVES * WAVE), 0, s, a);
+          else if (p.rows12) hipLaunchKernelGGL((k_fill_masks<T, false, false, OFF, 12, EXPAND_WAVES, CAP, 4>), cells, dim3(EXPAND_WAVES * WAVE), 0, s, a);
+          else if (p.idc == 2) hipLaunchKernelGGL((k_fill_masks<T, false, false, OFF, 24, EXPAND_WAVES, CAP, 2>), cells, dim3(EXPAND_WAVES * WAVE), 0, s, a);
+          else hipLaunchKernelGGL((k_fill_masks<T, false, false, OFF, 24, EXPAND_WAVES, CAP, 4>), cells, dim3(EXPAND_WAVES * WAVE), 0, s, a);
+        }
       } else if (p.rows12) {
         hipLaunchKernelGGL((k_fill_masks<T, FULL, PBC, OFF, 12>), cells, dim3(EXPAND_WAVES * WAVE), 0, s, a);
       } else {
@@ -624,6 +639,16 @@ template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, in
   p.list = !again_ok || h->list_quiet < LIST_QUIET_BUILDS;
   p.cap_row = again_ok ? bucket_cap<T>(h, n, a.mzl) : 0;
   p.binning = !two_level ? BINNING_ATOMIC : p.cap_row > 0 ? BINNING_BUCKET : BINNING_TWO_PASS;
+  // id classes (NL_IDCLASS; k_sweep_class_f32): where they are exact and simple -- the fp32 half list of the one-batch
+  // 4-wave path in an open box, ids 0..n-1 (no caller ids), a whole build (no slab, no distributed build), the
+  // row-wise binning that writes the class table (k_bin_cells), and a mesh of at least 3 cells a side (27 distinct
+  // stencil cells)
+  if (sizeof(T) == 4 && p.search == SEARCH_MASKS && !p.small && !p.full && p.pbc == 0 && h->idclass_env > 0 && !a.gid &&
+      !a.slab && !a.dyn && !p.split && p.binning != BINNING_ATOMIC && h->m[0] * h->idclass_env <= 4 * BIN_FINE_MAX_MX &&
+      h->m[0] >= 3 && h->m[1] >= 3 && a.mzl >= 3 && n > 0) {
+    p.idc = h->idclass_env;
+    while (((uint32_t)(n - 1) >> p.id_shift) >= (uint32_t)p.idc) p.id_shift++;  // classes [k 2^s, (k + 1) 2^s) cover [0, n)
+  }
   return p;
 }
 
@@ -653,15 +678,17 @@ template <typename T, bool BUCKET, typename L> void launch_unrolled(nl_handle_t 
 template <typename T>
 void launch_bin_cells(nl_handle_t h, const Grid<T>& g, int32_t grid, int32_t nrows, const int32_t* row_start, const BinPhase& ph,
                       int32_t cap_row, hipStream_t s) {
-  auto launch = [&](auto fine) {
-    hipLaunchKernelGGL((k_bin_cells<T, decltype(fine)::value>), dim3(grid), dim3(256), 0, s, g, nrows, row_start,
+  auto launch = [&](auto fine, auto idc) {
+    hipLaunchKernelGGL((k_bin_cells<T, decltype(fine)::value, decltype(idc)::value>), dim3(grid), dim3(256), 0, s, g, nrows, row_start,
                        static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
-                       h->sorted_row, h->sorted_gid, ph, cap_row);
+                       h->sorted_row, h->sorted_gid, ph, cap_row, h->cls_start, h->plan.id_shift);
   };
   if constexpr (sizeof(T) == 4) {
-    if (h->plan.search == SEARCH_ROWS) return launch(std::true_type());
+    if (h->plan.search == SEARCH_ROWS) return launch(std::true_type(), std::integral_constant<int, 0>());
+    if (h->plan.idc == 2) return launch(std::false_type(), std::integral_constant<int, 2>());
+    if (h->plan.idc == 4) return launch(std::false_type(), std::integral_constant<int, 4>());
   }
-  launch(std::false_type());
+  launch(std::false_type(), std::integral_constant<int, 0>());
 }
 
 // Enqueues build a along plan p (made by plan_build for these arguments), which becomes the handle's build.
@@ -1086,6 +1113,7 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
     if (const char* v = getenv("NL_SWEEP_VARIANT")) h->sweep_variant = atoi(v) <= 1 ? 1 : 3;
     if (const char* v = getenv("NL_ROWS")) h->rows_env = std::max(-1, std::min(atoi(v), 4));
+    if (const char* v = getenv("NL_IDCLASS")) h->idclass_env = atoi(v) >= 4 ? 4 : atoi(v) >= 2 ? 2 : 0;
     if (const char* v = getenv("NL_OFFSET_WIDTH")) h->offset_width = atoi(v) == 64 ? 64 : atoi(v) == 32 ? 32 : 0;
     if (const char* v = getenv("NL_BINNING")) h->bin_two_level = atoi(v) != 1;
     if (const char* v = getenv("NL_BIN_BUCKETS")) h->bucket_env = atoi(v) != 0;
@@ -1101,7 +1129,7 @@ int nl_destroy(nl_handle_t h) {
   (void)hipSetDevice(h->device);
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
   void* bufs[] = {h->snap, h->skin_words, h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
-                  h->cell_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor,
+                  h->cell_start, h->cls_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor,
                   h->ex_off, h->ex_ids, h->kp_pre, h->list_pre, h->ty_types, h->ty_rc2, h->lj_par};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1169,6 +1197,7 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   if ((rc = dev_alloc(h, &h->cell_count, 4 * ((size_t)h->ncell + 64 + 2 * (size_t)h->m[1] * h->m[2])))) return rc;
   h->row_count = h->cell_count + h->ncell + 32;
   if ((rc = dev_alloc(h, &h->cell_start, 4 * (4 * (size_t)h->ncell + 32)))) return rc;  // (cell_start, or the fine-row table: 4 M + 1)
+  if ((rc = dev_alloc(h, &h->cls_start, 4 * (4 * (size_t)h->ncell + 32)))) return rc;   // (the class table: up to 4 M + 1)
   const size_t nblk = std::max<size_t>(n, (size_t)h->ncell) / SCAN_BLOCK + 2;
   if ((rc = dev_alloc(h, &h->scan_look, 8 * (nblk + 1)))) return rc;
   HIPCHK(h, hipMemset(h->scan_look, 0, 8 * (nblk + 1)));
@@ -1524,7 +1553,7 @@ int nl_get_build_info(nl_handle_t h, int32_t info[8]) {
   info[4] = p.wide ? 64 : 32;
   info[5] = p.mask_nb;
   info[6] = p.search == SEARCH_ROWS ? 1 + p.rows_v : 0;  // fine-row search: the cell table of nl_get_sorted is the fine-row table
-  info[7] = p.small ? 1 : 0;
+  info[7] = (p.small ? 1 : 0) | p.idc << 8;  // (bits 8..: classes of an id-class build)
   info[0] = p.search != SEARCH_SWEEPS ? 1 : 0;
   info[1] = h->sweep_variant;
   info[2] = h->dtype == NL_F32 ? SweepCfg<float>::CAP : SweepCfg<double>::CAP;

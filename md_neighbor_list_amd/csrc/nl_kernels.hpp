@@ -750,20 +750,29 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
 // comes from the fraction of the same rounded product t = z * ims the reference truncates for the cell index
 // (neighlist_cpu.hpp:51-59): floor(4 (t - trunc(t))) -- a negative fraction (a particle just below the box: the
 // reference's truncation files t = -0.3 into cell 0) counts as quarter 0.
+//
+// IDC > 0 (id classes, nl_lean.hpp k_sweep_class_f32): the particles of a CELL are sorted by their id class
+// gid >> id_shift (C = IDC contiguous id ranges covering [0, n)), so the row is ordered by (x-cell, class).  Every cell
+// stays one run of the sorted array (cell_start keeps its meaning for every reader), and the class table
+// cls_start[(r * mx + cx) * IDC + class] (IDC M + 1 entries) gives where each class of the cell begins: entry e + 1 is
+// where the run of entry e ends.
 constexpr int BIN_FINE_MAX_MX = 2048;
-template <typename T, bool FINE = false>
+template <typename T, bool FINE = false, int IDC = 0>
 __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, const int32_t* __restrict__ row_start,
                                                    const Pos<T>* __restrict__ tmp, const int32_t* __restrict__ tmp_row,
                                                    int32_t* __restrict__ cell_start, Pos<T>* __restrict__ sorted,
                                                    int32_t* __restrict__ sorted_row, int32_t* __restrict__ sorted_gid,
-                                                   BinPhase ph, int32_t cap_row = 0) {
+                                                   BinPhase ph, int32_t cap_row = 0, int32_t* __restrict__ cls_start = nullptr,
+                                                   int32_t id_shift = 0) {
+  static_assert(!(FINE && IDC), "one sub-key at a time");
+  static_assert(IDC == 0 || IDC == 2 || IDC == 4, "id classes: 2 or 4");
   if (gate_closed(g.gate)) return;  // (nl_update_list: no build this time)
-  __shared__ int32_t cnt[FINE ? 4 * BIN_FINE_MAX_MX : BIN_MAX_MX];
+  __shared__ int32_t cnt[FINE || IDC ? 4 * BIN_FINE_MAX_MX : BIN_MAX_MX];
   __shared__ int32_t wsum[4];
   __shared__ int32_t carry_s;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int32_t bx = blockIdx.x, mx = g.m[0];
-  const int32_t nb = FINE ? 4 * mx : mx;  // bins of the row
+  const int32_t nb = FINE ? 4 * mx : IDC ? IDC * mx : mx;  // bins of the row
   const int32_t r = bx < ph.cells_n0 ? ph.cells_row0 + bx : ph.cells_row1 + (bx - ph.cells_n0);
   const int32_t beg = row_start[r], end = row_start[r + 1];
   // cap_row > 0 (k_bin_bucket): the row's particles are at the front of its bucket, tmp[r * cap_row ...]
@@ -789,6 +798,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
   auto bin_of = [&](const Pos<T>& p) {
     const int32_t c = xcell1(p.x);
     if constexpr (FINE) return quarter(p.z, g.ims[2]) * mx + c;
+    else if constexpr (IDC > 0) return c * IDC + min((int32_t)((uint32_t)p.gid >> id_shift), IDC - 1);
     else return c;
   };
   // The row's particles stay in registers between the histogram and the placement (rows of up to BC_KEEP * 256: one
@@ -830,14 +840,23 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
     if (c < nb) {
       cnt[c] = excl;
       // (FINE: bin c = quarter * mx + x-cell is filed at (r * mx + x-cell) * 4 + quarter: rows_fine_index)
-      if constexpr (FINE) cell_start[((size_t)r * mx + (c % mx)) * 4 + c / mx] = beg + excl;
-      else cell_start[(size_t)r * nb + c] = beg + excl;
+      if constexpr (FINE) {
+        cell_start[((size_t)r * mx + (c % mx)) * 4 + c / mx] = beg + excl;
+      } else if constexpr (IDC > 0) {
+        cls_start[(size_t)r * nb + c] = beg + excl;
+        if (c % IDC == 0) cell_start[(size_t)r * mx + c / IDC] = beg + excl;
+      } else {
+        cell_start[(size_t)r * nb + c] = beg + excl;
+      }
     }
     __syncthreads();
     if (tid == 255) carry_s = carry + woff + inc;
     __syncthreads();
   }
-  if (r == nrows - 1 && tid == 0) cell_start[(size_t)nrows * nb] = end;
+  if (r == nrows - 1 && tid == 0) {
+    if constexpr (IDC > 0) cls_start[(size_t)nrows * nb] = end, cell_start[(size_t)nrows * mx] = end;
+    else cell_start[(size_t)nrows * nb] = end;
+  }
   auto place = [&](Pos<T> p, int32_t row_of) {
     const int32_t dst = beg + atomicAdd(&cnt[bin_of(p)], 1);
     if (g.pbc & 1) {  // periodic x: a wrapped x index means the particle is stored at its image
@@ -890,6 +909,7 @@ template <typename T> struct SweepArgs {
   const int32_t* __restrict__ sorted_row;
   const int32_t* __restrict__ sorted_gid;  // sorted[k].gid, compact (k_fill_masks reads ids only: 4 x fewer cache lines)
   const int32_t* __restrict__ cell_start;
+  const int32_t* __restrict__ cls_start;  // id-class builds: [cell * C + class] first slot of the class (k_bin_cells<IDC>)
   int32_t mx, my, mzl, slab;
   FastDiv div_mx, div_my;         // i-cell index -> (cx, cy, cz) without integer division
   T rc2;                          // largest T value <= rc*rc in double, so !(r2 > rc2) == !((double)r2 > rc2_double)
@@ -1736,6 +1756,99 @@ __device__ __forceinline__ int32_t scan64_dpp(int32_t v) {  // inclusive scan ov
   return v;
 }
 
+// ---- id classes (fp32 half list, open box, ids 0..n-1: k_sweep_class_f32 in nl_lean.hpp and k_fill_masks<IDC>).  The
+// ids fall into C contiguous classes, class = id >> id_shift, and every cell's particles are sorted by class
+// (k_bin_cells<IDC>).  The stencil stream of a cell is staged CLASS-MAJOR: the class-0 runs of the 27 cells, then the
+// class-1 runs, ... -- 27 C windows, one per lane of NT table registers -- so class k occupies the stream from cstart(k)
+// = offset of window 27 k to cstart(k + 1).  An i-particle of class k has no partner of higher id in front of
+// cstart(k), and every slot from cstart(k + 1) on has a higher id: its group walks the stream from tile cstart(k) / 64
+// on, with the id test only in the tiles that hold a slot below cstart(k + 1).  Bit t of lane l of its hit word stands
+// for stream slot 64 (cstart(k) / 64 + t) + l.  Window 27 k + 13 is the i-cell's own class-k run.
+constexpr int CLS_OWN = 13;  // (dz, dy, dx) = (0, 0, 0): window 9 (dz + 1) + 3 (dy + 1) + dx + 1 of a class
+template <int IDC> struct ClsCtx {
+  static constexpr int NWIN = 27 * IDC, NT = (NWIN + WAVE - 1) / WAVE;
+  int32_t ibeg, ni, total_j;  // the cell's particles [ibeg, ibeg + ni) (all classes), its stream length
+  int32_t cx, cy, cz;
+  int32_t src[NT], len[NT], off[NT];  // per lane and register j: window 64 j + lane (start in the sorted array, length, offset in the stream)
+  // entry w (wave-uniform) of a table
+  __device__ __forceinline__ int32_t get(const int32_t (&v)[NT], int32_t w) const {
+    if constexpr (NT == 1) return __builtin_amdgcn_readlane(v[0], w);
+    else return w < WAVE ? __builtin_amdgcn_readlane(v[0], w) : __builtin_amdgcn_readlane(v[1], w - WAVE);
+  }
+};
+
+// The class-window table of the i-cell (cx, cy, cz), whole open box (the stencil wraps as segment_cells does; the plan
+// takes this path only for meshes of at least 3 cells a side, where the 27 cells are distinct).  Returns false for an
+// empty cell.
+template <int IDC>
+__device__ __forceinline__ bool cls_setup_at(const SweepArgs<float>& a, int lane, int32_t cx, int32_t cy, int32_t cz, ClsCtx<IDC>& c) {
+  typedef ClsCtx<IDC> X;
+  const int32_t cell = cx + (cy + cz * a.my) * a.mx;
+  const uint32_t st_word = *a.status;  // (see cell_setup_at)
+  c.ibeg = a.cell_start[cell];
+  c.ni = a.cell_start[cell + 1] - c.ibeg;
+  c.cx = cx, c.cy = cy, c.cz = cz;
+#pragma unroll
+  for (int j = 0; j < X::NT; j++) {
+    const int32_t w = j * WAVE + lane;
+    int32_t src = 0, len = 0;
+    if (w < X::NWIN) {
+      const int32_t k = w / 27, s = w - 27 * k, r9 = s / 3;
+      int32_t x = cx + (s - 3 * r9) - 1, y = cy + r9 % 3 - 1, z = cz + r9 / 3 - 1;
+      x += x < 0 ? a.mx : x >= a.mx ? -a.mx : 0;
+      y += y < 0 ? a.my : y >= a.my ? -a.my : 0;
+      z += z < 0 ? a.mzl : z >= a.mzl ? -a.mzl : 0;
+      const int32_t e = (x + (y + z * a.my) * a.mx) * IDC + k;
+      src = a.cls_start[e];
+      len = a.cls_start[e + 1] - src;
+    }
+    c.src[j] = src, c.len[j] = len;
+  }
+  if (c.ni <= 0 || (st_word & ST_DOMAIN)) return false;
+  int32_t carry = 0;
+#pragma unroll
+  for (int j = 0; j < X::NT; j++) {
+    const int32_t incl = scan64_dpp(c.len[j]);
+    c.off[j] = carry + incl - c.len[j];
+    carry += __builtin_amdgcn_readlane(incl, 63);
+  }
+  c.total_j = carry;
+  return true;
+}
+template <int IDC> __device__ __forceinline__ bool cls_setup(const SweepArgs<float>& a, int lane, ClsCtx<IDC>& c) {
+  const int32_t w = xcd_cell_index();
+  const int32_t wy = (int32_t)fastdiv((uint32_t)w, a.div_mx), cx = w - wy * a.mx;
+  const int32_t cz = (int32_t)fastdiv((uint32_t)wy, a.div_my), cy = wy - cz * a.my;
+  return cls_setup_at(a, lane, cx, cy, cz, c);
+}
+
+// The class-major stream of the cell into `dst` by LDS-DMA (elements of E: positions or ids).  The three x-cells of a
+// (class, dz, dy) row are three runs in memory (the classes of a cell lie between them) but one piece of the stream:
+// each lane of a DMA instruction takes its element from the run it falls in, so a row goes in one instruction (two
+// for more than 64 particles) -- 9 C pieces, not 27 C windows: the instruction count of the 27-cell staging.  Wave v
+// takes pieces v, v + NW, ...
+template <int IDC, int NW, typename E>
+__device__ __forceinline__ void cls_stage(const E* __restrict__ from, const ClsCtx<IDC>& c, E* dst, int lane, int wave) {
+#pragma unroll 1
+  for (int32_t pc = wave; pc < 9 * IDC; pc += NW) {
+    const int32_t w = 3 * pc;  // windows w, w + 1, w + 2: consecutive in the stream
+    const int32_t s0 = c.get(c.src, w), l0 = c.get(c.len, w), s1 = c.get(c.src, w + 1), l1 = c.get(c.len, w + 1);
+    const int32_t s2 = c.get(c.src, w + 2), l2 = c.get(c.len, w + 2), off = c.get(c.off, w);
+    const int32_t len = l0 + l1 + l2;
+#pragma unroll 1
+    for (int32_t kb = 0; kb < len; kb += WAVE) {
+      const int32_t i = kb + lane;
+      if (i < len) {
+        const int32_t at = i < l0 ? s0 + i : i < l0 + l1 ? s1 + (i - l0) : s2 + (i - l0 - l1);
+        const __attribute__((address_space(1))) void* const gp = (const __attribute__((address_space(1))) void*)(from + at);
+        __attribute__((address_space(3))) void* const lp = (__attribute__((address_space(3))) void*)(dst + off + kb);
+        if constexpr (sizeof(E) == 16) __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+        else __builtin_amdgcn_global_load_lds(gp, lp, 4, 0, 0);
+      }
+    }
+  }
+}
+
 // longest row k_fill_masks assembles in LDS (longer ones are written entry by entry); half list: 5 + 5 KiB of LDS =
 // 16 workgroups per CU
 template <bool FULL> constexpr int EXPAND_RMAX_OF = FULL ? 192 : 160;
@@ -1744,9 +1857,13 @@ constexpr int EXPAND_WAVES = 2;  // waves per workgroup of k_fill_masks: 16 work
 // EW, CAP: 2 waves and room for the ids of a full stream, or (sparse boxes, as k_sweep_lean_f32's small instance) one
 // wave per cell and half of it: half as many cell tables and id stagings, no barrier between waves (cfg 3: build -2.5 %).
 // (One wave per cell with 40 rows up front at cfg 2: 96 VGPRs, 5 waves per SIMD, expansion 0.207 against 0.175 ms.)
-template <typename T, bool FULL = false, bool PBC = false, typename OFF = int32_t, int RB = 24, int EW = EXPAND_WAVES, int CAP = SweepCfg<T>::CAP>
+// IDC > 0: an id-class build (ClsCtx): the ids are staged class-major, and the words of a row of class k count from
+// stream tile cstart(k) / 64 on.
+template <typename T, bool FULL = false, bool PBC = false, typename OFF = int32_t, int RB = 24, int EW = EXPAND_WAVES, int CAP = SweepCfg<T>::CAP,
+          int IDC = 0>
 __global__ void __launch_bounds__(EW* WAVE, (sizeof(OFF) == 8 ? 4 : sizeof(T) == 4 ? (FULL || RB > 12 ? 7 : 8) : 4)) __attribute__((amdgpu_num_sgpr(80)))
 k_fill_masks(SweepArgs<T> a) {
+  static_assert(IDC == 0 || (sizeof(T) == 4 && !FULL && !PBC), "id classes: fp32 half list, open box");
   if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   constexpr int EXPAND_RMAX = EXPAND_RMAX_OF<FULL>;
   // One LDS array (a second __shared__ object next to an LDS-DMA target makes hipcc drain the DMA before every
@@ -1763,8 +1880,10 @@ k_fill_masks(SweepArgs<T> a) {
   };
 #endif
   const int64_t total = a.total[0];  // read together with the cell table: one round trip, not two
-  CellCtx c;
-  const bool ok = cell_setup(a, lane, c);
+  typename std::conditional<(IDC > 0), ClsCtx<IDC ? IDC : 2>, CellCtx>::type c;
+  bool ok;
+  if constexpr (IDC > 0) ok = cls_setup<IDC>(a, lane, c);
+  else ok = cell_setup(a, lane, c);
 #if NL_STAMP_FILL
   fstamp(0);
 #endif
@@ -1830,6 +1949,16 @@ k_fill_masks(SweepArgs<T> a) {
   // LDS-DMA (global_load_lds_dword: lane l's dword lands at the uniform LDS address + 4 l): no VGPRs and no LDS
   // write instructions, and every segment's loads are in flight together.  (Loading and writing segment by segment
   // through registers cost one memory round trip per segment, 9 per wave.)
+  // id classes: rows [cls_row[k], cls_row[k + 1]) of the cell are of class k, their words start at stream slot cls_t0[k]
+  int32_t cls_row[IDC > 0 ? IDC : 1], cls_t0[IDC > 0 ? IDC : 1];
+  if constexpr (IDC > 0) {
+#pragma unroll
+    for (int k = 0; k < IDC; k++) {
+      cls_row[k] = c.get(c.src, 27 * k + CLS_OWN) - c.ibeg;
+      cls_t0[k] = c.get(c.off, 27 * k) & ~(WAVE - 1);
+    }
+    cls_stage<IDC, EW>(a.sorted_gid, c, gids, lane, wave);
+  } else
 #pragma unroll
   for (int s = 0; s < (NSEG + EW - 1) / EW; s++) {
     const int sg = min(wave + s * EW, NSEG - 1);  // wave-uniform
@@ -1860,6 +1989,18 @@ k_fill_masks(SweepArgs<T> a) {
       if (r0 + u0 >= r_end) continue;  // wave-uniform
       uint32_t word[4], ptr[4];
       int32_t nrow[4];
+      const int32_t* gq[4];  // where bit 0 of the row's words points
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        if constexpr (IDC > 0) {
+          int32_t t0 = cls_t0[0];
+#pragma unroll
+          for (int k = 1; k < IDC; k++) t0 = r0 + u0 + q >= cls_row[k] ? cls_t0[k] : t0;
+          gq[q] = g + t0;
+        } else {
+          gq[q] = g;
+        }
+      }
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         word[q] = r0 + u0 + q < r_end ? (w[u0 + q] & 0xFFFFFFu) : 0u;
@@ -1888,7 +2029,7 @@ k_fill_masks(SweepArgs<T> a) {
           for (int q = 0; q < 4; q++) {
             on[q] = word[q] != 0;
             const int32_t t = on[q] ? __ffs(word[q]) - 1 : 0;
-            val[q] = g[t * WAVE];  // unconditional read of a valid slot: the four reads go out back to back
+            val[q] = gq[q][t * WAVE];  // unconditional read of a valid slot: the four reads go out back to back
           }
 #pragma unroll
           for (int q = 0; q < 4; q++) {
@@ -1924,7 +2065,7 @@ k_fill_masks(SweepArgs<T> a) {
         for (int q = 0; q < 4; q++) {
           on[q] = word[q] != 0;
           const int32_t t = on[q] ? __ffs(word[q]) - 1 : 0;
-          val[q] = g[t * WAVE];
+          val[q] = gq[q][t * WAVE];
         }
 #pragma unroll
         for (int q = 0; q < 4; q++) {

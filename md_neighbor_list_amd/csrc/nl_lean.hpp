@@ -129,6 +129,159 @@ __global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80
   pipe_flush<NW == SWEEP_WAVES>(a, pend, lane, hi_plane_used(a.mask_nb, (c.total_j + WAVE - 1) / WAVE));
 }
 
+// ---- id classes (ClsCtx in nl_kernels.hpp; NL_IDCLASS).  One group of GC i-particles of class k against the
+// class-major stream from tile t0 = cstart(k) / 64 on: tiles [t0, tsplit) hold a slot of class <= k and take the id test,
+// tiles [tsplit, ntiles) hold higher classes only (or the sentinels) and take none -- rc2 - r2 goes straight into
+// v_alignbit.  Two loops, no branch inside either (a branch in the tile loop makes hipcc wait on lgkmcnt(0) every tile).
+// The words (bit t: slot 64 (t0 + t) + l) come back in `words`, the counts as in search_group.
+template <int GC>
+__device__ __forceinline__ int32_t class_group(const SweepArgs<float>& a, const Pos<float>* tile, int32_t t0, int32_t tsplit,
+                                               int32_t ntiles, int lane, const Pos<float>& pi_l, uint32_t* words) {
+  float xi[GC], yi[GC], zi[GC];
+  uint32_t gi1[GC], bits[GC];
+#pragma unroll
+  for (int k = 0; k < GC; k++) {
+    xi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int32_t, pi_l.x), k));
+    yi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int32_t, pi_l.y), k));
+    zi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int32_t, pi_l.z), k));
+    gi1[k] = (uint32_t)__builtin_amdgcn_readlane(pi_l.gid, k) + 1u;
+    bits[k] = 0;
+  }
+  // the tests of search_group's VBITS_F32 form, with (ID) or without the id word
+  auto test_tile = [&](const Pos<float>& pj, auto id) {
+    constexpr int HALF = (GC + 1) / 2;
+#pragma unroll
+    for (int k = 0; k < GC; k++) {
+      if (k == HALF) __builtin_amdgcn_sched_barrier(0);
+      const float dx = sub_rn(pj.x, xi[k]), dy = sub_rn(pj.y, yi[k]), dz = sub_rn(pj.z, zi[k]);
+      const float r2 = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
+      uint32_t w = __builtin_bit_cast(uint32_t, sub_rn(a.rc2, r2));
+      if constexpr (decltype(id)::value) w |= (uint32_t)pj.gid - gi1[k];
+      bits[k] = __builtin_amdgcn_alignbit(bits[k], w, 31);
+    }
+  };
+  const std::true_type with_id;
+  const std::false_type no_id;
+  const int32_t last = (ntiles - 1) * WAVE + lane;
+  Pos<float> pa = tile[t0 * WAVE + lane], pb;
+  int32_t t = t0;
+  __builtin_amdgcn_s_setprio(0);
+  for (; t + 1 < tsplit; t += 2) {
+    pb = tile[(t + 1) * WAVE + lane];
+    test_tile(pa, with_id);
+    pa = tile[min((t + 2) * WAVE + lane, last)];
+    test_tile(pb, with_id);
+  }
+  if (t < tsplit) {  // (uniform) an odd number of id-tested tiles
+    test_tile(pa, with_id);
+    t++;
+    pa = tile[min(t * WAVE + lane, last)];
+  }
+  for (; t + 1 < ntiles; t += 2) {
+    pb = tile[(t + 1) * WAVE + lane];
+    test_tile(pa, no_id);
+    pa = tile[min((t + 2) * WAVE + lane, last)];
+    test_tile(pb, no_id);
+  }
+  if (t < ntiles) test_tile(pa, no_id);
+  __builtin_amdgcn_s_setprio(NL_PRIO);
+  const int32_t nt = ntiles - t0;  // >= 1: the group's own particles lie behind cstart(k)
+  uint32_t tot[GC];
+#pragma unroll
+  for (int k = 0; k < GC; k++) words[k] = __brev(~bits[k]) >> (32 - nt);  // tile t0 + t ended at bit nt - 1 - t
+#pragma unroll
+  for (int k = 0; k < GC; k += 2) {  // two rows per DPP sum (fewer than 2^16 partners each)
+    const uint32_t two = wave_sum_dpp((uint32_t)__popc(words[k]) | (k + 1 < GC ? (uint32_t)__popc(words[k + 1]) << 16 : 0u));
+    tot[k] = two & 0xffffu;
+    if (k + 1 < GC) tot[k + 1] = two >> 16;
+  }
+  uint32_t mine = 0;
+#pragma unroll
+  for (int k = 0; k < GC; k++) mine = lane == k ? tot[k] : mine;
+  return (int32_t)mine;
+}
+
+template <int GC>
+__device__ __forceinline__ void class_pipe_group(const SweepArgs<float>& a, const Pos<float>* tile, int32_t t0, int32_t tsplit,
+                                                 int32_t ntiles, int lane, const Pos<float>& pi_l, PipePending& p) {
+  uint32_t words[GC];
+  p.mine = class_group<GC>(a, tile, t0, tsplit, ntiles, lane, pi_l, words);
+#pragma unroll
+  for (int k = 0; k < GC; k++) p.w[k] = words[k];
+}
+
+// The groups of the cell.  A class-k group walks ntiles - cstart(k) / 64 tiles, so the waves are dealt PAIRS of classes
+// (k, C - 1 - k): C / 2 pairs, NW / (C / 2) waves a pair, and each of those waves takes an equal share of the groups of
+// both classes of its pair -- a long walk and a short one each.
+template <int IDC, int NW>
+__device__ __forceinline__ void class_search(const SweepArgs<float>& a, const ClsCtx<IDC>& c, const Pos<float>* tile, int lane, int wave,
+                                             PipePending& p) {
+  constexpr int G = PIPE_G, NP = IDC / 2, WP = NW / NP;
+  static_assert(NW % NP == 0, "waves a pair of classes");
+  const int32_t ntiles = (c.total_j + WAVE - 1) / WAVE;
+  const bool hi = hi_plane_used(1, ntiles);
+  const int pair = wave / WP, wj = wave - pair * WP;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int32_t k = h == 0 ? pair : IDC - 1 - pair;  // (uniform)
+    const int32_t ni = c.get(c.len, 27 * k + CLS_OWN);
+    const int32_t own = c.get(c.off, 27 * k + CLS_OWN), slot_b = c.get(c.src, 27 * k + CLS_OWN);
+    const int32_t t0 = c.get(c.off, 27 * k) / WAVE;
+    const int32_t tsplit = k + 1 < IDC ? (c.get(c.off, 27 * (k + 1)) + WAVE - 1) / WAVE : ntiles;
+    const int32_t ngroups = (ni + WP * G - 1) / (WP * G) * WP;
+    if (ni <= 0) continue;
+    const int32_t gbase = ni / ngroups, grem = ni - gbase * ngroups;
+    for (int32_t g = wj; g < ngroups; g += WP) {
+      const int32_t i0 = g * gbase + min(g, grem);
+      const int32_t gcount = gbase + (g < grem ? 1 : 0);  // wave-uniform
+      if (gcount <= 0) break;
+      pipe_flush<NW == SWEEP_WAVES>(a, p, lane, hi);
+      const int32_t kk = min(lane, gcount - 1);
+      Pos<float> pi_l = tile[own + i0 + kk];  // from the staged stream
+      const int32_t row_l = a.sorted_row[slot_b + i0 + kk];
+      if (lane >= gcount) pi_l.x = 0, pi_l.y = 0, pi_l.z = 0, pi_l.gid = 0;
+      switch (gcount) {
+        case 1: class_pipe_group<1>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
+        case 2: class_pipe_group<2>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
+        case 3: class_pipe_group<3>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
+        case 4: class_pipe_group<4>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
+        case 5: class_pipe_group<5>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
+        case 6: class_pipe_group<6>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
+        default: class_pipe_group<7>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
+      }
+      p.row_l = row_l, p.slot0 = slot_b + i0, p.gcount = gcount;
+    }
+  }
+}
+
+// k_sweep_lean_f32 for an id-class build (fp32 half list, open box, ids 0..n-1, IDC = C classes): the class-major
+// stream, the class-paired groups; a cell whose stream does not fit goes to k_sweep_list_f32 as there.
+template <int IDC, int NW = SWEEP_WAVES, int CAP = SweepCfg<float>::CAP>
+__global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80))) k_sweep_class_f32(SweepArgs<float> a) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
+  __shared__ __attribute__((aligned(32))) Pos<float> buf[CAP];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  __builtin_amdgcn_s_setprio(NL_PRIO);
+  ClsCtx<IDC> c;
+  if (!cls_setup<IDC>(a, lane, c)) return;
+  if (c.total_j > CAP) {  // (rare) several LDS batches: k_sweep_list_f32
+    if (tid == 0) a.full27_list[atomicAdd(a.full27_count, 1)] = c.cx + (c.cy + c.cz * a.my) * a.mx;
+    return;
+  }
+  cls_stage<IDC, NW>(a.sorted, c, buf, lane, wave);
+  const int32_t pad = c.total_j + tid;
+  if (pad < ((c.total_j + WAVE - 1) & ~(WAVE - 1))) {
+    Pos<float> sentinel;  // as in pipe_stage: never in range
+    sentinel.x = 1.0e18f, sentinel.y = 0.f, sentinel.z = 0.f, sentinel.gid = INT32_MIN;
+    buf[pad] = sentinel;
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  PipePending pend;
+  pend.gcount = 0, pend.mine = 0, pend.row_l = 0, pend.slot0 = 0;
+  class_search<IDC, NW>(a, c, buf, lane, wave, pend);
+  pipe_flush<NW == SWEEP_WAVES>(a, pend, lane, hi_plane_used(1, (c.total_j + WAVE - 1) / WAVE));
+}
+
 // The cells k_sweep_pipe_f32 left out (local cell indices in full27_list): the batched search, a workgroup per cell.
 template <bool FULL>
 __global__ void __launch_bounds__(SWEEP_WAVES* WAVE) __attribute__((amdgpu_num_sgpr(80))) k_sweep_list_f32(SweepArgs<float> a) {
