@@ -132,6 +132,41 @@ int nl_set_periodic(nl_handle_t h, int minimum_image);
 int nl_set_periodic_axes(nl_handle_t h, int mask);
 int nl_get_periodic_axes(nl_handle_t h, int* mask);
 
+/* Triclinic boxes and box changes between builds (no reference counterpart: its box is orthogonal and fixed).
+ *   Box: LAMMPS convention, origin at 0: a = (Lx, 0, 0), b = (xy, Ly, 0), c = (xz, yz, Lz); a particle belongs to the cell
+ *     {la a + lb b + lc c : l in [0, 1)^3}.  nl_create(..., Lx, Ly, Lz, ...) is this box with zero tilt.
+ *   Mesh (double): the perpendicular widths w_x = Lx / sqrt(1 + (xy/Ly)^2 + ((xy yz - Ly xz)/(Ly Lz))^2),
+ *     w_y = Ly / sqrt(1 + (yz/Lz)^2), w_z = Lz; m_d = (int)(w_d / rc) >= 3 (NL_ERR_MESH); ms_d = L_d / m_d and ims_d rounded
+ *     as nl_create rounds them (zero tilt: the mesh, ms and ims of nl_create, bit for bit).  With m_d >= 3 every nonzero
+ *     lattice vector is at least 3 rc long: a pair has at most one image within rc, and the 27-cell stencil over cells in
+ *     sheared coordinates finds it.
+ *   Binning (position type T, round to nearest, no FMA): k_xy = (T)(xy/Ly), k_yz = (T)(yz/Lz),
+ *     k_xz = (T)((xz Ly - xy yz)/(Ly Lz)), each a double expression rounded once; x' = (x - y k_xy) - z k_xz,
+ *     y' = y - z k_yz, z' = z; the cell index of axis d is the nl_set_periodic_axes rule applied to d' ims_d (floor on a
+ *     periodic axis, truncation plus one wrap on an open one, NL_ERR_OUT_OF_BOX beyond one box length).  The wraps
+ *     n_d in {-1, 0, +1} of the periodic axes put the particle at its image q + S(n), S(n) = n_a a + n_b b + n_c c in double,
+ *     rounded to T once per component and added with one rounding per component (components where S is 0 untouched).
+ *     Cell and image are decided once, from the input coordinate.
+ *   Search: a stencil segment reached through the faces w = (wx, wy, wz) is staged at q_stored + S(w), rounded the same way;
+ *     r2 and the cut-off test are unchanged.  Zero tilt: S(w) = -+(T)L_d, today's lists bit for bit.
+ *   A tilt needs periodic axes: xy != 0 needs x and y in the nl_set_periodic_axes mask, xz x and z, yz y and z (the
+ *     hexagonal slab, mask 3 with xy only, is allowed).  The setters may come in either order: a build or update that
+ *     violates this is NL_ERR_STATE.  Open axes therefore keep the rule of nl_set_periodic_axes exactly.
+ *   Skin check (nl_update_list reason (c), double, no FMA): fold the periodic axes z, y, x (LAMMPS' minimum_image order):
+ *     k = rint(dz/Lz), dz -= k Lz, dy -= k yz, dx -= k xz; k = rint(dy/Ly), dy -= k Ly, dx -= k xy; dx -= Lx rint(dx/Lx).
+ *   nl_lj_forces(_typed)(_enqueue): with a tilt the pair is folded in T in the same order (rint form); every component of
+ *     the image within rc is below L_d / 2, so this is the image the list used.  The type filter's r2 is taken at S(w).
+ *   nl_set_box: synchronous, finishes a pending build.  A changed box drops the list, makes the next nl_update_list build
+ *     (its reason (a)) and captures graphs again; the same box again changes nothing.  Non-finite values or L <= 0 are
+ *     NL_ERR_ARG, a mesh of more than 2e9 cells NL_ERR_ARG, any m_d < 3 NL_ERR_MESH, failed growth NL_ERR_NOMEM: an error
+ *     leaves the old box, buffers and list.  An initialised handle regrows its per-cell and per-row buffers where the new mesh
+ *     needs more; the list capacity is re-estimated from the new volume unless nl_set_capacity set it; exclusion and type
+ *     tables are kept; nl_get_mesh reports the mesh of the next build.  Slab and distributed builds are NL_ERR_STATE while
+ *     the box differs from nl_create's.
+ *   nl_get_box: box = {Lx, Ly, Lz, xy, xz, yz} of the next build. */
+int nl_set_box(nl_handle_t h, double Lx, double Ly, double Lz, double xy, double xz, double yz);
+int nl_get_box(nl_handle_t h, double box[6]);
+
 int nl_destroy(nl_handle_t h);
 
 /* --------------------------------------------------------------------------------------------------- build */

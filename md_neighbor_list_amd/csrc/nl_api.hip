@@ -85,7 +85,12 @@ struct BuildPlan {
   int32_t pbc = 0;      // axes of the minimum image (nl_set_periodic_axes)
   int32_t idc = 0;      // SEARCH_MASKS with id classes (k_sweep_class_f32, k_fill_masks<IDC>): C = 2 or 4 classes, 0 = off
   int32_t id_shift = 0; // class of an id: id >> id_shift
-  auto tie() const { return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, pbc, idc, id_shift); }
+  Box box = {{0, 0, 0}, 0, 0, 0};  // the box of the build (nl_set_box): what its consumers (k_lj, the skin check) fold with
+  int32_t tilt = 0;     // box.xy, box.xz or box.yz is not 0: binning and search in sheared coordinates
+  auto tie() const {
+    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, pbc, idc, id_shift,
+                    box.L[0], box.L[1], box.L[2], box.xy, box.xz, box.yz, tilt);
+  }
   bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
 };
 
@@ -110,6 +115,11 @@ struct nl_handle_s {
   double rc = 0, L[3] = {0, 0, 0}, rc2 = 0;
   int32_t m[3] = {0, 0, 0};
   int64_t ncell = 0;
+  // nl_set_box: the tilt of the triclinic cell b = (xy, Ly, 0), c = (xz, yz, Lz) and its shear in double (Grid::k before
+  // the rounding to T); L0 = the box of nl_create (slab and distributed builds need it unchanged)
+  double xy = 0, xz = 0, yz = 0, shear[3] = {0, 0, 0}, L0[3] = {0, 0, 0};
+  int64_t mesh_cells_cap = 0, mesh_rows_cap = 0;  // cells and rows of x-cells the per-cell / per-row buffers hold
+  double* lat_dev = nullptr;  // [LATTICE_CODES][3] lattice vectors of the box of the next build (Grid::lat, SweepArgs::lat)
   float ims_f[3];
   double ims_d[3];
   float rc2_f = 0;
@@ -285,6 +295,52 @@ template <typename P> int dev_alloc(nl_handle_t h, P** p, size_t bytes) {
   return NL_OK;
 }
 
+// The per-cell and per-row buffers for the handle's mesh (h->m, h->ncell) and n particles: (re)allocated where the mesh needs
+// more cells or rows than they hold (nl_initialize allocates them all, nl_set_box only what a larger mesh needs), and cleared:
+// the status and meta words sit behind the histogram, at a place that moves with the number of cells, and every word of
+// them, of the row cursors and of the scan's look-back array must be zero before a build.
+// dev_alloc that keeps the old buffer where the new one cannot be had (nl_set_box: an error leaves the handle as it was)
+template <typename P> int swap_alloc(nl_handle_t h, P** p, size_t bytes) {
+  void* fresh = nullptr;
+  const hipError_t e = hipMalloc(&fresh, bytes ? bytes : 16);
+  if (e != hipSuccess) {
+    h->last_hip = (int)e;
+    return fail(h, e == hipErrorOutOfMemory ? NL_ERR_NOMEM : NL_ERR_HIP);
+  }
+  h->buffers_epoch++;  // a captured graph holds the old pointers
+  if (*p) (void)hipFree(*p);
+  *p = static_cast<P*>(fresh);
+  return NL_OK;
+}
+int reserve_mesh(nl_handle_t h, size_t n) {
+  int rc;
+  const size_t rows_cap = std::max<size_t>((size_t)h->m[1] * h->m[2], (size_t)h->mesh_rows_cap);
+  const size_t cells_cap = std::max<size_t>((size_t)h->ncell, (size_t)h->mesh_cells_cap);
+  if (rows_cap > (size_t)h->mesh_rows_cap) {
+    if ((rc = swap_alloc(h, &h->row_start, 4 * (2 * rows_cap + 64)))) return rc;  // (two arrays: a split slab build has two passes)
+    if ((rc = swap_alloc(h, &h->blk_base, 4 * (rows_cap * (size_t)h->bin_blocks + 16)))) return rc;
+    if ((rc = swap_alloc(h, &h->row_cursor, 4 * (rows_cap + 16)))) return rc;
+  }
+  if (cells_cap > (size_t)h->mesh_cells_cap || rows_cap > (size_t)h->mesh_rows_cap) {
+    // cells handed from one search kernel to another: half-shell -> 27-cell search, pipelined COUNT -> batched search
+    if ((rc = swap_alloc(h, &h->full27_list, 4 * (cells_cap + 16)))) return rc;
+    if ((rc = swap_alloc(h, &h->cell_count, 4 * (cells_cap + 64 + 2 * rows_cap)))) return rc;
+    if ((rc = swap_alloc(h, &h->cell_start, 4 * (4 * cells_cap + 32)))) return rc;  // (cell_start, or the fine-row table: 4 M + 1)
+    if ((rc = swap_alloc(h, &h->cls_start, 4 * (4 * cells_cap + 32)))) return rc;   // (the class table: up to 4 M + 1)
+    const size_t nblk = std::max<size_t>(n, cells_cap) / SCAN_BLOCK + 2;
+    if ((rc = swap_alloc(h, &h->scan_look, 8 * (nblk + 1)))) return rc;
+    h->scan_blocks = (int32_t)nblk;
+  }
+  h->mesh_rows_cap = (int64_t)rows_cap, h->mesh_cells_cap = (int64_t)cells_cap;
+  h->row_count = h->cell_count + h->ncell + 32;
+  h->status = reinterpret_cast<uint32_t*>(h->cell_count + h->ncell);  // cleared by the same memset as the histogram
+  h->buffers_epoch++;  // (a captured graph holds the old status address)
+  HIPCHK(h, hipMemset(h->row_cursor, 0, 4 * (rows_cap + 16)));
+  HIPCHK(h, hipMemset(h->scan_look, 0, 8 * ((size_t)h->scan_blocks + 1)));
+  HIPCHK(h, hipMemset(h->cell_count, 0, 4 * (cells_cap + 64 + 2 * rows_cap)));
+  return NL_OK;
+}
+
 float floor_to_float(double v) {  // largest float <= v
   float f = (float)v;
   if ((double)f > v) f = std::nextafterf(f, -INFINITY);
@@ -297,6 +353,28 @@ int status_to_error(uint32_t st) {
   if (st & ST_INDEX_OVERFLOW) return NL_ERR_INDEX_OVERFLOW;
   if (st & ST_CAPACITY) return NL_ERR_CAPACITY;
   return NL_OK;
+}
+
+bool has_tilt(nl_handle_t h) { return h->xy != 0 || h->xz != 0 || h->yz != 0; }
+Box box_of(nl_handle_t h) { return Box{{h->L[0], h->L[1], h->L[2]}, h->xy, h->xz, h->yz}; }
+// lat[3 wr + d] = component d of S(n) = n_a a + n_b b + n_c c for the code wr = (n_a + 1) | (n_b + 1) << 2 | (n_c + 1) << 4
+// (lattice_shift in nl_kernels.hpp), in double, in the order of the rule in nl_hip.h (this file is compiled without FMA
+// contraction); codes with a field of 3 are never looked up
+void lattice_table(const Box& b, double* lat) {
+  for (int wr = 0; wr < LATTICE_CODES; wr++) {
+    const double na = (wr & 3) - 1, nb = ((wr >> 2) & 3) - 1, nc = ((wr >> 4) & 3) - 1;
+    lat[3 * wr + 0] = (na * b.L[0] + nb * b.xy) + nc * b.xz;
+    lat[3 * wr + 1] = nb * b.L[1] + nc * b.yz;
+    lat[3 * wr + 2] = nc * b.L[2];
+  }
+}
+// The box differs from nl_create's (slab and distributed builds refuse it)
+bool box_changed(nl_handle_t h) {
+  return has_tilt(h) || h->L[0] != h->L0[0] || h->L[1] != h->L0[1] || h->L[2] != h->L0[2];
+}
+// A tilt needs both of its axes periodic: xy x and y, xz x and z, yz y and z (NL_ERR_STATE at the build otherwise)
+bool tilt_mask_ok(nl_handle_t h) {
+  return (h->xy == 0 || (h->pbc & 3) == 3) && (h->xz == 0 || (h->pbc & 5) == 5) && (h->yz == 0 || (h->pbc & 6) == 6);
 }
 
 template <typename T> Grid<T> make_grid(nl_handle_t h, const BuildArgs& a, int pbc) {
@@ -314,6 +392,9 @@ template <typename T> Grid<T> make_grid(nl_handle_t h, const BuildArgs& a, int p
   g.z_first = a.slab ? a.z_lo - 1 : 0;
   for (int d = 0; d < 3; d++) g.L[d] = (T)h->L[d];
   g.gate = h->gate;
+  g.tilt = has_tilt(h) ? 1 : 0;
+  for (int d = 0; d < 3; d++) g.k[d] = (T)h->shear[d];
+  g.lat = h->lat_dev;
   return g;
 }
 
@@ -382,6 +463,8 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.dbg = h->dbg_flags;
   a.dbg_buf = h->dbg_buf;
   a.gate = h->gate;
+  for (int d = 0; d < 3; d++) a.k[d] = (T)h->shear[d];
+  a.lat = h->lat_dev;
   return a;
 }
 
@@ -578,6 +661,8 @@ template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, in
   BuildPlan p;
   p.full = h->list_kind == NL_LIST_FULL;
   p.pbc = h->pbc;
+  p.box = box_of(h);
+  p.tilt = has_tilt(h) ? 1 : 0;
   p.filter = filter_tables(h);
   // 64-bit list offsets as soon as the list this handle can hold exceeds what an int32 key_pointer can address
   // (the reference's own limit, neighlist_cpu.hpp:15,29); nl_set_offset_width overrides.
@@ -809,12 +894,17 @@ int dispatch_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStr
 
 // Default list capacity (unless the caller fixed it): ideal-gas estimate of the half-pair count
 // N * rho * (2/3) pi rc^3 with 30 % head room, twice that for a full list.
-int estimate_capacity(nl_handle_t h) {
-  if (h->capacity_user) return NL_OK;
-  const double rho = (double)h->n_max / (h->L[0] * h->L[1] * h->L[2]);
+int64_t estimate_want(nl_handle_t h) {
+  const double rho = (double)h->n_max / (h->L[0] * h->L[1] * h->L[2]);  // (L[0] L[1] L[2]: the volume of a triclinic cell too)
   const double per = rho * (2.0 / 3.0) * 3.14159265358979323846 * h->rc * h->rc * h->rc;
   int64_t want = (int64_t)((double)h->n_max * per * 1.3) + 64 * (int64_t)h->n_max + 4096;
   if (h->list_kind == NL_LIST_FULL) want *= 2;
+  return want;
+}
+
+int estimate_capacity(nl_handle_t h) {
+  if (h->capacity_user) return NL_OK;
+  const int64_t want = estimate_want(h);
   if (want > h->capacity) {
     if (int rc = dev_alloc(h, &h->list, 4 * (size_t)want)) return rc;
     h->capacity = want;
@@ -1088,7 +1178,7 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
   h->rc2 = rc * rc;  // neighlist_cpu.hpp:394 (double)
   h->rc2_f = floor_to_float(h->rc2);
   for (int d = 0; d < 3; d++) {
-    h->L[d] = L[d], h->m[d] = m[d];
+    h->L[d] = L[d], h->m[d] = m[d], h->L0[d] = L[d];
     // ms_ and ims_ live in a Vec of the position type (neighlist_cpu.hpp:12,389-391,409-411)
     const float ms_f = (float)(L[d] / m[d]);
     h->ms_f[d] = ms_f;
@@ -1097,7 +1187,11 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
     h->ims_d[d] = 1.0 / ms_d;
   }
   h->ncell = (int64_t)m[0] * m[1] * m[2];
-  if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
+  double lat0[LATTICE_CODES * 3];
+  lattice_table(box_of(h), lat0);
+  if (hipMalloc(reinterpret_cast<void**>(&h->lat_dev), sizeof(lat0)) != hipSuccess ||
+      hipMemcpy(h->lat_dev, lat0, sizeof(lat0), hipMemcpyHostToDevice) != hipSuccess ||
+      hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&h->host), sizeof(HostResult), hipHostMallocDefault) != hipSuccess) {
     nl_destroy(h);
     return NL_ERR_HIP;
@@ -1130,7 +1224,7 @@ int nl_destroy(nl_handle_t h) {
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
   void* bufs[] = {h->snap, h->skin_words, h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
                   h->cell_start, h->cls_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor,
-                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre, h->ty_types, h->ty_rc2, h->lj_par};
+                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre, h->ty_types, h->ty_rc2, h->lj_par, h->lat_dev};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (h->host) (void)hipHostFree(h->host);
@@ -1169,43 +1263,29 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   if (h->resort_buf) (void)hipFree(h->resort_buf), h->resort_buf = nullptr;
   if ((rc = dev_alloc(h, &h->progress, 4 * (n + 16)))) return rc;
   if ((rc = dev_alloc(h, &h->base_sorted, 8 * (n + 64)))) return rc;  // (dense builds only: k_fill_dense)
-  {
-    const size_t nrows = (size_t)h->m[1] * h->m[2];
-    // chunk per block: 4096 particles, 8192 from half a million on (cfg 2: binning 60.7 -> 55.9 us, cfg 3 64.7 -> 58.0;
-    // 16384: 65.7), more for very large N so that blk_base stays small
-    h->bin_chunk = n >= (1 << 19) ? 8192 : 4096;
-    if (const char* v = getenv("NL_DEBUG_BIN_CHUNK")) h->bin_chunk = std::max(1024, atoi(v));  // diagnostics
-    while ((n + h->bin_chunk - 1) / h->bin_chunk > 1024) h->bin_chunk *= 2;
-    h->bin_blocks = (int32_t)((n + h->bin_chunk - 1) / h->bin_chunk);
-    if (h->bin_blocks < 1) h->bin_blocks = 1;
-    if ((rc = dev_alloc(h, &h->row_start, 4 * (2 * nrows + 64)))) return rc;  // (two arrays: a split slab build has two passes)
-    if ((rc = dev_alloc(h, &h->blk_base, 4 * (nrows * (size_t)h->bin_blocks + 16)))) return rc;
-    if ((rc = dev_alloc(h, &h->tmp_pos, pos_bytes * (n + 16)))) return rc;
-    if ((rc = dev_alloc(h, &h->tmp_row, 4 * (n + 16)))) return rc;
-    h->tmp_slots = n + 16;  // (the buckets of the one-pass binning grow them on first use)
-    if ((rc = dev_alloc(h, &h->row_cursor, 4 * (nrows + 16)))) return rc;
-    HIPCHK(h, hipMemset(h->row_cursor, 0, 4 * (nrows + 16)));
-  }
+  // chunk per block: 4096 particles, 8192 from half a million on (cfg 2: binning 60.7 -> 55.9 us, cfg 3 64.7 -> 58.0;
+  // 16384: 65.7), more for very large N so that blk_base stays small
+  h->bin_chunk = n >= (1 << 19) ? 8192 : 4096;
+  if (const char* v = getenv("NL_DEBUG_BIN_CHUNK")) h->bin_chunk = std::max(1024, atoi(v));  // diagnostics
+  while ((n + h->bin_chunk - 1) / h->bin_chunk > 1024) h->bin_chunk *= 2;
+  h->bin_blocks = (int32_t)((n + h->bin_chunk - 1) / h->bin_chunk);
+  if (h->bin_blocks < 1) h->bin_blocks = 1;
+  if ((rc = dev_alloc(h, &h->tmp_pos, pos_bytes * (n + 16)))) return rc;
+  if ((rc = dev_alloc(h, &h->tmp_row, 4 * (n + 16)))) return rc;
+  h->tmp_slots = n + 16;  // (the buckets of the one-pass binning grow them on first use)
   if (h->sweep_variant >= 3) {
     if ((rc = dev_alloc(h, &h->masks, (size_t)MASK_ROW_BYTES * (n + 64)))) return rc;
     h->masks_bytes = (size_t)MASK_ROW_BYTES * (n + 64);
   }
-  // cells handed from one search kernel to another: half-shell -> 27-cell search, pipelined COUNT -> batched search
-  if ((rc = dev_alloc(h, &h->full27_list, 4 * ((size_t)h->ncell + 16)))) return rc;
   if ((rc = dev_alloc(h, &h->dbg_buf, 8 * (64 + 4 * 4096)))) return rc;
   HIPCHK(h, hipMemset(h->dbg_buf, 0, 8 * (64 + 4 * 4096)));
-  if ((rc = dev_alloc(h, &h->cell_count, 4 * ((size_t)h->ncell + 64 + 2 * (size_t)h->m[1] * h->m[2])))) return rc;
-  h->row_count = h->cell_count + h->ncell + 32;
-  if ((rc = dev_alloc(h, &h->cell_start, 4 * (4 * (size_t)h->ncell + 32)))) return rc;  // (cell_start, or the fine-row table: 4 M + 1)
-  if ((rc = dev_alloc(h, &h->cls_start, 4 * (4 * (size_t)h->ncell + 32)))) return rc;   // (the class table: up to 4 M + 1)
-  const size_t nblk = std::max<size_t>(n, (size_t)h->ncell) / SCAN_BLOCK + 2;
-  if ((rc = dev_alloc(h, &h->scan_look, 8 * (nblk + 1)))) return rc;
-  HIPCHK(h, hipMemset(h->scan_look, 0, 8 * (nblk + 1)));
-  h->scan_blocks = (int32_t)nblk;
   if ((rc = dev_alloc(h, &h->totals, 8 * 4))) return rc;
-  h->status = reinterpret_cast<uint32_t*>(h->cell_count + h->ncell);  // cleared by the same memset as the histogram
   HIPCHK(h, hipMemset(h->totals, 0, 32));
-  HIPCHK(h, hipMemset(h->cell_count, 0, 4 * ((size_t)h->ncell + 64 + 2 * (size_t)h->m[1] * h->m[2])));
+  for (int32_t** b : {&h->row_start, &h->blk_base, &h->row_cursor, &h->full27_list, &h->cell_count, &h->cell_start, &h->cls_start})
+    if (*b) (void)hipFree(*b), *b = nullptr;  // (all of them anew, without holding the old ones meanwhile)
+  if (h->scan_look) (void)hipFree(h->scan_look), h->scan_look = nullptr;
+  h->mesh_cells_cap = h->mesh_rows_cap = 0;
+  if ((rc = reserve_mesh(h, n))) return rc;
   h->n_max = n_max;
   if ((rc = estimate_capacity(h))) return rc;
   h->t_valid = false;
@@ -1223,6 +1303,85 @@ int nl_set_periodic_axes(nl_handle_t h, int mask) {
     h->built = false;
     h->t_valid = false;
   }
+  return NL_OK;
+}
+
+int nl_set_box(nl_handle_t h, double Lx, double Ly, double Lz, double xy, double xz, double yz) {
+  if (!h) return NL_ERR_ARG;
+  const double L[3] = {Lx, Ly, Lz};
+  for (double v : {Lx, Ly, Lz, xy, xz, yz})
+    if (!std::isfinite(v)) return fail(h, NL_ERR_ARG);
+  if (!(Lx > 0) || !(Ly > 0) || !(Lz > 0)) return fail(h, NL_ERR_ARG);
+  // the perpendicular widths of the cell (the distances between opposite faces): every axis needs 3 cells of at least rc
+  const double sx = (xy * yz - Ly * xz) / (Ly * Lz);
+  const double w[3] = {Lx / std::sqrt(1.0 + (xy / Ly) * (xy / Ly) + sx * sx), Ly / std::sqrt(1.0 + (yz / Lz) * (yz / Lz)), Lz};
+  int32_t m[3];
+  for (int d = 0; d < 3; d++) {
+    const double r = w[d] / h->rc;
+    if (!(r < 2147483647.0)) return fail(h, NL_ERR_ARG);
+    m[d] = (int32_t)r;
+  }
+  if ((double)m[0] * m[1] * m[2] > 2.0e9) return fail(h, NL_ERR_ARG);
+  for (int d = 0; d < 3; d++)
+    if (m[d] < 3) return fail(h, NL_ERR_MESH);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->pending) (void)finish(h, false);
+  if (Lx == h->L[0] && Ly == h->L[1] && Lz == h->L[2] && xy == h->xy && xz == h->xz && yz == h->yz) return NL_OK;
+  // the old box, put back where the new one cannot be had: every step below either succeeds or leaves the buffers usable
+  // for the old mesh (swap_alloc keeps a buffer it cannot replace)
+  double old_L[3], old_ims_d[3], old_shear[3];
+  float old_ms_f[3], old_ims_f[3];
+  int32_t old_m[3];
+  for (int d = 0; d < 3; d++)
+    old_L[d] = h->L[d], old_m[d] = h->m[d], old_ms_f[d] = h->ms_f[d], old_ims_f[d] = h->ims_f[d], old_ims_d[d] = h->ims_d[d],
+    old_shear[d] = h->shear[d];
+  const double old_tilt[3] = {h->xy, h->xz, h->yz};
+  const int64_t old_ncell = h->ncell;
+  auto restore = [&](int rc) {
+    for (int d = 0; d < 3; d++)
+      h->L[d] = old_L[d], h->m[d] = old_m[d], h->ms_f[d] = old_ms_f[d], h->ims_f[d] = old_ims_f[d], h->ims_d[d] = old_ims_d[d],
+      h->shear[d] = old_shear[d];
+    h->xy = old_tilt[0], h->xz = old_tilt[1], h->yz = old_tilt[2];
+    h->ncell = old_ncell;
+    if (h->mesh_cells_cap > 0) (void)reserve_mesh(h, (size_t)h->n_max);  // (no allocation: points the status word back, clears)
+    double lat[LATTICE_CODES * 3];
+    lattice_table(box_of(h), lat);
+    (void)hipMemcpy(h->lat_dev, lat, sizeof(lat), hipMemcpyHostToDevice);
+    return fail(h, rc);
+  };
+  for (int d = 0; d < 3; d++) {  // (as nl_create)
+    h->L[d] = L[d], h->m[d] = m[d];
+    const float ms_f = (float)(L[d] / m[d]);
+    h->ms_f[d] = ms_f;
+    h->ims_f[d] = (float)(1.0 / (double)ms_f);
+    h->ims_d[d] = 1.0 / (L[d] / m[d]);
+  }
+  h->xy = xy, h->xz = xz, h->yz = yz;
+  h->shear[0] = xy / Ly, h->shear[1] = (xz * Ly - xy * yz) / (Ly * Lz), h->shear[2] = yz / Lz;
+  h->ncell = (int64_t)m[0] * m[1] * m[2];
+  if (h->mesh_cells_cap > 0) {  // an initialised handle (nl_initialize, n_max 0 included): its buffers follow the mesh
+    if (int rc = reserve_mesh(h, (size_t)h->n_max)) return restore(rc);
+    if (!h->capacity_user) {  // estimate_capacity for the new volume, keeping the old list where it cannot grow
+      const int64_t want = estimate_want(h);
+      if (want > h->capacity) {
+        if (int rc = swap_alloc(h, &h->list, 4 * (size_t)want)) return restore(rc);
+        h->capacity = want;
+      }
+    }
+    if (int rc = excl_reserve(h)) return restore(rc);  // (the pre-exclusion list follows the capacity)
+  }
+  double lat[LATTICE_CODES * 3];
+  lattice_table(box_of(h), lat);
+  if (hipMemcpy(h->lat_dev, lat, sizeof(lat), hipMemcpyHostToDevice) != hipSuccess) return restore(NL_ERR_HIP);
+  h->upd_valid = false;
+  h->built = false;
+  h->t_valid = false;
+  return NL_OK;
+}
+
+int nl_get_box(nl_handle_t h, double box[6]) {
+  if (!h || !box) return fail(h, NL_ERR_ARG);
+  box[0] = h->L[0], box[1] = h->L[1], box[2] = h->L[2], box[3] = h->xy, box[4] = h->xz, box[5] = h->yz;
   return NL_OK;
 }
 
@@ -1306,6 +1465,9 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
   }
   // an exclusion or type table applies to whole single-device builds of its own particle count
   if (filter_tables(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  // nl_set_box: slab and distributed builds need the box of nl_create, and a tilt needs both of its axes periodic
+  if (box_changed(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  if (!tilt_mask_ok(h)) return fail(h, NL_ERR_STATE);
   if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (filter_tables(h))  // (again, if an allocation failed since the table was set)

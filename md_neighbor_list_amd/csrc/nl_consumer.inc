@@ -18,6 +18,33 @@ template <typename T> __device__ __forceinline__ void lj_pair(T dx, T dy, T dz, 
   pe = eps4 * (s6 - (T)1) * s6;
 }
 
+// The image of a pair of the list's build.  Orthogonal box: one half-box test per periodic axis (L > 0; 0 = open axis).
+// Triclinic box (TRI: nl_set_box with a tilt): fold z, y, x in T with rint, as the skin check does in double -- one test per
+// axis is not enough there (after the z fold dy can exceed 1.5 Ly once yz is large).  Every component of the image within rc
+// is below L_d / 2, so this finds the image the list used.
+template <typename T> __device__ __forceinline__ T rint_t(T v) {
+  if constexpr (sizeof(T) == 4) return rintf(v);
+  else return rint(v);
+}
+template <typename T, bool TRI>
+__device__ __forceinline__ void lj_image(T& dx, T& dy, T& dz, T Lx, T Ly, T Lz, T xy, T xz, T yz) {
+  if constexpr (TRI) {
+    if (Lz > (T)0) {
+      const T k = rint_t(dz / Lz);
+      dz = dz - k * Lz, dy = dy - k * yz, dx = dx - k * xz;
+    }
+    if (Ly > (T)0) {
+      const T k = rint_t(dy / Ly);
+      dy = dy - k * Ly, dx = dx - k * xy;
+    }
+    if (Lx > (T)0) dx = dx - rint_t(dx / Lx) * Lx;
+  } else {
+    if (Lx > (T)0) dx = dx > (T)0.5 * Lx ? dx - Lx : dx < (T)-0.5 * Lx ? dx + Lx : dx;
+    if (Ly > (T)0) dy = dy > (T)0.5 * Ly ? dy - Ly : dy < (T)-0.5 * Ly ? dy + Ly : dy;
+    if (Lz > (T)0) dz = dz > (T)0.5 * Lz ? dz - Lz : dz < (T)-0.5 * Lz ? dz + Lz : dz;
+  }
+}
+
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -26,10 +53,11 @@ template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 
 // one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i.  status (nl_lj_forces_enqueue,
 // which does not wait for the build): the build's status word; a list whose build failed gives NaN forces.
-template <typename T, bool HALF, typename OFF>
+template <typename T, bool HALF, typename OFF, bool TRI>
 __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
                                             const int32_t* __restrict__ list, int32_t n, T eps4, T sig2, T rcf2,
-                                            T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status) {
+                                            T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status,
+                                            T xy, T xz, T yz) {
   const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (row >= n) return;
   if (status && *status != 0u) {  // (uniform: every row of the launch takes this branch)
@@ -52,9 +80,7 @@ __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t str
     T dx = xi - xj, dy = yi - yj, dz = zi - zj;
     // minimum-image list (nl_set_periodic_axes): on a periodic axis (L > 0) the pair is taken at the image the list
     // found it at
-    if (Lx > (T)0) dx = dx > (T)0.5 * Lx ? dx - Lx : dx < (T)-0.5 * Lx ? dx + Lx : dx;
-    if (Ly > (T)0) dy = dy > (T)0.5 * Ly ? dy - Ly : dy < (T)-0.5 * Ly ? dy + Ly : dy;
-    if (Lz > (T)0) dz = dz > (T)0.5 * Lz ? dz - Lz : dz < (T)-0.5 * Lz ? dz + Lz : dz;
+    lj_image<T, TRI>(dx, dy, dz, Lx, Ly, Lz, xy, xz, yz);
     lj_pair<T>(dx, dy, dz, eps4, sig2, rcf2, fx, fy, fz, pe, in);
     ax += fx, ay += fy, az += fz, ae += (T)0.5 * pe;
     if (HALF && in) {  // Newton's third law: the partner's share
@@ -86,15 +112,18 @@ int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, double eps, doub
   if (n == 0) return NL_OK;
   // box lengths for the minimum image on the axes of the list's build; 0 = open axis (the reference's distances,
   // neighlist_cpu.hpp:219-223)
-  const T Lx = (h->plan.pbc & 1) ? (T)h->L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)h->L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)h->L[2] : (T)0;
-  if (h->plan.full) {
-    hipLaunchKernelGGL((k_lj<T, false, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer),
-                       h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz, status);
-  } else {
-    HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
-    hipLaunchKernelGGL((k_lj<T, true, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer),
-                       h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz, status);
-  }
+  // (the build's box, BuildPlan::box, and its tilt: triclinic instances where it has one)
+  const Box& b = h->plan.box;
+  const T Lx = (h->plan.pbc & 1) ? (T)b.L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)b.L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)b.L[2] : (T)0;
+  const T xy = (T)b.xy, xz = (T)b.xz, yz = (T)b.yz;
+  auto launch = [&](auto half, auto tri) {
+    hipLaunchKernelGGL((k_lj<T, decltype(half)::value, OFF, decltype(tri)::value>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev),
+                       stride, static_cast<const OFF*>(h->key_pointer), h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz,
+                       status, xy, xz, yz);
+  };
+  if (!h->plan.full) HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
+  if (h->plan.tilt) h->plan.full ? launch(std::false_type(), std::true_type()) : launch(std::true_type(), std::true_type());
+  else h->plan.full ? launch(std::false_type(), std::false_type()) : launch(std::true_type(), std::false_type());
   HIPCHK(h, hipGetLastError());
   return NL_OK;
 }

@@ -40,6 +40,21 @@ template <> struct alignas(32) Pos<double> {
   int32_t row;
 };
 
+// The periodic cell of nl_set_box, LAMMPS convention: a = (L[0], 0, 0), b = (xy, L[1], 0), c = (xz, yz, L[2]), in double.
+struct Box {
+  double L[3];
+  double xy, xz, yz;
+};
+// The lattice vectors of the wraps / faces n in {-1, 0, 1}^3 by their code wr = (n_a + 1) | (n_b + 1) << 2 | (n_c + 1) << 4
+// (the code of CellCtx::wrap): lat[3 wr + d] = component d of S(n) = n_a a + n_b b + n_c c, evaluated in double on the host
+// ((n_a Lx + n_b xy) + n_c xz, n_b Ly + n_c yz, n_c Lz; lattice_table in nl_api.hip).  Here it is rounded to T once per
+// component.  With zero tilt that is -+(T)L_d or 0 on each axis: the orthogonal box's image shift.  A table lookup, not
+// double arithmetic, so that the kernels that carry it hold no more registers than the shift of the orthogonal box took.
+constexpr int LATTICE_CODES = 64;
+template <typename T> __device__ __forceinline__ void lattice_shift(const double* __restrict__ lat, int32_t wr, T s[3]) {
+  s[0] = (T)lat[3 * wr], s[1] = (T)lat[3 * wr + 1], s[2] = (T)lat[3 * wr + 2];
+}
+
 template <typename T> struct Grid {
   T ims[3];          // 1/ms rounded to T (neighlist_cpu.hpp:409-411)
   int32_t m[3];      // global mesh (neighlist_cpu.hpp:384-386)
@@ -55,6 +70,11 @@ template <typename T> struct Grid {
   int32_t z_first;   // slab: global layer that local layer 0 stands for, z_lo - 1 (may be -1)
   T L[3];            // box lengths rounded to T
   const uint32_t* gate = nullptr;  // nl_update_list: the `go` word of k_skin_check (gate_closed); nullptr in plain builds
+  // triclinic box (nl_set_box; 0 = no tilt, and nothing below is read): cells in sheared coordinates
+  // x' = (x - y k[0]) - z k[1], y' = y - z k[2], and a wrapped particle stored at its lattice image q + S(n)
+  int32_t tilt;
+  T k[3];            // k_xy = xy / Ly, k_xz = (xz Ly - xy yz) / (Ly Lz), k_yz = yz / Lz, each rounded to T once
+  const double* lat; // [LATTICE_CODES][3] lattice vectors of the box (lattice_shift)
 };
 
 // A launch of the update path (nl_update_list) runs only where k_skin_check has decided on a build: every kernel of
@@ -77,11 +97,15 @@ __device__ __forceinline__ double sub_rn(double a, double b) { return __dsub_rn(
 // GenHash(q) + ApplyPBC, neighlist_cpu.hpp:51-66: idx = (int32)(q * ims) truncated, one +-m wrap, then
 // idx.x + (idx.y + idx.z*my)*mx -- here with the z index taken relative to the local slab.
 // Returns -1 where the reference would index out of bounds, -2 for a particle outside this rank's layers.
+// Triclinic box (g.tilt): the same rule on the sheared coordinates (x', y', z), and the shift is the lattice vector
+// S(n) of the wraps n_d of the periodic axes (one decision, from the input coordinate).
 template <typename T>
 __device__ __forceinline__ int32_t local_cell(const Grid<T>& g, T x, T y, T z, int32_t* lz_out,
                                               int32_t* row_out = nullptr, T* shift_out = nullptr) {
-  const T t[3] = {mul_rn(x, g.ims[0]), mul_rn(y, g.ims[1]), mul_rn(z, g.ims[2])};
-  int32_t idx[3];
+  T xs = x, ys = y;
+  if (g.tilt) xs = sub_rn(sub_rn(x, mul_rn(y, g.k[0])), mul_rn(z, g.k[1])), ys = sub_rn(y, mul_rn(z, g.k[2]));
+  const T t[3] = {mul_rn(xs, g.ims[0]), mul_rn(ys, g.ims[1]), mul_rn(z, g.ims[2])};
+  int32_t idx[3], wrap[3] = {0, 0, 0};
   T sh[3] = {0, 0, 0};  // what to add to the coordinate so that it lies in / next to its cell (the callers apply it on
                         // the axes of the minimum-image mask only)
   bool bad = false;
@@ -93,12 +117,14 @@ __device__ __forceinline__ int32_t local_cell(const Grid<T>& g, T x, T y, T z, i
     // harmless in its open box, wrong for images; an open axis keeps the truncation and the coordinate)
     const bool per = (g.pbc >> d) & 1;
     if (per && t[d] < (T)0 && (T)v != t[d]) v -= 1;
-    if (v < 0) v += g.m[d], sh[d] = g.L[d];
-    if (v >= g.m[d]) v -= g.m[d], sh[d] = -g.L[d];
+    if (v < 0) v += g.m[d], sh[d] = g.L[d], wrap[d] = per ? 1 : 0;
+    if (v >= g.m[d]) v -= g.m[d], sh[d] = -g.L[d], wrap[d] = per ? -1 : 0;
     if (v < 0 || v >= g.m[d]) bad = true;
     idx[d] = v;
   }
   if (bad) return -1;
+  if (g.tilt) lattice_shift(g.lat, (wrap[0] + 1) | (wrap[1] + 1) << 2 | (wrap[2] + 1) << 4, sh);  // (no tilt along an open
+                                                                                                  // axis: S is 0 there)
   int32_t lz = idx[2] - g.z_origin;
   if (lz < 0) lz += g.m[2];
   if (lz >= g.mzl) return -2;
@@ -595,6 +621,10 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(const T* __restrict
       if (g.pbc & 2) p.y = add_rn(y[u], sh[1]);
       if (g.pbc & 4) p.z = add_rn(z[u], sh[2]);
       p.gid = id[u];
+      if (g.tilt) {  // triclinic: x' depends on y and z, so the x-cell is decided here and rides in the id slot
+        if (g.pbc & 1) p.x = add_rn(x[u], sh[0]);
+        p.gid = c - row * g.m[0];
+      }
       if constexpr (sizeof(T) == 8) p.row = i;
       tmp[dst] = p;
       tmp_row[dst] = i;
@@ -640,7 +670,8 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
   for (int u = 0; u < UNROLL; u++) row[u] = -1, rank[u] = 0;
   // the row of a particle (-1: rejected, its status bit noted); minimum-image mode: y and z moved to their image
   // (x keeps its value until k_bin_cells has derived the x-cell from it)
-  auto classify = [&](int32_t i, T& xi, T& yi, T& zi, uint32_t& fl) {
+  // (triclinic: x moved as well, and the id slot carries the x-cell, as in k_bin_scatter)
+  auto classify = [&](int32_t i, T& xi, T& yi, T& zi, int32_t& idi, uint32_t& fl) {
     int32_t lz = 0, r = 0;
     T sh[3];
     const int32_t c = local_cell(g, xi, yi, zi, &lz, &r, sh);
@@ -654,6 +685,10 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
     }
     if (g.pbc & 2) yi = add_rn(yi, sh[1]);
     if (g.pbc & 4) zi = add_rn(zi, sh[2]);
+    if (g.tilt) {
+      if (g.pbc & 1) xi = add_rn(xi, sh[0]);
+      idi = c - r * g.m[0];
+    }
     return r;
   };
   uint32_t fl = 0;
@@ -662,7 +697,7 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
 #pragma unroll
     for (int u = 0; u < UNROLL; u++) {
       const int32_t i = i0 + u * BIN_THREADS;
-      row[u] = i < end ? classify(i, x[u], y[u], z[u], fl) : -1;
+      row[u] = i < end ? classify(i, x[u], y[u], z[u], id[u], fl) : -1;
       if (row[u] >= 0) rank[u] = atomicAdd(&slot[row[u]], 1);
     }
   }
@@ -738,7 +773,7 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
     for (int u = 0; u < UNROLL; u++) {
       const int32_t i = i0 + u * BIN_THREADS;
       uint32_t unused = 0;
-      const int32_t r = i < end ? classify(i, x[u], y[u], z[u], unused) : -1;
+      const int32_t r = i < end ? classify(i, x[u], y[u], z[u], id[u], unused) : -1;
       if (r >= 0) put(r, atomicAdd(&slot[r], 1), i, x[u], y[u], z[u], id[u]);
     }
   }
@@ -795,8 +830,11 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
     const T f = sub_rn(t, (T)(int32_t)t);
     return (f >= (T)0.25 ? 1 : 0) + (f >= (T)0.5 ? 1 : 0) + (f >= (T)0.75 ? 1 : 0);
   };
+  // triclinic (plain rows only: the fine-row and id-class builds are open-box): the row pass decided the x-cell from
+  // the input coordinate and left it in the id slot; a tilted build has no slab ids, so the id is the input row
+  const bool tilt = !FINE && IDC == 0 && g.tilt;
   auto bin_of = [&](const Pos<T>& p) {
-    const int32_t c = xcell1(p.x);
+    const int32_t c = tilt ? p.gid : xcell1(p.x);
     if constexpr (FINE) return quarter(p.z, g.ims[2]) * mx + c;
     else if constexpr (IDC > 0) return c * IDC + min((int32_t)((uint32_t)p.gid >> id_shift), IDC - 1);
     else return c;
@@ -859,7 +897,9 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
   }
   auto place = [&](Pos<T> p, int32_t row_of) {
     const int32_t dst = beg + atomicAdd(&cnt[bin_of(p)], 1);
-    if (g.pbc & 1) {  // periodic x: a wrapped x index means the particle is stored at its image
+    if (tilt) {
+      p.gid = row_of;  // (the row pass has moved x to the image already)
+    } else if (g.pbc & 1) {  // periodic x: a wrapped x index means the particle is stored at its image
       const T tx = mul_rn(p.x, g.ims[0]);
       int32_t v = (int32_t)tx;
       if (tx < (T)0 && (T)v != tx) v -= 1;
@@ -938,7 +978,31 @@ template <typename T> struct SweepArgs {
   unsigned long long* dbg_buf;  // diagnostics only: cycle accumulators (dbg & 4)
   int32_t dbg;  // diagnostics only (NL_DEBUG_FLAGS): 1 = skip the search, 2 = skip the staging copy; 0 in production
   const uint32_t* gate = nullptr;  // nl_update_list: see gate_closed
+  // the box (nl_set_box; read by the PBC kernels only): a segment reached through faces w is staged at S(w)
+  T k[3];                         // the shear of Grid::k (screened fp64 search: the Cartesian centre of a sheared cell)
+  const double* lat;              // Grid::lat
 };
+
+// The image shift of a stencil segment reached through the periodic faces w (wr = its CellCtx::wrap code): S(w), which
+// in an orthogonal box is -+(T)L_d per axis, the shift the orthogonal kernels took before, bit for bit.  One formula for
+// both boxes (no branch on the tilt).
+template <typename T>
+__device__ __forceinline__ void face_shift(const SweepArgs<T>& a, int32_t wr, T& sx, T& sy, T& sz) {
+  T s[3];
+  lattice_shift(a.lat, wr, s);
+  sx = s[0], sy = s[1], sz = s[2];
+}
+
+// The screened fp64 search's re-check: pe (a lane's own partner, its face code wr) moved to S(w), one component at a time
+// (the three table loads kept apart: in flight together they cost the fp64 minimum-image COUNT sweep a wave per SIMD)
+__device__ __forceinline__ void recheck_image(const SweepArgs<double>& a, int32_t wr, Pos<double>& pe) {
+  const double* p = a.lat + 3 * wr;
+  pe.x = add_rn(pe.x, p[0]);
+  __builtin_amdgcn_sched_barrier(0);
+  pe.y = add_rn(pe.y, p[1]);
+  __builtin_amdgcn_sched_barrier(0);
+  pe.z = add_rn(pe.z, p[2]);
+}
 
 template <typename T> struct SweepCfg;
 // Hit masks in memory: a lane keeps one bit per j-tile, at most 24 (a staged stream has at most CAP / 64 = 20 tiles).
@@ -1122,12 +1186,7 @@ __device__ __forceinline__ int32_t search_group(const SweepArgs<T>& a, const typ
         pe.x = 0, pe.y = 0, pe.z = 0;
         if ((int32_t)uacc < 0) {
           pe = a.sorted[sc->sidx[at]];
-          if (PBC) {
-            const int32_t wr = sc->swrap[at];
-            pe.x = add_rn(pe.x, (double)((wr & 3) - 1) * a.L[0]);
-            pe.y = add_rn(pe.y, (double)(((wr >> 2) & 3) - 1) * a.L[1]);
-            pe.z = add_rn(pe.z, (double)(((wr >> 4) & 3) - 1) * a.L[2]);
-          }
+          if (PBC) recheck_image(a, sc->swrap[at], pe);
         }
 #pragma unroll
         for (int k = 0; k < GC; k++) {
@@ -1181,12 +1240,7 @@ __device__ __forceinline__ int32_t search_group(const SweepArgs<T>& a, const typ
         pe.x = 0, pe.y = 0, pe.z = 0;
         if ((any_unc >> lane) & 1ull) {
           pe = a.sorted[sc->sidx[at]];
-          if (PBC) {
-            const int32_t wr = sc->swrap[at];
-            pe.x = add_rn(pe.x, (double)((wr & 3) - 1) * a.L[0]);
-            pe.y = add_rn(pe.y, (double)(((wr >> 2) & 3) - 1) * a.L[1]);
-            pe.z = add_rn(pe.z, (double)(((wr >> 4) & 3) - 1) * a.L[2]);
-          }
+          if (PBC) recheck_image(a, sc->swrap[at], pe);
         }
 #pragma unroll
         for (int k = 0; k < GC; k++) {
@@ -1435,6 +1489,9 @@ __device__ __forceinline__ void cell_search(const SweepArgs<T>& a, const CellCtx
   T ox = 0, oy = 0, oz = 0;
   if constexpr (SCREEN) {
     ox = ((T)c.cx + (T)0.5) * a.ms[0], oy = ((T)c.cy + (T)0.5) * a.ms[1], oz = ((T)(c.cz + a.z_origin) + (T)0.5) * a.ms[2];
+    // (triclinic: the Cartesian centre of the sheared cell, y = y' + z k_yz, x = x' + y k_xy + z k_xz, so that the
+    // band of the screen does not widen with the tilt)
+    if (PBC) oy = oy + oz * a.k[2], ox = (ox + oy * a.k[0]) + oz * a.k[1];  // (k = 0: the same centre)
   }
   const int32_t ibeg = c.ibeg, ni = c.ni, total_j = c.total_j;
   const int32_t nbatch = (total_j + CAP - 1) / CAP;
@@ -1500,7 +1557,8 @@ __device__ __forceinline__ void cell_search(const SweepArgs<T>& a, const CellCtx
       const int32_t wr = PBC ? __builtin_amdgcn_readlane(c.wrap, sg) : 0x15;  // (compile-time: the open-box kernels
                                                                               // carry none of this)
       if constexpr (SCREEN) {
-        const T sx = (T)((wr & 3) - 1) * a.L[0], sy = (T)(((wr >> 2) & 3) - 1) * a.L[1], sz = (T)(((wr >> 4) & 3) - 1) * a.L[2];
+        T sx = 0, sy = 0, sz = 0;
+        if (PBC) face_shift(a, wr, sx, sy, sz);
         for (int32_t k = lane; k < len; k += WAVE) {
           Pos<T> v0 = a.sorted[src + k];
           if (PBC && wr != 0x15) v0.x = add_rn(v0.x, sx), v0.y = add_rn(v0.y, sy), v0.z = add_rn(v0.z, sz);
@@ -1515,7 +1573,8 @@ __device__ __forceinline__ void cell_search(const SweepArgs<T>& a, const CellCtx
         }
       } else {
         if (PBC && wr != 0x15) {
-          const T sx = (T)((wr & 3) - 1) * a.L[0], sy = (T)(((wr >> 2) & 3) - 1) * a.L[1], sz = (T)(((wr >> 4) & 3) - 1) * a.L[2];
+          T sx, sy, sz;
+          face_shift(a, wr, sx, sy, sz);
           for (int32_t k = lane; k < len; k += WAVE) {
             Pos<T> v0 = a.sorted[src + k];
             v0.x = add_rn(v0.x, sx), v0.y = add_rn(v0.y, sy), v0.z = add_rn(v0.z, sz);

@@ -33,7 +33,7 @@ template <typename T, bool PBC>
 __global__ void __launch_bounds__(SKIN_THREADS) k_skin_check(const T* __restrict__ q, const T* __restrict__ snap, int32_t stride,
                                                              int32_t n, double thr, double Lx, double Ly, double Lz, int32_t mask, int32_t force,
                                                              uint32_t* __restrict__ words, const uint32_t* status, int32_t* zero,
-                                                             int32_t nzero) {
+                                                             int32_t nzero, double xy, double xz, double yz) {
   __shared__ int32_t last_s;
   __shared__ uint32_t go_s;
   bool past = false;
@@ -42,7 +42,17 @@ __global__ void __launch_bounds__(SKIN_THREADS) k_skin_check(const T* __restrict
     load_xyz(q, stride, i, x, y, z);
     load_xyz(snap, stride, i, sx, sy, sz);
     double dx = (double)sub_rn(x, sx), dy = (double)sub_rn(y, sy), dz = (double)sub_rn(z, sz);
-    if (PBC) {  // (mask: the axes of the minimum image, nl_set_periodic_axes)
+    if (PBC && (xy != 0 || xz != 0 || yz != 0)) {  // triclinic (nl_set_box): z, y, x as LAMMPS' minimum_image, rint form
+      if (mask & 4) {
+        const double k = rint(dz / Lz);
+        dz = __dsub_rn(dz, __dmul_rn(k, Lz)), dy = __dsub_rn(dy, __dmul_rn(k, yz)), dx = __dsub_rn(dx, __dmul_rn(k, xz));
+      }
+      if (mask & 2) {
+        const double k = rint(dy / Ly);
+        dy = __dsub_rn(dy, __dmul_rn(k, Ly)), dx = __dsub_rn(dx, __dmul_rn(k, xy));
+      }
+      if (mask & 1) dx = __dsub_rn(dx, __dmul_rn(Lx, rint(dx / Lx)));
+    } else if (PBC) {  // (mask: the axes of the minimum image, nl_set_periodic_axes)
       if (mask & 1) dx = __dsub_rn(dx, __dmul_rn(Lx, rint(dx / Lx)));
       if (mask & 2) dy = __dsub_rn(dy, __dmul_rn(Ly, rint(dy / Ly)));
       if (mask & 4) dz = __dsub_rn(dz, __dmul_rn(Lz, rint(dz / Lz)));
@@ -97,12 +107,14 @@ int enqueue_update(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, bool f
   // binning clears histogram + meta words with a gated launch of its own)
   int32_t* zero = reinterpret_cast<int32_t*>(h->status);
   const int32_t nzero = p.binning == BINNING_TWO_PASS ? 32 + nrows : 0;
+  // (the box of this update's plan: a changed box forces the build, so with force == 0 it is the box of the snapshot's build)
+  const Box& b = p.box;
   if (h->pbc != 0)
-    hipLaunchKernelGGL((k_skin_check<T, true>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, h->L[0], h->L[1],
-                       h->L[2], h->pbc, force ? 1 : 0, h->skin_words, h->status, zero, nzero);
+    hipLaunchKernelGGL((k_skin_check<T, true>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, b.L[0], b.L[1],
+                       b.L[2], h->pbc, force ? 1 : 0, h->skin_words, h->status, zero, nzero, b.xy, b.xz, b.yz);
   else
-    hipLaunchKernelGGL((k_skin_check<T, false>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, h->L[0], h->L[1],
-                       h->L[2], 0, force ? 1 : 0, h->skin_words, h->status, zero, nzero);
+    hipLaunchKernelGGL((k_skin_check<T, false>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, b.L[0], b.L[1],
+                       b.L[2], 0, force ? 1 : 0, h->skin_words, h->status, zero, nzero, 0.0, 0.0, 0.0);
   h->gate = h->skin_words + SKIN_GO;
   int rc = enqueue_build<T>(h, a, p, s, nullptr);
   if (!rc) {
@@ -136,6 +148,7 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
   if (h->n_max <= 0 && n > 0) return fail(h, NL_ERR_STATE);
   if (n < 0 || n > h->n_max || (q_stride != 3 && q_stride != 4) || (!q_dev && n > 0)) return fail(h, NL_ERR_ARG);
   if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);  // (nl_set_exclusions, nl_set_type_cutoffs)
+  if (!tilt_mask_ok(h)) return fail(h, NL_ERR_STATE);  // (nl_set_box: a tilt needs both of its axes periodic)
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;

@@ -51,12 +51,13 @@ __device__ __forceinline__ int32_t type_frame(const TypeArgs<T>& a, int32_t i, T
   return faces;
 }
 
-// The shift of a partner with faces fj seen from a row with faces fi along axis d: -L where the row's cell is the first
-// and the partner's the last (the stencil reached it through the low face), +L the other way round.  (m >= 3: never both.)
-template <typename T> __device__ __forceinline__ T type_face_shift(int32_t fi, int32_t fj, int d, T L) {
+// The face a partner with faces fj is reached through from a row with faces fi along axis d: -1 where the row's cell is
+// the first and the partner's the last (the stencil reached it through the low face), +1 the other way round, else 0
+// (m >= 3: never both).  The partner is shifted by S(w) = w_a a + w_b b + w_c c (lattice_shift): -+L_d in an orthogonal box.
+__device__ __forceinline__ int32_t type_face_w(int32_t fi, int32_t fj, int d) {
   const int32_t lo_i = (fi >> (2 * d)) & 1, hi_i = (fi >> (2 * d + 1)) & 1;
   const int32_t lo_j = (fj >> (2 * d)) & 1, hi_j = (fj >> (2 * d + 1)) & 1;
-  return (lo_i & hi_j) ? -L : (hi_i & lo_j) ? L : (T)0;
+  return (lo_i & hi_j) ? -1 : (hi_i & lo_j) ? 1 : 0;
 }
 
 template <typename T> __device__ __forceinline__ T shfl_t(T v, int src) {
@@ -129,9 +130,11 @@ __device__ __forceinline__ bool type_keep(const TypeArgs<T>& a, const TypeRows<T
   const int32_t tf = __shfl(r.tf, lr, WAVE);
   if constexpr (PBC) {
     const int32_t fi = tf >> 8;
-    if (a.g.pbc & 1) xj = add_rn(xj, type_face_shift<T>(fi, fj, 0, a.g.L[0]));
-    if (a.g.pbc & 2) yj = add_rn(yj, type_face_shift<T>(fi, fj, 1, a.g.L[1]));
-    if (a.g.pbc & 4) zj = add_rn(zj, type_face_shift<T>(fi, fj, 2, a.g.L[2]));
+    T sw[3];  // the lattice vector of the faces, as the search staged the partner
+    lattice_shift(a.g.lat, (type_face_w(fi, fj, 0) + 1) | (type_face_w(fi, fj, 1) + 1) << 2 | (type_face_w(fi, fj, 2) + 1) << 4, sw);
+    if (a.g.pbc & 1) xj = add_rn(xj, sw[0]);
+    if (a.g.pbc & 2) yj = add_rn(yj, sw[1]);
+    if (a.g.pbc & 4) zj = add_rn(zj, sw[2]);
   }
   const T dx = sub_rn(xj, xi), dy = sub_rn(yj, yi), dz = sub_rn(zj, zi);
   const T r2 = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
@@ -279,11 +282,11 @@ int types_relabel(nl_handle_t h) {
 // ------------------------------------------------------------------------------------------ typed Lennard-Jones
 // k_lj with the parameters of the pair's types: lane t < ntypes holds eps4, sig2 and rcf2 of (t_row, t), an entry picks
 // them by its partner's type with ds_bpermute.  Everything else as k_lj (images, NaN on a failed build, half / full).
-template <typename T, bool HALF, typename OFF>
+template <typename T, bool HALF, typename OFF, bool TRI>
 __global__ void __launch_bounds__(256) k_lj_typed(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
                                                   const int32_t* __restrict__ list, int32_t n, const int32_t* __restrict__ types,
                                                   const T* __restrict__ par, T* __restrict__ f, T Lx, T Ly, T Lz,
-                                                  const uint32_t* __restrict__ status) {
+                                                  const uint32_t* __restrict__ status, T xy, T xz, T yz) {
   const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (row >= n) return;
   if (status && *status != 0u) {  // (uniform: every row of the launch takes this branch)
@@ -312,9 +315,7 @@ __global__ void __launch_bounds__(256) k_lj_typed(const T* __restrict__ q, int32
     T fx, fy, fz, pe;
     bool in;
     T dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    if (Lx > (T)0) dx = dx > (T)0.5 * Lx ? dx - Lx : dx < (T)-0.5 * Lx ? dx + Lx : dx;
-    if (Ly > (T)0) dy = dy > (T)0.5 * Ly ? dy - Ly : dy < (T)-0.5 * Ly ? dy + Ly : dy;
-    if (Lz > (T)0) dz = dz > (T)0.5 * Lz ? dz - Lz : dz < (T)-0.5 * Lz ? dz + Lz : dz;
+    lj_image<T, TRI>(dx, dy, dz, Lx, Ly, Lz, xy, xz, yz);
     lj_pair<T>(dx, dy, dz, eps4, sig2, rcf2, fx, fy, fz, pe, in);
     ax += fx, ay += fy, az += fz, ae += (T)0.5 * pe;
     if (HALF && in) {
@@ -342,16 +343,18 @@ int lj_typed_launch(nl_handle_t h, const void* q_dev, int32_t stride, void* f_de
   const int32_t n = h->n;
   if (n == 0) return NL_OK;
   const int32_t nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
-  const T Lx = (h->plan.pbc & 1) ? (T)h->L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)h->L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)h->L[2] : (T)0;
+  const Box& b = h->plan.box;  // (the build's box, as k_lj)
+  const T Lx = (h->plan.pbc & 1) ? (T)b.L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)b.L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)b.L[2] : (T)0;
+  const T xy = (T)b.xy, xz = (T)b.xz, yz = (T)b.yz;
   const T* par = static_cast<const T*>(h->lj_par);
-  if (h->plan.full) {
-    hipLaunchKernelGGL((k_lj_typed<T, false, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride,
-                       static_cast<const OFF*>(h->key_pointer), h->list, n, h->ty_types, par, static_cast<T*>(f_dev), Lx, Ly, Lz, status);
-  } else {
-    HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
-    hipLaunchKernelGGL((k_lj_typed<T, true, OFF>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev), stride,
-                       static_cast<const OFF*>(h->key_pointer), h->list, n, h->ty_types, par, static_cast<T*>(f_dev), Lx, Ly, Lz, status);
-  }
+  auto launch = [&](auto half, auto tri) {
+    hipLaunchKernelGGL((k_lj_typed<T, decltype(half)::value, OFF, decltype(tri)::value>), dim3(nbw), dim3(256), 0, s,
+                       static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer), h->list, n, h->ty_types, par,
+                       static_cast<T*>(f_dev), Lx, Ly, Lz, status, xy, xz, yz);
+  };
+  if (!h->plan.full) HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
+  if (h->plan.tilt) h->plan.full ? launch(std::false_type(), std::true_type()) : launch(std::true_type(), std::true_type());
+  else h->plan.full ? launch(std::false_type(), std::false_type()) : launch(std::true_type(), std::false_type());
   HIPCHK(h, hipGetLastError());
   return NL_OK;
 }

@@ -47,10 +47,11 @@ class NeighListGPU:
     Parameters follow neighlist_gpu.hpp:236-255: ``search_length`` (cut-off rc) and the box edges.  ``dtype``
     plays the role of the reference's compile-time ``Dtype``/``Vec`` choice (make_list.cu:6-12).  ``minimum_image``:
     False (the reference's open box), True (every axis periodic), or the periodic axes as in ``set_periodic(axes=)``.
+    ``tilt``: (xy, xz, yz) of a triclinic box (``set_box``); a tilt needs both of its axes periodic.
     """
 
     def __init__(self, search_length, Lx, Ly, Lz, dtype=torch.float32, device=None, full_list=False,
-                 minimum_image=False):
+                 minimum_image=False, tilt=None):
         if dtype not in (torch.float32, torch.float64):
             raise TypeError("dtype must be torch.float32 or torch.float64")
         self._lib = _lib.load()  # raises when the HIP extension is missing
@@ -65,11 +66,7 @@ class NeighListGPU:
                                 float(search_length), float(Lx), float(Ly), float(Lz), self.device.index or 0),
             "nl_create",
         )
-        mesh = (C.c_int32 * 3)()
-        ncell = C.c_int64()
-        check(self._lib.nl_get_mesh(self._h, C.byref(mesh), C.byref(ncell)))
-        self.mesh_size = tuple(mesh)
-        self.number_of_mesh = int(ncell.value)
+        self._read_mesh()
         self._n = 0
         self._n_rows = 0
         self.full_list = False
@@ -79,6 +76,8 @@ class NeighListGPU:
             self.set_full_list(True)
         if minimum_image:
             self.set_periodic(axes=minimum_image)
+        if tilt is not None and any(float(t) != 0.0 for t in tilt):
+            self.set_box(Lx, Ly, Lz, *(float(t) for t in tilt))
         self._q = None  # keeps the positions of an asynchronous build alive
         self.skin = 0.0
 
@@ -116,6 +115,27 @@ class NeighListGPU:
         check(self._lib.nl_set_periodic_axes(self._h, mask), "nl_set_periodic_axes")
         self.periodic_axes = tuple(bool(mask >> d & 1) for d in range(3))
         self.minimum_image = mask == 7
+
+    def set_box(self, Lx, Ly, Lz, xy=0.0, xz=0.0, yz=0.0):
+        """A new box for the next builds (nl_set_box): edge vectors a = (Lx, 0, 0), b = (xy, Ly, 0), c = (xz, yz, Lz)
+        (LAMMPS convention, origin 0).  Synchronous; a changed box drops the list and the next update builds.  Exclusion
+        and type tables, the skin and the periodic axes are kept; ``mesh_size`` follows the new box."""
+        check(self._lib.nl_set_box(self._h, float(Lx), float(Ly), float(Lz), float(xy), float(xz), float(yz)), "nl_set_box")
+        self._read_mesh()
+
+    @property
+    def box(self):
+        """(Lx, Ly, Lz, xy, xz, yz) of the next build (nl_get_box)."""
+        b = (C.c_double * 6)()
+        check(self._lib.nl_get_box(self._h, C.byref(b)), "nl_get_box")
+        return tuple(float(v) for v in b)
+
+    def _read_mesh(self):
+        mesh = (C.c_int32 * 3)()
+        ncell = C.c_int64()
+        check(self._lib.nl_get_mesh(self._h, C.byref(mesh), C.byref(ncell)))
+        self.mesh_size = tuple(mesh)
+        self.number_of_mesh = int(ncell.value)
 
     def periodic_mask(self):
         """The axis mask the next build uses (nl_get_periodic_axes): bit 0 = x, bit 1 = y, bit 2 = z."""
