@@ -262,7 +262,7 @@ int nl_synchronize(nl_handle_t h);
  *   nl_set_skin: skin >= 0 (default 0: every particle that moved at all triggers a build); forces the next update to build.
  *   nl_update_list: builds as nl_make_list does (the same list) exactly when
  *     (a) the host knows a reason: no list of an update to keep (first update; nl_initialize, nl_set_list_kind,
- *         nl_set_periodic(_axes), nl_set_offset_width, nl_set_capacity, nl_set_skin or nl_resort called, or a build other than
+ *         nl_set_periodic(_axes), nl_set_offset_width, nl_set_capacity, nl_set_skin, nl_set_pair_images (a changed value) or nl_resort called, or a build other than
  *         an update's run, since; the host has seen the last build fail) or q_dev, q_stride or n differ from that build's;
  *     (b) the status word of the last performed build is not OK (an asynchronous build that overflowed its capacity);
  *     (c) for some particle i < n, with d = q_now - snap per component in the position type (round to nearest, no
@@ -348,6 +348,51 @@ int nl_get_exclusions(nl_handle_t h, const int32_t** offsets_dev, const int32_t*
 #define NL_MAX_TYPES 32
 int nl_set_type_cutoffs(nl_handle_t h, const int32_t* types_dev, int32_t n, int32_t ntypes, const double* rc_host);
 int nl_get_types(nl_handle_t h, const int32_t** types_dev, int32_t* n, int32_t* ntypes);
+
+/* ---------------------------------------------------------------------------------------------- pair images */
+
+/* The periodic image of every entry of the list (no reference counterpart: its box is open), as ASE / matscipy
+ * neighbour_list("ijS"), the edge_index + shifts tensors of machine-learned potentials and LAMMPS image flags report it.
+ *   The rule: for an entry (row i, partner j) of the list the getters return, the image is the integer triple
+ *       s = n_j + w_ij - n_i
+ *     n_p = the wraps of particle p, as the binning decides them from the input coordinate (nl_set_box: n_p[d] in
+ *       {-1, 0, +1} on an axis of the nl_set_periodic_axes mask, 0 on an open axis);
+ *     w_ij[d] = -1 where i's cell is the first along d and j's the last, +1 the other way round, else 0 (axes of the mask
+ *       only): the face through which the search staged j.
+ *     So |s[d]| <= 3, and s[d] = 0 on an open axis and in the open box (mask 0).
+ *     Meaning: q_j + S(s) - q_i, S(s) = s_a a + s_b b + s_c c over the build's box, is the displacement at which the search
+ *     found the pair; with m_d >= 3 it is the only image within rc.  The two rows of a full list give s_ji = -s_ij exactly
+ *     (both terms are antisymmetric).
+ *   Storage: 4 bytes per entry, int8 {s_a, s_b, s_c, 0}, at the index of the entry in sorted_list / list (both offset widths).
+ *   nl_set_pair_images: off by default.  Synchronous, as the other setters: finishes a pending build; a changed value drops
+ *     the list, makes the next nl_update_list build and captures graphs again; the same value again changes nothing.  While on, the handle holds one more buffer of
+ *     capacity x 4 bytes (and 2 bytes per particle), allocated, estimated and grown wherever the list is; NL_ERR_NOMEM
+ *     leaves the flag off.  Slab builds (a slab, ids, the _begin / _finish pair) and distributed builds are NL_ERR_STATE
+ *     while it is on.  Builds with the flag on run one more stage at their very end, behind the filter stage of an
+ *     exclusion or type table: the images describe the filtered list.  Builds with the flag off launch nothing of this.
+ *   nl_get_pair_images: the images of the last build, *nentries of them (npairs / nentries of nl_get_*_csr); synchronises;
+ *     NL_ERR_STATE when the flag is off or there is no build.  The pointer is valid until the next build.
+ *   nl_update_list while the flag is on: rule (c) is taken WITHOUT the fold to the minimum image (the open-box form, on
+ *     every axis).  A particle that the caller wrapped back into the box has moved by a box vector, which is longer than
+ *     skin / 2: the update builds, and the images are computed again.  Images are therefore valid for the positions of the
+ *     build and for any continuation of them within the skin; a list with the flag on never outlives a re-wrap.  A skipped
+ *     update leaves the list and the images as they are.  With the flag off rule (c) is unchanged.
+ *   nl_pair_vectors: the consumer.  out_dev[k] = {dx, dy, dz, r2} in the position type T for every entry k of the last
+ *     build, from q_dev (the build's positions, or positions moved within the skin; same dtype, q_stride 3 or 4):
+ *     S(s) in double as ((s_a Lx + s_b xy) + s_c xz, s_b Ly + s_c yz, s_c Lz), each component rounded to T once;
+ *     d_c = (S_c == 0 ? q_j[c] : q_j[c] + (T)S_c) - q_i[c], one rounding per operation; r2 = (dx*dx + dy*dy) + dz*dz without
+ *     FMA.  The sign is r_j - r_i (the ASE convention).  This r2 is NOT the r2 the search tested: the search rounds the wrap
+ *     and the face shift separately, so the two may differ in the last place, and no claim r2 <= rc2 is made.  Needs the
+ *     flag on, a single-device build and ids that index q (else NL_ERR_STATE); waits for the build first.
+ *   nl_pair_vectors_enqueue: without the wait, stream-ordered behind the last nl_update_list on the same stream (or behind a
+ *     build that has been synchronised), with the rules of nl_lj_forces_enqueue: a pending plain asynchronous build is
+ *     NL_ERR_STATE; where the build's status word says the list is invalid the vectors are NaN and the error surfaces at
+ *     the next nl_synchronize.  out_dev must hold the list's capacity (nl_set_capacity), since the host does not know the
+ *     number of entries yet.  Copies nothing from the host: it can be captured. */
+int nl_set_pair_images(nl_handle_t h, int on);
+int nl_get_pair_images(nl_handle_t h, const int8_t** images_dev, int64_t* nentries);
+int nl_pair_vectors(nl_handle_t h, const void* q_dev, int32_t q_stride, void* out_dev, void* stream);
+int nl_pair_vectors_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------- results */
 

@@ -65,6 +65,10 @@ PROTOTYPES = {
     "nl_set_lj_type_params": (C.c_int, [_P, _I32, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
     "nl_lj_forces_typed": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_lj_forces_typed_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_set_pair_images": (C.c_int, [_P, C.c_int]),
+    "nl_get_pair_images": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64)]),
+    "nl_pair_vectors": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_pair_vectors_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_get_full_transposed": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I32)]),
     "nl_number_of_pairs": (C.c_int, [_P, C.POINTER(_I64)]),
     "nl_get_mesh": (C.c_int, [_P, C.POINTER(_I32 * 3), C.POINTER(_I64)]),

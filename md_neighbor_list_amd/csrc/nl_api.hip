@@ -82,13 +82,14 @@ struct BuildPlan {
   bool full = false;    // full list (both directions), nl_set_list_kind
   bool wide = false;    // key_pointer / base_sorted hold int64 (the list may exceed INT32_MAX entries)
   bool filter = false;  // the filter stage runs: an exclusion table (nl_exclude.inc), a type table (nl_types.inc) or both
+  bool images = false;  // the image stage runs behind it (nl_set_pair_images, nl_images.inc)
   int32_t pbc = 0;      // axes of the minimum image (nl_set_periodic_axes)
   int32_t idc = 0;      // SEARCH_MASKS with id classes (k_sweep_class_f32, k_fill_masks<IDC>): C = 2 or 4 classes, 0 = off
   int32_t id_shift = 0; // class of an id: id >> id_shift
   Box box = {{0, 0, 0}, 0, 0, 0};  // the box of the build (nl_set_box): what its consumers (k_lj, the skin check) fold with
   int32_t tilt = 0;     // box.xy, box.xz or box.yz is not 0: binning and search in sheared coordinates
   auto tie() const {
-    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, pbc, idc, id_shift,
+    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, images, pbc, idc, id_shift,
                     box.L[0], box.L[1], box.L[2], box.xy, box.xz, box.yz, tilt);
   }
   bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
@@ -245,6 +246,13 @@ struct nl_handle_s {
   void* lj_par = nullptr;          // nl_set_lj_type_params: [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2 in T
   int32_t lj_ntypes = 0;
   double lj_rcf[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // rc_force_ab, [lj_ntypes][lj_ntypes]
+
+  // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
+  bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
+  uint32_t* images = nullptr;      // [capacity] int8 {s_a, s_b, s_c, 0} per entry, at the entry's index in `list`
+  uint16_t* img_code = nullptr;    // [n_max] faces and wraps of every particle (k_image_codes)
+  uint32_t* img_words = nullptr;   // [wrapped, ticket, pad, pad] of the stage (IMG_* in nl_images.inc); zero between builds
+  int64_t img_capacity = -1, img_rows = -1;  // entries / particles the two buffers hold
 };
 
 namespace {
@@ -273,6 +281,10 @@ void filter_release(nl_handle_t h);
 // nl_types.inc
 int launch_filter(nl_handle_t h, int32_t n_rows, hipStream_t s);
 int types_relabel(nl_handle_t h);
+// nl_images.inc
+int images_reserve(nl_handle_t h);
+bool images_ready(nl_handle_t h);
+int launch_images(nl_handle_t h, int32_t n_rows, hipStream_t s);
 
 // A table that filters builds is set (exclusions, types or both): builds run the filter stage.
 bool filter_tables(nl_handle_t h) { return h->ex_ids || h->ty_types; }
@@ -664,6 +676,7 @@ template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, in
   p.box = box_of(h);
   p.tilt = has_tilt(h) ? 1 : 0;
   p.filter = filter_tables(h);
+  p.images = h->pair_images;
   // 64-bit list offsets as soon as the list this handle can hold exceeds what an int32 key_pointer can address
   // (the reference's own limit, neighlist_cpu.hpp:15,29); nl_set_offset_width overrides.
   p.wide = h->offset_width == 64 || (h->offset_width == 0 && h->capacity > 2147483647LL);
@@ -784,6 +797,8 @@ int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStre
   if (p.filter && ((h->ex_ids && a.n != h->ex_n) || (h->ty_types && a.n != h->ty_n) || a.slab || a.gid || a.dyn))
     return fail(h, NL_ERR_STATE);  // (checked by the entry points)
   if (p.filter && !excl_ready(h)) return fail(h, NL_ERR_NOMEM);  // (the search would write through a missing buffer)
+  if (p.images && (a.slab || a.gid || a.dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
+  if (p.images && !images_ready(h)) return fail(h, NL_ERR_NOMEM);
   if (part != PART_ALL && !p.split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
     if (part == PART_BEGIN) return NL_OK;
     part = PART_ALL;
@@ -877,6 +892,9 @@ int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStre
   // the filter tables: the unfiltered list compacted into the getters' buffers (counted in the FILL stage)
   if (p.filter)
     if (int rc = launch_filter(h, a.n_rows, s)) return rc;
+  // the image of every entry of the list the getters return (nl_set_pair_images; counted in the FILL stage)
+  if (p.images)
+    if (int rc = launch_images(h, a.n_rows, s)) return rc;
   if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_TOTAL], s));
   HIPCHK(h, hipGetLastError());
   return NL_OK;
@@ -909,7 +927,8 @@ int estimate_capacity(nl_handle_t h) {
     if (int rc = dev_alloc(h, &h->list, 4 * (size_t)want)) return rc;
     h->capacity = want;
   }
-  return excl_reserve(h);
+  if (int rc = excl_reserve(h)) return rc;
+  return images_reserve(h);
 }
 
 int grow_list(nl_handle_t h, int64_t need) {
@@ -922,7 +941,8 @@ int grow_list(nl_handle_t h, int64_t need) {
     return rc;
   }
   h->capacity = cap;
-  return excl_reserve(h);
+  if (int rc = excl_reserve(h)) return rc;
+  return images_reserve(h);
 }
 
 // The last build once more, from its own arguments, with the two-pass binning and every launch of its path; waits for it.
@@ -973,6 +993,7 @@ int finish(nl_handle_t h, bool may_grow) {
     else
       launch_sweep<double>(h, MODE_FILL, h->last_stream);
     if (h->plan.filter) rc = launch_filter(h, h->n_rows, h->last_stream);  // (the refilled list is the unfiltered one)
+    if (!rc && h->plan.images) rc = launch_images(h, h->n_rows, h->last_stream);  // (into the grown buffer)
     if (!rc) rc = enqueue_result_copy(h, h->last_stream);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
@@ -1224,7 +1245,7 @@ int nl_destroy(nl_handle_t h) {
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
   void* bufs[] = {h->snap, h->skin_words, h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
                   h->cell_start, h->cls_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor,
-                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre, h->ty_types, h->ty_rc2, h->lj_par, h->lat_dev};
+                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre, h->ty_types, h->ty_rc2, h->lj_par, h->lat_dev, h->images, h->img_code, h->img_words};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (h->host) (void)hipHostFree(h->host);
@@ -1289,7 +1310,8 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   h->n_max = n_max;
   if ((rc = estimate_capacity(h))) return rc;
   h->t_valid = false;
-  return excl_reserve(h);  // (the pre-exclusion offsets follow n_max)
+  if ((rc = excl_reserve(h))) return rc;  // (the pre-exclusion offsets follow n_max)
+  return images_reserve(h);               // (and so do the particle codes of the image stage)
 }
 
 int nl_set_periodic_axes(nl_handle_t h, int mask) {
@@ -1369,6 +1391,7 @@ int nl_set_box(nl_handle_t h, double Lx, double Ly, double Lz, double xy, double
       }
     }
     if (int rc = excl_reserve(h)) return restore(rc);  // (the pre-exclusion list follows the capacity)
+    if (int rc = images_reserve(h)) return restore(rc);  // (and so do the images)
   }
   double lat[LATTICE_CODES * 3];
   lattice_table(box_of(h), lat);
@@ -1428,7 +1451,8 @@ int nl_set_capacity(nl_handle_t h, int64_t max_pairs) {
   }
   h->capacity = max_pairs;
   h->capacity_user = true;
-  return excl_reserve(h);
+  if ((rc = excl_reserve(h))) return rc;
+  return images_reserve(h);
 }
 
 namespace {
@@ -1468,10 +1492,13 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
   // nl_set_box: slab and distributed builds need the box of nl_create, and a tilt needs both of its axes periodic
   if (box_changed(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
   if (!tilt_mask_ok(h)) return fail(h, NL_ERR_STATE);
+  // nl_set_pair_images: the images are those of whole single-device builds, whose ids index the positions
+  if (h->pair_images && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
   if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (filter_tables(h))  // (again, if an allocation failed since the table was set)
     if (int rc = excl_reserve(h)) return rc;
+  if (int rc = images_reserve(h)) return rc;  // (the same for the images; nothing with the flag off)
   if (h->pending) {
     // back-to-back asynchronous builds (the reference's timing loop): errors of the previous one are dropped,
     // exactly like its results; stream order keeps the buffers consistent when the stream is the same.
@@ -1830,3 +1857,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_dist.inc"
 #include "nl_exclude.inc"
 #include "nl_types.inc"
+#include "nl_images.inc"

@@ -101,7 +101,7 @@ __device__ __forceinline__ double sub_rn(double a, double b) { return __dsub_rn(
 // S(n) of the wraps n_d of the periodic axes (one decision, from the input coordinate).
 template <typename T>
 __device__ __forceinline__ int32_t local_cell(const Grid<T>& g, T x, T y, T z, int32_t* lz_out,
-                                              int32_t* row_out = nullptr, T* shift_out = nullptr) {
+                                              int32_t* row_out = nullptr, T* shift_out = nullptr, int32_t* wrap_out = nullptr) {
   T xs = x, ys = y;
   if (g.tilt) xs = sub_rn(sub_rn(x, mul_rn(y, g.k[0])), mul_rn(z, g.k[1])), ys = sub_rn(y, mul_rn(z, g.k[2]));
   const T t[3] = {mul_rn(xs, g.ims[0]), mul_rn(ys, g.ims[1]), mul_rn(z, g.ims[2])};
@@ -134,6 +134,7 @@ __device__ __forceinline__ int32_t local_cell(const Grid<T>& g, T x, T y, T z, i
     if (acting >= g.m[2]) sh[2] += g.L[2];
   }
   if (shift_out) shift_out[0] = sh[0], shift_out[1] = sh[1], shift_out[2] = sh[2];
+  if (wrap_out) wrap_out[0] = wrap[0], wrap_out[1] = wrap[1], wrap_out[2] = wrap[2];  // (the wraps n of nl_set_pair_images)
   *lz_out = lz;
   if (row_out) *row_out = idx[1] + lz * g.m[1];  // the row of x-cells the particle lies in
   return idx[0] + (idx[1] + lz * g.m[1]) * g.m[0];

@@ -109,7 +109,8 @@ int enqueue_update(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, bool f
   const int32_t nzero = p.binning == BINNING_TWO_PASS ? 32 + nrows : 0;
   // (the box of this update's plan: a changed box forces the build, so with force == 0 it is the box of the snapshot's build)
   const Box& b = p.box;
-  if (h->pbc != 0)
+  // (nl_set_pair_images: no fold -- a particle the caller re-wrapped has moved by a box vector, and the update builds)
+  if (h->pbc != 0 && !p.images)
     hipLaunchKernelGGL((k_skin_check<T, true>), dim3(grid), dim3(SKIN_THREADS), 0, s, q, snap, stride, n, thr, b.L[0], b.L[1],
                        b.L[2], h->pbc, force ? 1 : 0, h->skin_words, h->status, zero, nzero, b.xy, b.xz, b.yz);
   else
@@ -156,6 +157,8 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
   const bool capturing = cap != hipStreamCaptureStatusNone;
   if (filter_tables(h) && !capturing)  // (again, if an allocation failed since the table was set)
     if (int rc = excl_reserve(h)) return rc;
+  if (!capturing)
+    if (int rc = images_reserve(h)) return rc;
   // (a): what forces a build before any particle is looked at -- no list of an update to keep (a setter, nl_resort or
   // another kind of build since, the host has seen the last build fail), or other positions
   const bool force = !h->upd_valid || q_dev != h->upd_q || q_stride != h->upd_stride || n != h->upd_n || (!h->pending && !h->built);

@@ -36,7 +36,7 @@ def _as_tensor(ptr, shape, typestr, owner, device):
     for s in shape:
         n *= int(s)
     if n == 0 or not ptr:
-        dt = {"<i4": torch.int32, "<i8": torch.int64, "<f4": torch.float32, "<f8": torch.float64}[typestr]
+        dt = {"|i1": torch.int8, "<i4": torch.int32, "<i8": torch.int64, "<f4": torch.float32, "<f8": torch.float64}[typestr]
         return torch.empty(tuple(int(s) for s in shape), dtype=dt, device=device)
     return torch.as_tensor(_DevView(ptr, shape, typestr, owner), device=device)
 
@@ -284,6 +284,69 @@ class NeighListGPU:
         check(fn(self._h, q.data_ptr(), q.shape[1], f.data_ptr(), stream),
               "nl_lj_forces_typed" if wait else "nl_lj_forces_typed_enqueue")
         return f
+
+    # ------------------------------------------------------------------ pair images
+    def set_pair_images(self, on=True):
+        """Builds also report the periodic image of every entry (nl_set_pair_images): the integer triple s with
+        q_j + s_a a + s_b b + s_c c - q_i the displacement at which the search found the pair -- the ``S`` of ASE's
+        ``neighbour_list("ijS")``, the ``shifts`` of an ``edge_index`` consumer.  Synchronous; a changed value drops the list.
+        While on, update() takes its skin check without the minimum-image fold: re-wrapping a particle into the box rebuilds."""
+        check(self._lib.nl_set_pair_images(self._h, 1 if on else 0), "nl_set_pair_images")
+
+    def pair_images(self):
+        """int8 ``[P, 3]`` images of the entries of the last build (nl_get_pair_images), entry k at the index of
+        ``sorted_list()[k]`` / ``full_csr()[1][k]``: a view of the ``[P, 4]`` buffer, valid until the next build."""
+        ptr, ne = C.c_void_p(), C.c_int64()
+        check(self._lib.nl_get_pair_images(self._h, C.byref(ptr), C.byref(ne)), "nl_get_pair_images")
+        return _as_tensor(ptr.value, (ne.value, 4), "|i1", self, self.device)[:, :3]
+
+    def pair_vectors(self, q, out=None, wait=True):
+        """``[P, 4] = {dx, dy, dz, r2}`` of every entry of the last build at its image, r_j - r_i (nl_pair_vectors), from
+        ``q``: the build's positions or positions moved within the skin.  ``wait=False`` (nl_pair_vectors_enqueue): no
+        wait for the build, stream-ordered behind the last update(); ``out`` is then required and must hold the list's
+        capacity, and a list whose build failed gives NaN.  ``out``: a contiguous ``[>= P, 4]`` tensor to write into."""
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        entries = None
+        if wait:  # the count the library reports with the images (NL_ERR_STATE with the flag off or without a build)
+            ne = C.c_int64()
+            check(self._lib.nl_get_pair_images(self._h, None, C.byref(ne)), "nl_get_pair_images")
+            entries = int(ne.value)
+        if out is None:
+            if not wait:
+                raise ValueError("pair_vectors(wait=False) needs out= with room for the list's capacity")
+            out = torch.empty((entries, 4), dtype=self.dtype, device=self.device)
+        if out.dim() != 2 or out.shape[1] != 4 or out.dtype != self.dtype or not out.is_contiguous() or out.device.type != "cuda":
+            raise TypeError("out must be a contiguous (P, 4) device tensor of the list's dtype")
+        if wait and out.shape[0] < entries:
+            raise ValueError("out is shorter than the list")
+        target = out
+        if out.numel() == 0:  # (torch gives an empty tensor no address: the call still runs, and reports its errors)
+            if not wait:
+                raise ValueError("pair_vectors(wait=False) needs out= with room for the list's capacity")
+            target = torch.empty((1, 4), dtype=self.dtype, device=self.device)  # (an empty list: nothing is written)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        fn = self._lib.nl_pair_vectors if wait else self._lib.nl_pair_vectors_enqueue
+        check(fn(self._h, q.data_ptr(), q.shape[1], target.data_ptr(), stream), "nl_pair_vectors" if wait else "nl_pair_vectors_enqueue")
+        return out
+
+    def list_entries(self):
+        """Entries of the last list as the library counts them (npairs of nl_get_half_csr, nentries of nl_get_full_csr;
+        waits for the build).  Not 2 x number_of_pairs: the two rows of a full list decide a pair on their own and may
+        differ within one ulp of the cut-off across a periodic face, so a full list can hold an odd number of entries."""
+        return (self._full(0) if self.full_list else self._half(0))[3]
+
+    def edge_index(self):
+        """``[2, P]`` int64 (row, partner) of every entry of the last build, in the order of pair_images() and
+        pair_vectors(): the ``edge_index`` of a PyTorch consumer.  Plumbing over the CSR; a copy."""
+        if self.full_list:
+            _kp, lst, cnt = self.full_csr(64)
+        else:
+            lst, cnt = self.sorted_list(), self.half_number_of_partners()
+        rows = torch.repeat_interleave(torch.arange(self._n_rows, dtype=torch.int64, device=self.device), cnt.to(torch.int64),
+                                       output_size=int(lst.shape[0]))
+        return torch.stack([rows, lst.to(torch.int64)])
 
     GID_IN_W = "w"  # MakeNeighListSlab(gid=GID_IN_W): ids are stored in q[:, 3] as integer bit patterns (NL_GID_IN_W)
 
