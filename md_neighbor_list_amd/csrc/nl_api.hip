@@ -13,6 +13,7 @@
 #include <tuple>
 
 #include "nl_kernels.hpp"
+#include "nl_stage.hpp"
 
 using namespace nl;
 
@@ -273,18 +274,35 @@ int fail(nl_handle_t h, int code) {
 }
 
 // nl_exclude.inc
-int excl_reserve(nl_handle_t h);
-bool excl_ready(nl_handle_t h);
 int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s);
 int excl_relabel(nl_handle_t h);
-void filter_release(nl_handle_t h);
 // nl_types.inc
 int launch_filter(nl_handle_t h, int32_t n_rows, hipStream_t s);
 int types_relabel(nl_handle_t h);
 // nl_images.inc
-int images_reserve(nl_handle_t h);
-bool images_ready(nl_handle_t h);
 int launch_images(nl_handle_t h, int32_t n_rows, hipStream_t s);
+
+// f(T(), OFF()) with the position type and the offset type of the handle's build.
+template <typename F> int dispatch_t_off(nl_handle_t h, F&& f) {
+  const bool f32 = h->dtype == NL_F32;
+  if (h->plan.wide) return f32 ? f(float(), int64_t()) : f(double(), int64_t());
+  return f32 ? f(float(), int32_t()) : f(double(), int32_t());
+}
+
+// What every consumer of the list needs first (nl_lj_forces*, nl_pair_vectors*).  Synchronous: the list must be complete
+// (and its build must have succeeded).  enqueue: stream-ordered behind the build instead -- a build, or one the host has
+// not seen fail; a pending one must be an update's (a plain asynchronous build may still need finish() to complete its
+// list) and enqueued on this stream.  Either way the list's ids must index q.
+int consumer_ready(nl_handle_t h, hipStream_t s, bool enqueue) {
+  if (enqueue) {
+    if (!h->pending && !h->built) return fail(h, NL_ERR_STATE);
+    if (h->pending && (!h->last_update || s != h->last_stream)) return fail(h, NL_ERR_STATE);
+  } else if (int rc = nl_synchronize(h)) {
+    return rc;
+  }
+  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);
+  return NL_OK;
+}
 
 // A table that filters builds is set (exclusions, types or both): builds run the filter stage.
 bool filter_tables(nl_handle_t h) { return h->ex_ids || h->ty_types; }
@@ -305,6 +323,68 @@ template <typename P> int dev_alloc(nl_handle_t h, P** p, size_t bytes) {
     return fail(h, e == hipErrorOutOfMemory ? NL_ERR_NOMEM : NL_ERR_HIP);
   }
   return NL_OK;
+}
+
+// ---- the stages' buffers, which follow n_max and the list's capacity
+constexpr int IMG_WORDS = 4;  // words of h->img_words (IMG_* in nl_images.inc)
+
+// A buffer of `bytes` for `want` items, where it holds fewer; *held is -1 while the allocation is in flight (an error
+// leaves it there: the buffer is not ready).
+template <typename P> int follow(nl_handle_t h, P** p, int64_t* held, int64_t want, size_t bytes) {
+  if (*held >= want) return NL_OK;
+  *held = -1;
+  if (int rc = dev_alloc(h, p, bytes)) return rc;
+  *held = want;
+  return NL_OK;
+}
+
+// The unfiltered offsets and list while a table filters builds (exclusions, types or both: one offset array, one list
+// capacity); nothing without one.
+int filter_reserve(nl_handle_t h) {
+  if (!filter_tables(h)) return NL_OK;
+  if (int rc = follow(h, &h->kp_pre, &h->pre_rows, h->n_max, 8 * ((size_t)h->n_max + 32))) return rc;
+  return follow(h, &h->list_pre, &h->pre_capacity, h->capacity, 4 * ((size_t)h->capacity + 16));
+}
+
+// The image stage's buffers while the flag is on: one word per entry of the list's capacity, one code per particle of n_max.
+int images_reserve(nl_handle_t h) {
+  if (!h->pair_images) return NL_OK;
+  if (!h->img_words) {
+    if (int rc = dev_alloc(h, &h->img_words, sizeof(uint32_t) * IMG_WORDS)) return rc;
+    HIPCHK(h, hipMemset(h->img_words, 0, sizeof(uint32_t) * IMG_WORDS));
+  }
+  if (int rc = follow(h, &h->img_code, &h->img_rows, h->n_max, 2 * ((size_t)h->n_max + 64))) return rc;
+  return follow(h, &h->images, &h->img_capacity, h->capacity, 4 * ((size_t)h->capacity + 16));
+}
+
+// Both: wherever n_max or the capacity changes, and again in front of a build (if an allocation failed since).
+int stage_reserve(nl_handle_t h) {
+  if (int rc = filter_reserve(h)) return rc;
+  return images_reserve(h);
+}
+
+// The buffers that plan p's stages write through are there.
+bool stage_ready(nl_handle_t h, const BuildPlan& p) {
+  if (p.filter && !(h->kp_pre && h->list_pre && h->pre_rows >= (int64_t)h->n_max && h->pre_capacity >= h->capacity)) return false;
+  if (p.images && !(h->images && h->img_code && h->img_words && h->img_rows >= (int64_t)h->n_max && h->img_capacity >= h->capacity))
+    return false;
+  return true;
+}
+
+// The unfiltered buffers, once no table needs them.
+void filter_release(nl_handle_t h) {
+  for (void* b : {h->kp_pre, (void*)h->list_pre})
+    if (b) (void)hipFree(b);
+  h->kp_pre = nullptr, h->list_pre = nullptr;
+  h->pre_capacity = h->pre_rows = -1;
+}
+
+void images_release(nl_handle_t h) {
+  for (void* b : {(void*)h->images, (void*)h->img_code, (void*)h->img_words})
+    if (b) (void)hipFree(b);
+  h->images = nullptr, h->img_code = nullptr, h->img_words = nullptr;
+  h->img_capacity = h->img_rows = -1;
+  h->buffers_epoch++;
 }
 
 // The per-cell and per-row buffers for the handle's mesh (h->m, h->ncell) and n particles: (re)allocated where the mesh needs
@@ -428,6 +508,22 @@ int launch_scan(nl_handle_t h, const int32_t* in, int64_t n, OFF* out, int64_t* 
   if (nb > h->scan_blocks) return fail(h, NL_ERR_ARG);  // (sized for max(n_max, cells) in nl_reserve)
   hipLaunchKernelGGL(k_scan_chained<OFF>, dim3(nb), dim3(SCAN_THREADS), 0, s, in, n, h->scan_look, h->scan_blocks, total, out,
                      h->status, total_split, h->gate);
+  return NL_OK;
+}
+
+// Blocks of a stage kernel whose waves each take one of `units` (rows, or chunks of STAGE_ROWS rows).
+int32_t stage_grid(nl_handle_t h, int32_t units) { return std::max(1, std::min((units + 3) / 4, 16 * h->num_cus)); }
+
+// The filter stage on stream s: `count` fills h->count per row, the row scan turns that into key_pointer (its total into
+// the meta words, META_KEPT), `compact` copies the kept entries into h->list.  a: the stage's arguments.
+template <typename OFF, typename A>
+int launch_passes(nl_handle_t h, int32_t n_rows, int32_t units, hipStream_t s, const A& a, void (*count)(A, int32_t*),
+                  void (*compact)(A, const OFF*, int32_t*)) {
+  const dim3 grid(stage_grid(h, units));
+  if (n_rows > 0) hipLaunchKernelGGL(count, grid, dim3(STAGE_THREADS), 0, s, a, h->count);
+  if (int rc = launch_scan(h, h->count, n_rows, static_cast<OFF*>(h->key_pointer), h->totals + 2, s, h->status + META_KEPT)) return rc;
+  if (n_rows > 0) hipLaunchKernelGGL(compact, grid, dim3(STAGE_THREADS), 0, s, a, static_cast<const OFF*>(h->key_pointer), h->list);
+  HIPCHK(h, hipGetLastError());
   return NL_OK;
 }
 
@@ -796,9 +892,8 @@ int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStre
   adopt_build(h, a, p);
   if (p.filter && ((h->ex_ids && a.n != h->ex_n) || (h->ty_types && a.n != h->ty_n) || a.slab || a.gid || a.dyn))
     return fail(h, NL_ERR_STATE);  // (checked by the entry points)
-  if (p.filter && !excl_ready(h)) return fail(h, NL_ERR_NOMEM);  // (the search would write through a missing buffer)
   if (p.images && (a.slab || a.gid || a.dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
-  if (p.images && !images_ready(h)) return fail(h, NL_ERR_NOMEM);
+  if (!stage_ready(h, p)) return fail(h, NL_ERR_NOMEM);  // (the search or a stage would write through a missing buffer)
   if (part != PART_ALL && !p.split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
     if (part == PART_BEGIN) return NL_OK;
     part = PART_ALL;
@@ -927,8 +1022,7 @@ int estimate_capacity(nl_handle_t h) {
     if (int rc = dev_alloc(h, &h->list, 4 * (size_t)want)) return rc;
     h->capacity = want;
   }
-  if (int rc = excl_reserve(h)) return rc;
-  return images_reserve(h);
+  return stage_reserve(h);
 }
 
 int grow_list(nl_handle_t h, int64_t need) {
@@ -941,8 +1035,7 @@ int grow_list(nl_handle_t h, int64_t need) {
     return rc;
   }
   h->capacity = cap;
-  if (int rc = excl_reserve(h)) return rc;
-  return images_reserve(h);
+  return stage_reserve(h);
 }
 
 // The last build once more, from its own arguments, with the two-pass binning and every launch of its path; waits for it.
@@ -1310,8 +1403,7 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   h->n_max = n_max;
   if ((rc = estimate_capacity(h))) return rc;
   h->t_valid = false;
-  if ((rc = excl_reserve(h))) return rc;  // (the pre-exclusion offsets follow n_max)
-  return images_reserve(h);               // (and so do the particle codes of the image stage)
+  return stage_reserve(h);  // (the unfiltered offsets and the particle codes follow n_max)
 }
 
 int nl_set_periodic_axes(nl_handle_t h, int mask) {
@@ -1390,8 +1482,7 @@ int nl_set_box(nl_handle_t h, double Lx, double Ly, double Lz, double xy, double
         h->capacity = want;
       }
     }
-    if (int rc = excl_reserve(h)) return restore(rc);  // (the pre-exclusion list follows the capacity)
-    if (int rc = images_reserve(h)) return restore(rc);  // (and so do the images)
+    if (int rc = stage_reserve(h)) return restore(rc);  // (the unfiltered list and the images follow the capacity)
   }
   double lat[LATTICE_CODES * 3];
   lattice_table(box_of(h), lat);
@@ -1451,8 +1542,7 @@ int nl_set_capacity(nl_handle_t h, int64_t max_pairs) {
   }
   h->capacity = max_pairs;
   h->capacity_user = true;
-  if ((rc = excl_reserve(h))) return rc;
-  return images_reserve(h);
+  return stage_reserve(h);
 }
 
 namespace {
@@ -1496,9 +1586,7 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
   if (h->pair_images && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
   if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
-  if (filter_tables(h))  // (again, if an allocation failed since the table was set)
-    if (int rc = excl_reserve(h)) return rc;
-  if (int rc = images_reserve(h)) return rc;  // (the same for the images; nothing with the flag off)
+  if (int rc = stage_reserve(h)) return rc;  // (again, if an allocation failed since a table or the flag was set)
   if (h->pending) {
     // back-to-back asynchronous builds (the reference's timing loop): errors of the previous one are dropped,
     // exactly like its results; stream order keeps the buffers consistent when the stream is the same.

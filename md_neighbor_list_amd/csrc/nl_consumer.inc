@@ -3,6 +3,8 @@
 // uses it, make_list.cpp:135,138-140); here it answers which list kind the builder should be optimised for.
 //   full list: row i gathers its partners and writes f[i] once -- no atomics, every pair evaluated twice;
 //   half list: every pair once, the reaction goes to f[j] with floating-point atomics.
+// nl_lj_forces takes one epsilon, sigma and rc_force; nl_lj_forces_typed takes them per pair of types (nl_types.inc sets the
+// tables).  One kernel body (lj_row) and one launch serve both.
 // Included at the end of nl_api.hip.
 
 namespace {
@@ -45,19 +47,24 @@ __device__ __forceinline__ void lj_image(T& dx, T& dy, T& dz, T Lx, T Ly, T Lz, 
   }
 }
 
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
+// Where a pair's parameters come from: the launch's scalars, or a table over the types of the pair (nl_set_lj_type_params).
+template <typename T> struct LjScalars {
+  static constexpr bool typed = false;
+  T eps4, sig2, rcf2;
+};
+template <typename T> struct LjByType {
+  static constexpr bool typed = true;
+  const int32_t* __restrict__ types;
+  const T* __restrict__ par;  // [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2
+};
 
-// one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i.  status (nl_lj_forces_enqueue,
-// which does not wait for the build): the build's status word; a list whose build failed gives NaN forces.
-template <typename T, bool HALF, typename OFF, bool TRI>
-__global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
-                                            const int32_t* __restrict__ list, int32_t n, T eps4, T sig2, T rcf2,
-                                            T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status,
-                                            T xy, T xz, T yz) {
+// one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i.  status (the enqueue
+// variants, which do not wait for the build): the build's status word; a list whose build failed gives NaN forces.
+// By type: lane t < ntypes holds eps4, sig2 and rcf2 of (t_row, t), an entry picks them by its partner's type with ds_bpermute.
+template <typename T, bool HALF, typename OFF, bool TRI, typename PAR>
+__device__ __forceinline__ void lj_row(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp, const int32_t* __restrict__ list,
+                                       int32_t n, const PAR& p, T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status,
+                                       T xy, T xz, T yz) {
   const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (row >= n) return;
   if (status && *status != 0u) {  // (uniform: every row of the launch takes this branch)
@@ -67,12 +74,27 @@ __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t str
     }
     return;
   }
+  T eps4, sig2, rcf2;  // scalars: the pair's; by type: this lane's entries of the row's type
+  if constexpr (PAR::typed) {
+    constexpr int NT2 = NL_MAX_TYPES * NL_MAX_TYPES;
+    const int32_t at = (p.types[row] & (NL_MAX_TYPES - 1)) * NL_MAX_TYPES + (lane & (NL_MAX_TYPES - 1));
+    eps4 = p.par[at], sig2 = p.par[NT2 + at], rcf2 = p.par[2 * NT2 + at];
+  } else {
+    eps4 = p.eps4, sig2 = p.sig2, rcf2 = p.rcf2;
+  }
   T xi, yi, zi;
   load_xyz(q, stride, row, xi, yi, zi);
   T ax = 0, ay = 0, az = 0, ae = 0;
   const OFF b = kp[row], e = kp[row + 1];
-  for (OFF k = b + lane; k < e; k += 64) {
-    const int32_t j = list[k];
+  for (OFF k = b + lane; (PAR::typed ? k - lane : k) < e; k += 64) {  // (by type: every lane stays for the bpermute)
+    const bool valid = !PAR::typed || k < e;
+    const int32_t j = valid ? list[k] : row;
+    T e4 = eps4, s2 = sig2, c2 = rcf2;
+    if constexpr (PAR::typed) {
+      const int32_t tj = p.types[j] & (NL_MAX_TYPES - 1);
+      e4 = shfl_t(eps4, tj), s2 = shfl_t(sig2, tj), c2 = shfl_t(rcf2, tj);
+      if (!valid) continue;
+    }
     T xj, yj, zj;
     load_xyz(q, stride, j, xj, yj, zj);
     T fx, fy, fz, pe;
@@ -81,7 +103,7 @@ __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t str
     // minimum-image list (nl_set_periodic_axes): on a periodic axis (L > 0) the pair is taken at the image the list
     // found it at
     lj_image<T, TRI>(dx, dy, dz, Lx, Ly, Lz, xy, xz, yz);
-    lj_pair<T>(dx, dy, dz, eps4, sig2, rcf2, fx, fy, fz, pe, in);
+    lj_pair<T>(dx, dy, dz, e4, s2, c2, fx, fy, fz, pe, in);
     ax += fx, ay += fy, az += fz, ae += (T)0.5 * pe;
     if (HALF && in) {  // Newton's third law: the partner's share
       atomicAdd(&f[(size_t)j * 4 + 0], -fx);
@@ -103,64 +125,106 @@ __global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t str
   }
 }
 
-template <typename T, typename OFF>
-int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, double eps, double sigma, double rc_force, void* f_dev,
-              hipStream_t s, const uint32_t* status = nullptr) {
+template <typename T, bool HALF, typename OFF, bool TRI>
+__global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
+                                            const int32_t* __restrict__ list, int32_t n, T eps4, T sig2, T rcf2,
+                                            T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status,
+                                            T xy, T xz, T yz) {
+  lj_row<T, HALF, OFF, TRI>(q, stride, kp, list, n, LjScalars<T>{eps4, sig2, rcf2}, f, Lx, Ly, Lz, status, xy, xz, yz);
+}
+template <typename T, bool HALF, typename OFF, bool TRI>
+__global__ void __launch_bounds__(256) k_lj_typed(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
+                                                  const int32_t* __restrict__ list, int32_t n, const int32_t* __restrict__ types,
+                                                  const T* __restrict__ par, T* __restrict__ f, T Lx, T Ly, T Lz,
+                                                  const uint32_t* __restrict__ status, T xy, T xz, T yz) {
+  lj_row<T, HALF, OFF, TRI>(q, stride, kp, list, n, LjByType<T>{types, par}, f, Lx, Ly, Lz, status, xy, xz, yz);
+}
+
+// lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables.
+int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, void* f_dev, hipStream_t s, const uint32_t* status) {
   const int32_t n = h->n;
-  const T eps4 = (T)(4.0 * eps), sig2 = (T)(sigma * sigma), rcf2 = (T)(rc_force * rc_force);
-  const int32_t nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
   if (n == 0) return NL_OK;
-  // box lengths for the minimum image on the axes of the list's build; 0 = open axis (the reference's distances,
-  // neighlist_cpu.hpp:219-223)
-  // (the build's box, BuildPlan::box, and its tilt: triclinic instances where it has one)
-  const Box& b = h->plan.box;
-  const T Lx = (h->plan.pbc & 1) ? (T)b.L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)b.L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)b.L[2] : (T)0;
-  const T xy = (T)b.xy, xz = (T)b.xz, yz = (T)b.yz;
-  auto launch = [&](auto half, auto tri) {
-    hipLaunchKernelGGL((k_lj<T, decltype(half)::value, OFF, decltype(tri)::value>), dim3(nbw), dim3(256), 0, s, static_cast<const T*>(q_dev),
-                       stride, static_cast<const OFF*>(h->key_pointer), h->list, n, eps4, sig2, rcf2, static_cast<T*>(f_dev), Lx, Ly, Lz,
-                       status, xy, xz, yz);
-  };
-  if (!h->plan.full) HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
-  if (h->plan.tilt) h->plan.full ? launch(std::false_type(), std::true_type()) : launch(std::true_type(), std::true_type());
-  else h->plan.full ? launch(std::false_type(), std::false_type()) : launch(std::true_type(), std::false_type());
-  HIPCHK(h, hipGetLastError());
+  return dispatch_t_off(h, [&](auto t, auto off) -> int {
+    using T = decltype(t);
+    using OFF = decltype(off);
+    const int32_t nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
+    // box lengths for the minimum image on the axes of the list's build; 0 = open axis (the reference's distances,
+    // neighlist_cpu.hpp:219-223)
+    // (the build's box, BuildPlan::box, and its tilt: triclinic instances where it has one)
+    const Box& b = h->plan.box;
+    const T Lx = (h->plan.pbc & 1) ? (T)b.L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)b.L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)b.L[2] : (T)0;
+    const T xy = (T)b.xy, xz = (T)b.xz, yz = (T)b.yz;
+    const T* q = static_cast<const T*>(q_dev);
+    const OFF* kp = static_cast<const OFF*>(h->key_pointer);
+    T* f = static_cast<T*>(f_dev);
+    auto launch = [&](auto half, auto tri) {
+      constexpr bool H = decltype(half)::value, R = decltype(tri)::value;
+      if (lj)
+        hipLaunchKernelGGL((k_lj<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, q, stride, kp, h->list, n, (T)(4.0 * lj[0]), (T)(lj[1] * lj[1]),
+                           (T)(lj[2] * lj[2]), f, Lx, Ly, Lz, status, xy, xz, yz);
+      else
+        hipLaunchKernelGGL((k_lj_typed<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, q, stride, kp, h->list, n, h->ty_types,
+                           static_cast<const T*>(h->lj_par), f, Lx, Ly, Lz, status, xy, xz, yz);
+    };
+    if (!h->plan.full) HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
+    if (h->plan.tilt) h->plan.full ? launch(std::false_type(), std::true_type()) : launch(std::true_type(), std::true_type());
+    else h->plan.full ? launch(std::false_type(), std::false_type()) : launch(std::true_type(), std::false_type());
+    HIPCHK(h, hipGetLastError());
+    return NL_OK;
+  });
+}
+
+// The typed forces' preconditions beyond the untyped ones: a type table and parameters of its ntypes, and rc_force_ab
+// within rc_ab (less the skin for the enqueue variant, whose list may be reused).
+int lj_typed_check(nl_handle_t h, double skin) {
+  if (!h->ty_types || !h->lj_par) return fail(h, NL_ERR_STATE);
+  if (h->lj_ntypes != h->ty_ntypes) return fail(h, NL_ERR_ARG);
+  const int32_t nt = h->ty_ntypes;
+  for (int32_t k = 0; k < nt * nt; k++)
+    if (!(h->lj_rcf[k] <= h->ty_rc[k] - skin)) return fail(h, NL_ERR_ARG);
   return NL_OK;
 }
 
 }  // namespace
 
-extern "C" int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma,
-                            double rc_force, void* f_dev, void* stream) {
+extern "C" {
+
+int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force, void* f_dev,
+                 void* stream) {
   if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4) || !(rc_force > 0) || !(sigma > 0)) return fail(h, NL_ERR_ARG);
-  int rc = nl_synchronize(h);  // the list must be complete (and its build must have succeeded)
-  if (rc) return rc;
-  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
-  if (rc_force > h->rc) return fail(h, NL_ERR_ARG);                   // the list does not reach that far
+  if (int rc = consumer_ready(h, (hipStream_t)stream, false)) return rc;
+  if (rc_force > h->rc) return fail(h, NL_ERR_ARG);  // the list does not reach that far
   HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (h->plan.wide)
-    return h->dtype == NL_F32 ? lj_launch<float, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s)
-                              : lj_launch<double, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s);
-  return h->dtype == NL_F32 ? lj_launch<float, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s)
-                            : lj_launch<double, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s);
+  const double lj[3] = {epsilon, sigma, rc_force};
+  return lj_launch(h, q_dev, q_stride, lj, f_dev, (hipStream_t)stream, nullptr);
 }
 
 // nl_lj_forces without the wait: stream-ordered behind the update (or completed build) whose list it reads.
-extern "C" int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma,
-                                    double rc_force, void* f_dev, void* stream) {
+int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
+                         void* f_dev, void* stream) {
   if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4) || !(rc_force > 0) || !(sigma > 0)) return fail(h, NL_ERR_ARG);
   if (!(rc_force <= h->rc - h->skin)) return fail(h, NL_ERR_ARG);  // beyond what a list reused within the skin guarantees
-  hipStream_t s = (hipStream_t)stream;
-  if (!h->pending && !h->built) return fail(h, NL_ERR_STATE);  // no build, or one the host has seen fail
-  // a pending build must be an update's (a plain asynchronous build may still need finish() to complete its list) and
-  // enqueued on this stream
-  if (h->pending && (!h->last_update || s != h->last_stream)) return fail(h, NL_ERR_STATE);
-  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
+  if (int rc = consumer_ready(h, (hipStream_t)stream, true)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->plan.wide)
-    return h->dtype == NL_F32 ? lj_launch<float, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status)
-                              : lj_launch<double, int64_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status);
-  return h->dtype == NL_F32 ? lj_launch<float, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status)
-                            : lj_launch<double, int32_t>(h, q_dev, q_stride, epsilon, sigma, rc_force, f_dev, s, h->status);
+  const double lj[3] = {epsilon, sigma, rc_force};
+  return lj_launch(h, q_dev, q_stride, lj, f_dev, (hipStream_t)stream, h->status);
 }
+
+int nl_lj_forces_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream) {
+  if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
+  if (int rc = consumer_ready(h, (hipStream_t)stream, false)) return rc;
+  if (int rc = lj_typed_check(h, 0.0)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  return lj_launch(h, q_dev, q_stride, nullptr, f_dev, (hipStream_t)stream, nullptr);
+}
+
+// nl_lj_forces_typed without the wait, as nl_lj_forces_enqueue.
+int nl_lj_forces_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream) {
+  if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
+  if (int rc = lj_typed_check(h, h->skin)) return rc;
+  if (int rc = consumer_ready(h, (hipStream_t)stream, true)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  return lj_launch(h, q_dev, q_stride, nullptr, f_dev, (hipStream_t)stream, h->status);
+}
+
+}  // extern "C"

@@ -8,131 +8,86 @@
 //               the kept entries into `list`.  A wave per row; the row's excluded ids are broadcast with readlane, or
 //               binary-searched where a row has more than EXCL_BCAST of them.  Every kernel takes the update's gate.
 // Builds without a table launch none of this and use the buffers they always used.
-// Included at the end of nl_api.hip.
+// Included at the end of nl_api.hip; the pieces it shares with the other stages: nl_stage.hpp.
 
 namespace {
 
 constexpr int EXCL_BCAST = 32;  // rows with up to this many excluded ids compare against registers; more: binary search
-constexpr int EXCL_THREADS = 256;
 
 // Is v (a partner of the row) one of the row's excluded ids?  exid: lane l holds ids[xb + l] for l < ne (<= EXCL_BCAST).
 __device__ __forceinline__ bool excl_hit(int32_t v, int32_t exid, int32_t ne, const int32_t* __restrict__ ids, int32_t xb) {
-  if (ne <= EXCL_BCAST) {
-    bool hit = false;
-    for (int32_t t = 0; t < ne; t++) hit |= v == __builtin_amdgcn_readlane(exid, t);  // (ne is uniform)
-    return hit;
-  }
-  int32_t lo = xb, hi = xb + ne;  // first id >= v in the sorted segment
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (ids[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < xb + ne && ids[lo] == v;
+  if (ne > EXCL_BCAST) return sorted_contains(ids, xb, ne, v);
+  bool hit = false;
+  for (int32_t t = 0; t < ne; t++) hit |= v == __builtin_amdgcn_readlane(exid, t);  // (ne is uniform)
+  return hit;
 }
 
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
+template <typename OFF> struct ExclArgs {
+  const OFF* __restrict__ kp_pre;  // the unfiltered offsets and list
+  const int32_t* __restrict__ list_pre;
+  int32_t n_rows;
+  int64_t capacity;
+  const int32_t* __restrict__ ex_off;  // the table
+  const int32_t* __restrict__ ex_ids;
+  const uint32_t* __restrict__ gate;
+};
 
-// count[row] = entries of the unfiltered row that the table keeps.  Rows without exclusions do not read the list.
+// Both passes of the stage, a wave per row.  Count: count[row] = entries of the unfiltered row that the table keeps; rows
+// without exclusions do not read the list.  COMPACT: list[kp[row] ...] = the kept entries in their order (ballot + mbcnt).
 // (Entries at or past the list capacity were never written: an overflowed build fails, and they are only not read.)
-template <typename OFF>
-__global__ void __launch_bounds__(EXCL_THREADS) k_excl_count(const OFF* __restrict__ kp_pre, const int32_t* __restrict__ list_pre,
-                                                            int32_t n_rows, int64_t capacity, const int32_t* __restrict__ ex_off,
-                                                            const int32_t* __restrict__ ex_ids, int32_t* __restrict__ count,
-                                                            const uint32_t* __restrict__ gate) {
-  if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
+template <typename OFF, bool COMPACT>
+__device__ __forceinline__ void excl_pass(const ExclArgs<OFF>& a, int32_t* __restrict__ count, const OFF* __restrict__ kp,
+                                          int32_t* __restrict__ list) {
+  if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   const int lane = threadIdx.x & 63;
-  const int32_t waves = gridDim.x * (EXCL_THREADS / WAVE);
-  for (int32_t row = blockIdx.x * (EXCL_THREADS / WAVE) + (threadIdx.x >> 6); row < n_rows; row += waves) {
-    const int64_t b = (int64_t)kp_pre[row], e = (int64_t)kp_pre[row + 1];
-    const int32_t xb = ex_off[row], ne = ex_off[row + 1] - xb;
-    int64_t kept = e - b;
-    if (ne > 0) {
-      const int32_t exid = lane < ne && ne <= EXCL_BCAST ? ex_ids[xb + lane] : -1;
-      const int64_t end = e < capacity ? e : capacity;
-      for (int64_t k = b + lane; k - lane < end; k += WAVE) {
-        const int32_t v = k < end ? list_pre[k] : -1;
-        const bool hit = excl_hit(v, exid, ne, ex_ids, xb) & (k < end);  // (no short cut: readlane below)
-        kept -= __builtin_popcountll(__ballot(hit));
-      }
-    }
-    if (lane == 0) count[row] = (int32_t)kept;
-  }
-}
-
-// list[key_pointer[row] ...] = the kept entries of the unfiltered row, in their order (ballot + mbcnt).
-template <typename OFF>
-__global__ void __launch_bounds__(EXCL_THREADS) k_excl_compact(const OFF* __restrict__ kp_pre, const int32_t* __restrict__ list_pre,
-                                                              const OFF* __restrict__ kp, int32_t n_rows, int64_t capacity,
-                                                              const int32_t* __restrict__ ex_off, const int32_t* __restrict__ ex_ids,
-                                                              int32_t* __restrict__ list, const uint32_t* __restrict__ gate) {
-  if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
-  const int lane = threadIdx.x & 63;
-  const int32_t waves = gridDim.x * (EXCL_THREADS / WAVE);
-  for (int32_t row = blockIdx.x * (EXCL_THREADS / WAVE) + (threadIdx.x >> 6); row < n_rows; row += waves) {
-    const int64_t b = (int64_t)kp_pre[row], e = (int64_t)kp_pre[row + 1];
-    const int64_t end = e < capacity ? e : capacity;
-    int64_t dst = (int64_t)kp[row];
-    const int32_t xb = ex_off[row], ne = ex_off[row + 1] - xb;
+  const int32_t waves = gridDim.x * (STAGE_THREADS / WAVE);
+  for (int32_t row = blockIdx.x * (STAGE_THREADS / WAVE) + (threadIdx.x >> 6); row < a.n_rows; row += waves) {
+    const int64_t b = (int64_t)a.kp_pre[row], e = (int64_t)a.kp_pre[row + 1];
+    const int64_t end = e < a.capacity ? e : a.capacity;
+    const int32_t xb = a.ex_off[row], ne = a.ex_off[row + 1] - xb;
+    int64_t kept = e - b, dst = 0;
+    if constexpr (COMPACT) dst = (int64_t)kp[row];
     if (ne == 0) {
-      for (int64_t k = b + lane; k < end; k += WAVE) {
-        const int64_t d = dst + (k - b);
-        if (d < capacity) list[d] = list_pre[k];
+      if constexpr (COMPACT)
+        for (int64_t k = b + lane; k < end; k += WAVE) {
+          const int64_t d = dst + (k - b);
+          if (d < a.capacity) list[d] = a.list_pre[k];
+        }
+    } else {
+      const int32_t exid = lane < ne && ne <= EXCL_BCAST ? a.ex_ids[xb + lane] : -1;
+      for (int64_t k = b + lane; k - lane < end; k += WAVE) {
+        const int32_t v = k < end ? a.list_pre[k] : -1;
+        const bool hit = excl_hit(v, exid, ne, a.ex_ids, xb);  // (no short cut: readlane in it)
+        if constexpr (COMPACT) {
+          const bool keep = !hit & (k < end);
+          const uint64_t mask = __ballot(keep);
+          const int64_t d = dst + lanes_below(mask);
+          if (keep && d < a.capacity) list[d] = v;
+          dst += __builtin_popcountll(mask);
+        } else {
+          kept -= __builtin_popcountll(__ballot(hit & (k < end)));
+        }
       }
-      continue;
     }
-    const int32_t exid = lane < ne && ne <= EXCL_BCAST ? ex_ids[xb + lane] : -1;
-    for (int64_t k = b + lane; k - lane < end; k += WAVE) {
-      const int32_t v = k < end ? list_pre[k] : -1;
-      const bool keep = !excl_hit(v, exid, ne, ex_ids, xb) & (k < end);
-      const uint64_t mask = __ballot(keep);
-      const int64_t d = dst + lanes_below(mask);
-      if (keep && d < capacity) list[d] = v;
-      dst += __builtin_popcountll(mask);
-    }
+    if (!COMPACT && lane == 0) count[row] = (int32_t)kept;
   }
 }
 
-template <typename OFF> int launch_exclude_w(nl_handle_t h, int32_t n_rows, hipStream_t s) {
-  const OFF* kp_pre = static_cast<const OFF*>(h->kp_pre);
-  const int32_t grid = std::max(1, std::min((n_rows + 3) / 4, 16 * h->num_cus));
-  if (n_rows > 0)
-    hipLaunchKernelGGL(k_excl_count<OFF>, dim3(grid), dim3(EXCL_THREADS), 0, s, kp_pre, h->list_pre, n_rows, h->capacity, h->ex_off,
-                       h->ex_ids, h->count, h->gate);
-  if (int rc = launch_scan(h, h->count, n_rows, static_cast<OFF*>(h->key_pointer), h->totals + 2, s, h->status + META_KEPT)) return rc;
-  if (n_rows > 0)
-    hipLaunchKernelGGL(k_excl_compact<OFF>, dim3(grid), dim3(EXCL_THREADS), 0, s, kp_pre, h->list_pre,
-                       static_cast<const OFF*>(h->key_pointer), n_rows, h->capacity, h->ex_off, h->ex_ids, h->list, h->gate);
-  HIPCHK(h, hipGetLastError());
-  return NL_OK;
+template <typename OFF> __global__ void __launch_bounds__(STAGE_THREADS) k_excl_count(ExclArgs<OFF> a, int32_t* __restrict__ count) {
+  excl_pass<OFF, false>(a, count, nullptr, nullptr);
+}
+template <typename OFF>
+__global__ void __launch_bounds__(STAGE_THREADS) k_excl_compact(ExclArgs<OFF> a, const OFF* __restrict__ kp, int32_t* __restrict__ list) {
+  excl_pass<OFF, true>(a, nullptr, kp, list);
 }
 
 // (declared at the top of nl_api.hip)
 int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s) {
-  return h->plan.wide ? launch_exclude_w<int64_t>(h, n_rows, s) : launch_exclude_w<int32_t>(h, n_rows, s);
-}
-
-// The pre-exclusion offsets and list while a table is set (one offset array, one list capacity); nothing without one.
-// (Shared with the type table of nl_types.inc: either table filters builds through these buffers.)
-int excl_reserve(nl_handle_t h) {
-  if (!filter_tables(h)) return NL_OK;
-  if (h->pre_rows < (int64_t)h->n_max) {
-    h->pre_rows = -1;
-    if (int rc = dev_alloc(h, &h->kp_pre, 8 * ((size_t)h->n_max + 32))) return rc;
-    h->pre_rows = h->n_max;
-  }
-  if (h->pre_capacity < h->capacity) {
-    h->pre_capacity = -1;
-    if (int rc = dev_alloc(h, &h->list_pre, 4 * ((size_t)h->capacity + 16))) return rc;
-    h->pre_capacity = h->capacity;
-  }
-  return NL_OK;
-}
-
-bool excl_ready(nl_handle_t h) {
-  return h->kp_pre && h->list_pre && h->pre_rows >= (int64_t)h->n_max && h->pre_capacity >= h->capacity;
+  return dispatch_t_off(h, [&](auto, auto off) -> int {
+    using OFF = decltype(off);
+    const ExclArgs<OFF> a = {static_cast<const OFF*>(h->kp_pre), h->list_pre, n_rows, h->capacity, h->ex_off, h->ex_ids, h->gate};
+    return launch_passes<OFF>(h, n_rows, n_rows, s, a, k_excl_count<OFF>, k_excl_compact<OFF>);
+  });
 }
 
 // ------------------------------------------------------------------------------------------- the table, on the device
@@ -300,14 +255,6 @@ int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool 
   return rc;
 }
 
-// (declared at the top of nl_api.hip) The unfiltered buffers, once no table needs them.
-void filter_release(nl_handle_t h) {
-  for (void* b : {h->kp_pre, (void*)h->list_pre})
-    if (b) (void)hipFree(b);
-  h->kp_pre = nullptr, h->list_pre = nullptr;
-  h->pre_capacity = h->pre_rows = -1;
-}
-
 void excl_clear(nl_handle_t h) {
   for (void* b : {h->ex_off, h->ex_ids})
     if (b) (void)hipFree(b);
@@ -358,7 +305,7 @@ int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, 
   HIPCHK(h, hipDeviceSynchronize());  // (the caller's pairs may come from any stream)
   if (int rc = excl_build(h, pairs_dev, n_pairs, n, true)) return rc;
   h->upd_valid = false;
-  if (int rc = excl_reserve(h)) {  // no room for the pre-exclusion buffers: no table
+  if (int rc = filter_reserve(h)) {  // no room for the pre-exclusion buffers: no table
     excl_clear(h);
     return rc;
   }

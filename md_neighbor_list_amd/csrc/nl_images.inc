@@ -1,13 +1,12 @@
 // nl_images.inc -- the periodic image of every entry of the list (nl_set_pair_images) and its consumer (nl_pair_vectors).
 //   The rule    include/nl_hip.h: s = n_j + w_ij - n_i, with n the wraps local_cell decides from the input coordinate and w
-//               the faces through which the stencil of i's cell reaches j's cell (segment_cells; type_face_w restates it).
+//               the faces through which the stencil of i's cell reaches j's cell (segment_cells; face_w of nl_stage.hpp states it).
 //   The stage   at the very end of a build, behind the filter stage where there is one, on the build's stream:
-//               k_image_codes   one thread per particle runs local_cell once and writes a 16-bit code: bit d = its cell is
-//                               the first along axis d, bit 3 + d = the last (axes of the mask only: type_frame's faces),
-//                               bits 6 + 2d .. 7 + 2d the wrap n_d + 1.  2 bytes a particle: the table of a million
-//                               particles stays in one XCD's L2.
-//               k_pair_images   a wave takes IMG_ROWS consecutive rows of the final key_pointer / list at once (their
-//                               entries are contiguous); per entry one 4-byte read, one 2-byte gather of code[j] and one
+//               k_image_codes   one thread per particle runs local_cell once and writes its 16-bit frame (particle_frame:
+//                               faces and wraps).  2 bytes a particle: the table of a million particles stays in one
+//                               XCD's L2.
+//               k_pair_images   a wave takes a chunk of STAGE_ROWS consecutive rows of the final key_pointer / list at
+//                               once (row_chunk); per entry one 4-byte read, one 2-byte gather of code[j] and one
 //                               4-byte vector store of {s_a, s_b, s_c, 0}, coalesced along the list.  No position is read
 //                               and local_cell is not run per entry.  The gather is what costs (a cache line per entry
 //                               where ids are not spatially ordered), and most builds need little of it: k_image_codes
@@ -22,45 +21,30 @@
 
 namespace {
 
-constexpr int IMG_THREADS = 256;
-constexpr int IMG_ROWS = 8;    // rows a wave takes at once (as TYPE_ROWS)
 constexpr int IMG_UNROLL = 4;  // entries a lane keeps in flight
-constexpr uint32_t IMG_CODE_NONE = 1u << 6 | 1u << 8 | 1u << 10;  // no faces, no wraps
-// words of h->img_words: both zero between builds
+// words of h->img_words (IMG_WORDS of them, nl_api.hip): both zero between builds
 constexpr int IMG_WRAPPED = 0;  // some particle of the build has a wrap (k_image_codes)
 constexpr int IMG_TICKET = 1;   // blocks of k_pair_images through
-constexpr int IMG_WORDS = 4;
 
 template <typename T>
-__global__ void __launch_bounds__(IMG_THREADS) k_image_codes(Grid<T> g, const T* __restrict__ q, int32_t stride, int32_t n,
+__global__ void __launch_bounds__(STAGE_THREADS) k_image_codes(Grid<T> g, const T* __restrict__ q, int32_t stride, int32_t n,
                                                             uint16_t* __restrict__ code, uint32_t* __restrict__ words) {
   if (gate_closed(g.gate)) return;  // (nl_update_list: no build this time)
   bool wrapped = false;
-  for (int32_t i = blockIdx.x * IMG_THREADS + threadIdx.x; i < n; i += gridDim.x * IMG_THREADS) {
+  for (int32_t i = blockIdx.x * STAGE_THREADS + threadIdx.x; i < n; i += gridDim.x * STAGE_THREADS) {
     T x, y, z;
     load_xyz(q, stride, i, x, y, z);
-    int32_t lz = 0, row = 0, wrap[3] = {0, 0, 0};
-    const int32_t c = local_cell(g, x, y, z, &lz, &row, static_cast<T*>(nullptr), wrap);
-    uint32_t v = IMG_CODE_NONE;  // (a rejected particle fails its build: its code does not matter)
-    if (c >= 0) {
-      const int32_t ci[3] = {c - row * g.m[0], row - lz * g.m[1], lz};
-      v = 0;
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        if ((g.pbc >> d) & 1) v |= (ci[d] == 0 ? 1u : 0u) << d | (ci[d] == g.m[d] - 1 ? 8u : 0u) << d;
-        v |= (uint32_t)(wrap[d] + 1) << (6 + 2 * d);
-      }
-      wrapped |= (wrap[0] | wrap[1] | wrap[2]) != 0;
-    }
+    const uint32_t v = particle_frame(g, x, y, z);  // (a rejected particle fails its build: its code does not matter)
+    wrapped |= (v & ~FRAME_FACES) != FRAME_NONE;
     code[i] = (uint16_t)v;
   }
   if (__ballot(wrapped) != 0ull && (threadIdx.x & 63) == 0) atomicOr(words + IMG_WRAPPED, 1u);
 }
 
 // {s_a, s_b, s_c, 0} as bytes of one word, from the codes of the row (ci) and of the partner (cj): the three axes at
-// once, one byte each.  w_ij is type_face_w's: -1 where the row's cell is the first and the partner's the last, +1 the
-// other way round.  Per byte (n_j + 1) + [hi_i & lo_j] + 3 - (n_i + 1) - [lo_i & hi_j] = s + 3 lies in 0..6: no borrow
-// crosses a byte; the last line takes the 3 off again inside each byte.
+// once, one byte each -- the byte-parallel form of s_d = n_j + face_w(ci, cj, d) - n_i (nl_stage.hpp).  Per byte
+// (n_j + 1) + [hi_i & lo_j] + 3 - (n_i + 1) - [lo_i & hi_j] = s + 3 lies in 0..6: no borrow crosses a byte; the last
+// line takes the 3 off again inside each byte.
 __device__ __forceinline__ uint32_t image_word(uint32_t ci, uint32_t cj) {
   constexpr uint32_t BITS = 1u | 1u << 7 | 1u << 14, WRAPS = 1u | 1u << 6 | 1u << 12;  // (bit d -> byte d; field d -> byte d)
   const uint32_t lo_i = ((ci & 7u) * BITS) & 0x010101u, hi_i = (((ci >> 3) & 7u) * BITS) & 0x010101u;
@@ -70,48 +54,11 @@ __device__ __forceinline__ uint32_t image_word(uint32_t ci, uint32_t cj) {
   return ((t | 0x808080u) - 0x030303u) ^ 0x808080u;
 }
 
-// The rows of a wave's chunk: first entries of its rows, uniform.  beg[t] for t >= nr is the chunk's end.
-struct ImgRows {
-  int64_t beg[IMG_ROWS + 1];
-  int64_t b, e;  // the chunk's entries [b, e), within the list's capacity
-  int32_t nr;
-};
-
-template <typename OFF>
-__device__ __forceinline__ void image_rows(const OFF* __restrict__ kp, int32_t n_rows, int64_t capacity, int32_t r0, int lane, ImgRows& r) {
-  r.nr = min(IMG_ROWS, n_rows - r0);
-  const int64_t v = (int64_t)kp[r0 + min(lane, r.nr)];
-#pragma unroll
-  for (int t = 0; t <= IMG_ROWS; t++) {
-    const int src = min(t, r.nr);
-    r.beg[t] = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)((uint64_t)v >> 32), src) << 32) |
-                         (uint32_t)__builtin_amdgcn_readlane((int32_t)v, src));
-  }
-  r.b = max(r.beg[0], (int64_t)0);
-  r.e = min(r.beg[IMG_ROWS], capacity);  // (entries past the capacity were never written: such a build fails)
-}
-
-// The code of the row of entry k of the chunk (rows past nr begin at the chunk's end).  A list behind int32 offsets is
-// compared in 32 bits, relative to the chunk's first entry.
-template <typename OFF>
-__device__ __forceinline__ uint32_t image_row_code(const ImgRows& r, const uint32_t (&rc)[IMG_ROWS], int64_t k) {
-  uint32_t ci = rc[0];
-  if constexpr (sizeof(OFF) == 4) {
-    const uint32_t rel = (uint32_t)(k - r.beg[0]);
-#pragma unroll
-    for (int t = 1; t < IMG_ROWS; t++) ci = rel >= (uint32_t)(r.beg[t] - r.beg[0]) ? rc[t] : ci;
-  } else {
-#pragma unroll
-    for (int t = 1; t < IMG_ROWS; t++) ci = k >= r.beg[t] ? rc[t] : ci;
-  }
-  return ci;
-}
-
 // The entries of one chunk.  ALL: some particle of the build was wrapped, every entry looks at its partner (the list is
 // read first, the rows are found while the gathers are in flight).  Else every n is 0 and s = w_ij: an entry of a row
 // whose cell touches no periodic face is 0, and neither the list nor the partner's code is read for it.
 template <typename OFF, bool ALL>
-__device__ __forceinline__ void image_chunk(const ImgRows& r, const uint32_t (&rc)[IMG_ROWS], int lane, const int32_t* __restrict__ list,
+__device__ __forceinline__ void image_chunk(const RowChunk& r, const uint32_t (&rc)[STAGE_ROWS], int lane, const int32_t* __restrict__ list,
                                             int32_t n, const uint16_t* __restrict__ code, uint32_t* __restrict__ images) {
   for (int64_t k0 = r.b + lane; k0 - lane < r.e; k0 += IMG_UNROLL * WAVE) {
     int32_t j[IMG_UNROLL];
@@ -121,20 +68,20 @@ __device__ __forceinline__ void image_chunk(const ImgRows& r, const uint32_t (&r
       const int64_t k = k0 + u * WAVE;
       bool need = k < r.e;
       if constexpr (!ALL) {
-        ci[u] = image_row_code<OFF>(r, rc, k);
-        need = need && (ci[u] & 63u) != 0u;
+        ci[u] = chunk_pick<OFF>(r, k, rc);
+        need = need && (ci[u] & FRAME_FACES) != 0u;
       }
       j[u] = need ? list[k] : -1;
     }
 #pragma unroll
     for (int u = 0; u < IMG_UNROLL; u++) {
-      cj[u] = IMG_CODE_NONE;
+      cj[u] = FRAME_NONE;
       if ((uint32_t)j[u] < (uint32_t)n) cj[u] = code[j[u]];  // (an entry of a failed build may be anything)
     }
 #pragma unroll
     for (int u = 0; u < IMG_UNROLL; u++) {
       const int64_t k = k0 + u * WAVE;
-      if constexpr (ALL) ci[u] = image_row_code<OFF>(r, rc, k);
+      if constexpr (ALL) ci[u] = chunk_pick<OFF>(r, k, rc);
       if (k < r.e) images[k] = image_word(ci[u], cj[u]);
     }
   }
@@ -142,26 +89,26 @@ __device__ __forceinline__ void image_chunk(const ImgRows& r, const uint32_t (&r
 
 // images[k] of every entry k of the list
 template <typename OFF>
-__global__ void __launch_bounds__(IMG_THREADS) k_pair_images(const OFF* __restrict__ kp, const int32_t* __restrict__ list, int32_t n_rows,
+__global__ void __launch_bounds__(STAGE_THREADS) k_pair_images(const OFF* __restrict__ kp, const int32_t* __restrict__ list, int32_t n_rows,
                                                             int32_t n, int64_t capacity, const uint16_t* __restrict__ code,
                                                             uint32_t* __restrict__ images, uint32_t* __restrict__ words,
                                                             const uint32_t* __restrict__ gate) {
   if (gate_closed(gate)) return;  // (nl_update_list: no build this time)
   const int lane = threadIdx.x & 63;
-  const int32_t chunks = (n_rows + IMG_ROWS - 1) / IMG_ROWS, waves = gridDim.x * (IMG_THREADS / WAVE);
+  const int32_t chunks = (n_rows + STAGE_ROWS - 1) / STAGE_ROWS, waves = gridDim.x * (STAGE_THREADS / WAVE);
   const bool wrapped = words[IMG_WRAPPED] != 0u;  // (uniform; no block resets it before every block has read it)
-  for (int32_t c = blockIdx.x * (IMG_THREADS / WAVE) + (threadIdx.x >> 6); c < chunks; c += waves) {
-    const int32_t r0 = c * IMG_ROWS;
-    ImgRows r;
-    image_rows<OFF>(kp, n_rows, capacity, r0, lane, r);
-    const uint32_t mine = lane < r.nr ? code[r0 + lane] : IMG_CODE_NONE;
-    uint32_t rc[IMG_ROWS];  // (uniform) the codes of the chunk's rows
+  for (int32_t c = blockIdx.x * (STAGE_THREADS / WAVE) + (threadIdx.x >> 6); c < chunks; c += waves) {
+    const int32_t r0 = c * STAGE_ROWS;
+    RowChunk r;
+    row_chunk<OFF>(kp, n_rows, capacity, r0, lane, r);
+    const uint32_t mine = lane < r.nr ? code[r0 + lane] : FRAME_NONE;
+    uint32_t rc[STAGE_ROWS];  // (uniform) the codes of the chunk's rows
 #pragma unroll
-    for (int t = 0; t < IMG_ROWS; t++) rc[t] = (uint32_t)__builtin_amdgcn_readlane((int32_t)mine, t);
+    for (int t = 0; t < STAGE_ROWS; t++) rc[t] = (uint32_t)__builtin_amdgcn_readlane((int32_t)mine, t);
     uint32_t any = rc[0];
 #pragma unroll
-    for (int t = 1; t < IMG_ROWS; t++) any |= rc[t];
-    if (!wrapped && (any & 63u) == 0u) {  // (uniform) no row of the chunk touches a periodic face: nothing to read
+    for (int t = 1; t < STAGE_ROWS; t++) any |= rc[t];
+    if (!wrapped && (any & FRAME_FACES) == 0u) {  // (uniform) no row of the chunk touches a periodic face: nothing to read
       for (int64_t k = r.b + lane; k < r.e; k += WAVE) images[k] = 0u;
       continue;
     }
@@ -191,70 +138,28 @@ __global__ void __launch_bounds__(256) k_zero_images(const OFF* __restrict__ kp,
   if (blockIdx.x == 0 && (int64_t)threadIdx.x < end - 4 * quads) images[4 * quads + threadIdx.x] = 0u;
 }
 
-template <typename T> int launch_images_t(nl_handle_t h, int32_t n_rows, hipStream_t s) {
-  const int32_t n = h->args.n;
-  const bool wide = h->plan.wide;
-  if (h->plan.pbc == 0) {
-    const int64_t quads = std::max<int64_t>(1, h->capacity / 4);
-    const dim3 grid((uint32_t)std::min<int64_t>((quads + 1023) / 1024, 8 * h->num_cus));
-    if (wide) hipLaunchKernelGGL(k_zero_images<int64_t>, grid, dim3(256), 0, s, static_cast<const int64_t*>(h->key_pointer), n_rows, h->capacity, h->images, h->gate);
-    else hipLaunchKernelGGL(k_zero_images<int32_t>, grid, dim3(256), 0, s, static_cast<const int32_t*>(h->key_pointer), n_rows, h->capacity, h->images, h->gate);
-    HIPCHK(h, hipGetLastError());
-    return NL_OK;
-  }
-  if (n > 0 && n_rows > 0) {
-    const Grid<T> g = make_grid<T>(h, h->args, h->plan.pbc);
-    const int32_t cgrid = std::max(1, std::min((n + IMG_THREADS - 1) / IMG_THREADS, 8 * h->num_cus));
-    hipLaunchKernelGGL(k_image_codes<T>, dim3(cgrid), dim3(IMG_THREADS), 0, s, g, static_cast<const T*>(h->args.q), h->args.stride, n, h->img_code, h->img_words);
-    const int32_t chunks = (n_rows + IMG_ROWS - 1) / IMG_ROWS;
-    const int32_t grid = std::max(1, std::min((chunks + 3) / 4, 16 * h->num_cus));
-    if (wide)
-      hipLaunchKernelGGL(k_pair_images<int64_t>, dim3(grid), dim3(IMG_THREADS), 0, s, static_cast<const int64_t*>(h->key_pointer), h->list, n_rows, n,
-                         h->capacity, h->img_code, h->images, h->img_words, h->gate);
-    else
-      hipLaunchKernelGGL(k_pair_images<int32_t>, dim3(grid), dim3(IMG_THREADS), 0, s, static_cast<const int32_t*>(h->key_pointer), h->list, n_rows, n,
-                         h->capacity, h->img_code, h->images, h->img_words, h->gate);
-  }
-  HIPCHK(h, hipGetLastError());
-  return NL_OK;
-}
-
 // (declared at the top of nl_api.hip) The image stage of the handle's build (h->args, h->plan), on stream s.
 int launch_images(nl_handle_t h, int32_t n_rows, hipStream_t s) {
-  return h->dtype == NL_F32 ? launch_images_t<float>(h, n_rows, s) : launch_images_t<double>(h, n_rows, s);
-}
-
-// The two buffers while the flag is on: one word per entry of the list's capacity, one code per particle of n_max.
-int images_reserve(nl_handle_t h) {
-  if (!h->pair_images) return NL_OK;
-  if (!h->img_words) {
-    if (int rc = dev_alloc(h, &h->img_words, sizeof(uint32_t) * IMG_WORDS)) return rc;
-    HIPCHK(h, hipMemset(h->img_words, 0, sizeof(uint32_t) * IMG_WORDS));
-  }
-  if (h->img_rows < (int64_t)h->n_max) {
-    h->img_rows = -1;
-    if (int rc = dev_alloc(h, &h->img_code, 2 * ((size_t)h->n_max + 64))) return rc;
-    h->img_rows = h->n_max;
-  }
-  if (h->img_capacity < h->capacity) {
-    h->img_capacity = -1;
-    if (int rc = dev_alloc(h, &h->images, 4 * ((size_t)h->capacity + 16))) return rc;
-    h->img_capacity = h->capacity;
-  }
-  return NL_OK;
-}
-
-bool images_ready(nl_handle_t h) {
-  return h->images && h->img_code && h->img_words && h->img_rows >= (int64_t)h->n_max && h->img_capacity >= h->capacity;
-}
-
-void images_release(nl_handle_t h) {
-  if (h->images) (void)hipFree(h->images);
-  if (h->img_code) (void)hipFree(h->img_code);
-  if (h->img_words) (void)hipFree(h->img_words);
-  h->images = nullptr, h->img_code = nullptr, h->img_words = nullptr;
-  h->img_capacity = h->img_rows = -1;
-  h->buffers_epoch++;
+  return dispatch_t_off(h, [&](auto t, auto off) -> int {
+    using T = decltype(t);
+    using OFF = decltype(off);
+    const int32_t n = h->args.n;
+    const OFF* kp = static_cast<const OFF*>(h->key_pointer);
+    if (h->plan.pbc == 0) {
+      const int64_t quads = std::max<int64_t>(1, h->capacity / 4);
+      const dim3 grid((uint32_t)std::min<int64_t>((quads + 1023) / 1024, 8 * h->num_cus));
+      hipLaunchKernelGGL(k_zero_images<OFF>, grid, dim3(256), 0, s, kp, n_rows, h->capacity, h->images, h->gate);
+    } else if (n > 0 && n_rows > 0) {
+      const Grid<T> g = make_grid<T>(h, h->args, h->plan.pbc);
+      const int32_t cgrid = std::max(1, std::min((n + STAGE_THREADS - 1) / STAGE_THREADS, 8 * h->num_cus));
+      hipLaunchKernelGGL(k_image_codes<T>, dim3(cgrid), dim3(STAGE_THREADS), 0, s, g, static_cast<const T*>(h->args.q), h->args.stride, n,
+                         h->img_code, h->img_words);
+      hipLaunchKernelGGL(k_pair_images<OFF>, dim3(stage_grid(h, (n_rows + STAGE_ROWS - 1) / STAGE_ROWS)), dim3(STAGE_THREADS), 0, s, kp, h->list,
+                         n_rows, n, h->capacity, h->img_code, h->images, h->img_words, h->gate);
+    }
+    HIPCHK(h, hipGetLastError());
+    return NL_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------- the consumer
@@ -262,25 +167,22 @@ void images_release(nl_handle_t h) {
 // rounded to T once, d = (q_j + S) - q_i with one rounding per operation (components where S is 0 untouched),
 // r2 = (dx^2 + dy^2) + dz^2 without FMA.  status (nl_pair_vectors_enqueue): a list whose build failed gives NaN.
 template <typename T, typename OFF>
-__global__ void __launch_bounds__(IMG_THREADS) k_pair_vectors(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
+__global__ void __launch_bounds__(STAGE_THREADS) k_pair_vectors(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
                                                              const int32_t* __restrict__ list, const uint32_t* __restrict__ images,
                                                              int32_t n_rows, int32_t n, int64_t capacity, T* __restrict__ out, Box box,
                                                              const uint32_t* __restrict__ status) {
   const bool failed = status && *status != 0u;  // (uniform)
   const int lane = threadIdx.x & 63;
-  const int32_t chunks = (n_rows + IMG_ROWS - 1) / IMG_ROWS, waves = gridDim.x * (IMG_THREADS / WAVE);
-  for (int32_t c = blockIdx.x * (IMG_THREADS / WAVE) + (threadIdx.x >> 6); c < chunks; c += waves) {
-    const int32_t r0 = c * IMG_ROWS;
-    ImgRows r;
-    image_rows<OFF>(kp, n_rows, capacity, r0, lane, r);
+  const int32_t chunks = (n_rows + STAGE_ROWS - 1) / STAGE_ROWS, waves = gridDim.x * (STAGE_THREADS / WAVE);
+  for (int32_t c = blockIdx.x * (STAGE_THREADS / WAVE) + (threadIdx.x >> 6); c < chunks; c += waves) {
+    const int32_t r0 = c * STAGE_ROWS;
+    RowChunk r;
+    row_chunk<OFF>(kp, n_rows, capacity, r0, lane, r);
     T xr = (T)0, yr = (T)0, zr = (T)0;  // lane t: the position of row r0 + t
     if (lane < r.nr) load_xyz(q, stride, r0 + lane, xr, yr, zr);
     for (int64_t k = r.b + lane; k - lane < r.e; k += WAVE) {
       const bool valid = k < r.e;
-      int32_t lr = 0;
-#pragma unroll
-      for (int t = 1; t < IMG_ROWS; t++) lr += k >= r.beg[t] ? 1 : 0;
-      lr = min(lr, r.nr - 1);
+      const int32_t lr = chunk_row<OFF>(r, k);
       const T xi = shfl_t(xr, lr), yi = shfl_t(yr, lr), zi = shfl_t(zr, lr);  // (every lane: bpermute)
       if (!valid) continue;
       T d[4];
@@ -315,25 +217,18 @@ __global__ void __launch_bounds__(IMG_THREADS) k_pair_vectors(const T* __restric
   }
 }
 
-template <typename T, typename OFF>
 int pair_vectors_launch(nl_handle_t h, const void* q_dev, int32_t stride, void* out_dev, hipStream_t s, const uint32_t* status) {
   const int32_t n_rows = h->n_rows;
   if (n_rows <= 0) return NL_OK;
-  const int32_t chunks = (n_rows + IMG_ROWS - 1) / IMG_ROWS;
-  const int32_t grid = std::max(1, std::min((chunks + 3) / 4, 16 * h->num_cus));
-  hipLaunchKernelGGL((k_pair_vectors<T, OFF>), dim3(grid), dim3(IMG_THREADS), 0, s, static_cast<const T*>(q_dev), stride,
-                     static_cast<const OFF*>(h->key_pointer), h->list, h->images, n_rows, h->n, h->capacity, static_cast<T*>(out_dev),
-                     h->plan.box, status);  // (the build's box, as k_lj)
-  HIPCHK(h, hipGetLastError());
-  return NL_OK;
-}
-
-int pair_vectors_dispatch(nl_handle_t h, const void* q_dev, int32_t stride, void* out_dev, hipStream_t s, const uint32_t* status) {
-  if (h->plan.wide)
-    return h->dtype == NL_F32 ? pair_vectors_launch<float, int64_t>(h, q_dev, stride, out_dev, s, status)
-                              : pair_vectors_launch<double, int64_t>(h, q_dev, stride, out_dev, s, status);
-  return h->dtype == NL_F32 ? pair_vectors_launch<float, int32_t>(h, q_dev, stride, out_dev, s, status)
-                            : pair_vectors_launch<double, int32_t>(h, q_dev, stride, out_dev, s, status);
+  return dispatch_t_off(h, [&](auto t, auto off) -> int {
+    using T = decltype(t);
+    using OFF = decltype(off);
+    hipLaunchKernelGGL((k_pair_vectors<T, OFF>), dim3(stage_grid(h, (n_rows + STAGE_ROWS - 1) / STAGE_ROWS)), dim3(STAGE_THREADS), 0, s,
+                       static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer), h->list, h->images, n_rows, h->n,
+                       h->capacity, static_cast<T*>(out_dev), h->plan.box, status);  // (the build's box, as k_lj)
+    HIPCHK(h, hipGetLastError());
+    return NL_OK;
+  });
 }
 
 }  // namespace
@@ -377,23 +272,20 @@ int nl_get_pair_images(nl_handle_t h, const int8_t** images_dev, int64_t* nentri
 int nl_pair_vectors(nl_handle_t h, const void* q_dev, int32_t q_stride, void* out_dev, void* stream) {
   if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
   if (!h->pair_images) return fail(h, NL_ERR_STATE);
-  int rc = nl_synchronize(h);  // the list must be complete (and its build must have succeeded)
-  if (rc) return rc;
-  if (!h->plan.images || h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
+  if (int rc = consumer_ready(h, (hipStream_t)stream, false)) return rc;
+  if (!h->plan.images) return fail(h, NL_ERR_STATE);
   HIPCHK(h, hipSetDevice(h->device));
-  return pair_vectors_dispatch(h, q_dev, q_stride, out_dev, (hipStream_t)stream, nullptr);
+  return pair_vectors_launch(h, q_dev, q_stride, out_dev, (hipStream_t)stream, nullptr);
 }
 
 // nl_pair_vectors without the wait: stream-ordered behind the update (or completed build) whose list it reads.
 int nl_pair_vectors_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* out_dev, void* stream) {
   if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
   if (!h->pair_images) return fail(h, NL_ERR_STATE);
-  hipStream_t s = (hipStream_t)stream;
-  if (!h->pending && !h->built) return fail(h, NL_ERR_STATE);  // no build, or one the host has seen fail
-  if (h->pending && (!h->last_update || s != h->last_stream)) return fail(h, NL_ERR_STATE);
-  if (!h->plan.images || h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);  // ids must index q
+  if (int rc = consumer_ready(h, (hipStream_t)stream, true)) return rc;
+  if (!h->plan.images) return fail(h, NL_ERR_STATE);
   HIPCHK(h, hipSetDevice(h->device));
-  return pair_vectors_dispatch(h, q_dev, q_stride, out_dev, s, h->status);
+  return pair_vectors_launch(h, q_dev, q_stride, out_dev, (hipStream_t)stream, h->status);
 }
 
 }  // extern "C"

@@ -155,10 +155,8 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIPCHK(h, hipStreamIsCapturing(s, &cap));
   const bool capturing = cap != hipStreamCaptureStatusNone;
-  if (filter_tables(h) && !capturing)  // (again, if an allocation failed since the table was set)
-    if (int rc = excl_reserve(h)) return rc;
-  if (!capturing)
-    if (int rc = images_reserve(h)) return rc;
+  if (!capturing)  // (again, if an allocation failed since a table or the flag was set)
+    if (int rc = stage_reserve(h)) return rc;
   // (a): what forces a build before any particle is looked at -- no list of an update to keep (a setter, nl_resort or
   // another kind of build since, the host has seen the last build fail), or other positions
   const bool force = !h->upd_valid || q_dev != h->upd_q || q_stride != h->upd_stride || n != h->upd_n || (!h->pending && !h->built);
