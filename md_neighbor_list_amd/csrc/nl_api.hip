@@ -87,10 +87,12 @@ struct BuildPlan {
   int32_t pbc = 0;      // axes of the minimum image (nl_set_periodic_axes)
   int32_t idc = 0;      // SEARCH_MASKS with id classes (k_sweep_class_f32, k_fill_masks<IDC>): C = 2 or 4 classes, 0 = off
   int32_t id_shift = 0; // class of an id: id >> id_shift
+  bool id_rows = false; // no caller ids, no tilt, the two-level binning: the id of a particle is its input row, so sorted_row
+                        // is the compact id array as well (tmp_row and sorted_gid are neither written nor read)
   Box box = {{0, 0, 0}, 0, 0, 0};  // the box of the build (nl_set_box): what its consumers (k_lj, the skin check) fold with
   int32_t tilt = 0;     // box.xy, box.xz or box.yz is not 0: binning and search in sheared coordinates
   auto tie() const {
-    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, images, pbc, idc, id_shift,
+    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, images, pbc, idc, id_shift, id_rows,
                     box.L[0], box.L[1], box.L[2], box.xy, box.xz, box.yz, tilt);
   }
   bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
@@ -541,7 +543,7 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   SweepArgs<T> a;
   a.sorted = static_cast<const Pos<T>*>(h->sorted);
   a.sorted_row = h->sorted_row;
-  a.sorted_gid = h->sorted_gid;
+  a.sorted_gid = h->plan.id_rows ? h->sorted_row : h->sorted_gid;
   a.cell_start = h->cell_start;
   a.cls_start = h->cls_start;
   a.mx = h->m[0], a.my = h->m[1], a.mzl = h->args.mzl, a.slab = h->args.slab;
@@ -579,7 +581,7 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
 RowsArgs rows_args(nl_handle_t h) {
   RowsArgs a;
   a.sorted = static_cast<const Pos<float>*>(h->sorted);
-  a.sorted_row = h->sorted_row, a.sorted_gid = h->sorted_gid;
+  a.sorted_row = h->sorted_row, a.sorted_gid = h->plan.id_rows ? h->sorted_row : h->sorted_gid;
   a.fine_start = h->cell_start;
   a.mx = h->m[0], a.my = h->m[1], a.mzl = h->args.mzl, a.slab = h->args.slab;
   a.div_mx = fastdiv_make((uint32_t)h->m[0]), a.div_my = fastdiv_make((uint32_t)h->m[1]);
@@ -638,9 +640,12 @@ template <typename T, bool FULL, bool PBC, typename OFF> void launch_search(nl_h
       if (mode == MODE_COUNT) {
         if constexpr (F32_OPEN) {
           // a workgroup per cell, single-batch cells only; the others go on the hand-over list of the batched search
-          if (p.small) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, 2, LEAN_SMALL_CAP>), cells, dim3(2 * WAVE), 0, s, a);
+          constexpr int CAP = SweepCfg<float>::CAP;
+          if (p.small && p.id_rows) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, 2, LEAN_SMALL_CAP, true>), cells, dim3(2 * WAVE), 0, s, a);
+          else if (p.small) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, 2, LEAN_SMALL_CAP>), cells, dim3(2 * WAVE), 0, s, a);
           else if (!FULL && p.idc == 2) hipLaunchKernelGGL((k_sweep_class_f32<2>), cells, wg, 0, s, a);
           else if (!FULL && p.idc == 4) hipLaunchKernelGGL((k_sweep_class_f32<4>), cells, wg, 0, s, a);
+          else if (p.id_rows) hipLaunchKernelGGL((k_sweep_lean_f32<FULL, SWEEP_WAVES, CAP, true>), cells, wg, 0, s, a);
           else hipLaunchKernelGGL((k_sweep_lean_f32<FULL>), cells, wg, 0, s, a);
           if (p.list) hipLaunchKernelGGL((k_sweep_list_f32<FULL>), list_grid, wg, 0, s, a);
         } else {
@@ -833,6 +838,9 @@ template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, in
   p.list = !again_ok || h->list_quiet < LIST_QUIET_BUILDS;
   p.cap_row = again_ok ? bucket_cap<T>(h, n, a.mzl) : 0;
   p.binning = !two_level ? BINNING_ATOMIC : p.cap_row > 0 ? BINNING_BUCKET : BINNING_TWO_PASS;
+  // ids that are input rows: no caller ids (a slab or distributed build passes them), no tilt (a tilted build parks the
+  // x-cell in the id slot of tmp and needs tmp_row), the row-wise binning
+  p.id_rows = !a.gid && !p.tilt && p.binning != BINNING_ATOMIC;
   // id classes (NL_IDCLASS; k_sweep_class_f32): where they are exact and simple -- the fp32 half list of the one-batch
   // 4-wave path in an open box, ids 0..n-1 (no caller ids), a whole build (no slab, no distributed build), the
   // row-wise binning that writes the class table (k_bin_cells), and a mesh of at least 3 cells a side (27 distinct
@@ -861,21 +869,34 @@ void adopt_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p) {
 
 // k_bin_bucket / k_bin_scatter keep 8 particles a thread in flight where a chunk is 8 per thread, else 4.  (k_bin_bucket
 // in fp32 only: 127 VGPRs; fp64 would spill, and reads its chunk twice instead.)
+// The second argument of `launch`: the IDROW instance (BuildPlan::id_rows).
 template <typename T, bool BUCKET, typename L> void launch_unrolled(nl_handle_t h, L&& launch) {
+  auto by_id = [&](auto u) {
+    if (h->plan.id_rows) launch(u, std::true_type());
+    else launch(u, std::false_type());
+  };
   if constexpr (sizeof(T) == 4 || !BUCKET) {
-    if (h->bin_chunk >= 8 * BIN_THREADS) return launch(std::integral_constant<int, 8>());
+    if (h->bin_chunk >= 8 * BIN_THREADS) return by_id(std::integral_constant<int, 8>());
   }
-  launch(std::integral_constant<int, 4>());
+  by_id(std::integral_constant<int, 4>());
 }
 
 // k_bin_cells: the particles of the rows into cell order, with the fine-row table (FINE) for the fine-row search
 template <typename T>
 void launch_bin_cells(nl_handle_t h, const Grid<T>& g, int32_t grid, int32_t nrows, const int32_t* row_start, const BinPhase& ph,
                       int32_t cap_row, hipStream_t s) {
-  auto launch = [&](auto fine, auto idc) {
-    hipLaunchKernelGGL((k_bin_cells<T, decltype(fine)::value, decltype(idc)::value>), dim3(grid), dim3(256), 0, s, g, nrows, row_start,
+  auto launch_as = [&](auto fine, auto idc, auto idrow) {
+    hipLaunchKernelGGL((k_bin_cells<T, decltype(fine)::value, decltype(idc)::value, decltype(idrow)::value>), dim3(grid), dim3(256), 0, s, g, nrows, row_start,
                        static_cast<const Pos<T>*>(h->tmp_pos), h->tmp_row, h->cell_start, static_cast<Pos<T>*>(h->sorted),
                        h->sorted_row, h->sorted_gid, ph, cap_row, h->cls_start, h->plan.id_shift);
+  };
+  auto launch = [&](auto fine, auto idc) {
+    if constexpr (decltype(idc)::value > 0) {
+      launch_as(fine, idc, std::true_type());  // (an id-class build has no caller ids)
+    } else {
+      if (h->plan.id_rows) launch_as(fine, idc, std::true_type());
+      else launch_as(fine, idc, std::false_type());
+    }
   };
   if constexpr (sizeof(T) == 4) {
     if (h->plan.search == SEARCH_ROWS) return launch(std::true_type(), std::integral_constant<int, 0>());
@@ -910,8 +931,8 @@ int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStre
     if (events) (void)hipEventRecord(ev[NL_STAGE_CELL_SCAN], s);
     // (no scan launch: every block of k_bin_scatter scans the row totals itself and block 0 publishes the row starts)
     if (events) (void)hipEventRecord(ev[NL_STAGE_REORDER], s);
-    launch_unrolled<T, false>(h, [&](auto u) {
-      hipLaunchKernelGGL((k_bin_scatter<T, decltype(u)::value>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, a.stride, a.gid, n,
+    launch_unrolled<T, false>(h, [&](auto u, auto idrow) {
+      hipLaunchKernelGGL((k_bin_scatter<T, decltype(u)::value, decltype(idrow)::value>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, a.stride, a.gid, n,
                          h->bin_chunk, g, nrows, rc_arr, rs_arr, h->blk_base, static_cast<Pos<T>*>(h->tmp_pos), h->tmp_row,
                          h->status, ph);
     });
@@ -924,8 +945,8 @@ int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStre
       // one pass into the row buckets; k_bin_bucket also starts the meta words and leaves its cursors at zero
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
       const int32_t blocks = std::max(1, (n + h->bin_chunk - 1) / h->bin_chunk);
-      launch_unrolled<T, true>(h, [&](auto u) {
-        hipLaunchKernelGGL((k_bin_bucket<T, decltype(u)::value>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, a.stride, a.gid, n,
+      launch_unrolled<T, true>(h, [&](auto u, auto idrow) {
+        hipLaunchKernelGGL((k_bin_bucket<T, decltype(u)::value, decltype(idrow)::value>), dim3(blocks), dim3(BIN_THREADS), 0, s, q, a.stride, a.gid, n,
                            h->bin_chunk, g, nrows, p.cap_row, h->row_cursor, h->row_start, static_cast<Pos<T>*>(h->tmp_pos),
                            h->tmp_row, h->status);
       });

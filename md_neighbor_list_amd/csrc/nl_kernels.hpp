@@ -558,7 +558,8 @@ __device__ __forceinline__ void bin_load_trip(const T* __restrict__ q, int32_t s
 // UNROLL: particles per thread whose loads are in flight together: 8 where a chunk is 8 particles per thread (one round
 // trip per chunk: binning 2 + 3 at cfg 2 41.6 -> 38.1 us), 4 for the smaller chunks of small boxes.  (k_bin_rows is
 // 1 us slower with 8.)
-template <typename T, int UNROLL = BIN_UNROLL>
+// IDROW (BuildPlan::id_rows: no caller ids, so a particle's id is its input row): tmp_row is not written.
+template <typename T, int UNROLL = BIN_UNROLL, bool IDROW = false>
 __global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(const T* __restrict__ q, int32_t stride,
                                                              const int32_t* __restrict__ gid, int32_t n, int32_t chunk,
                                                              Grid<T> g, int32_t nrows, const int32_t* __restrict__ row_count,
@@ -628,7 +629,7 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(const T* __restrict
       }
       if constexpr (sizeof(T) == 8) p.row = i;
       tmp[dst] = p;
-      tmp_row[dst] = i;
+      if constexpr (!IDROW) tmp_row[dst] = i;
     }
   }
 }
@@ -648,7 +649,8 @@ constexpr int META_BIN_DONE = 21;    // blocks of k_bin_bucket through with thei
 // packed as the two-pass binning places them), sets the cursors back to zero for the next build and starts the
 // build's meta words: status = what the binning raised, tickets zero.  No memset per build; graph replays included.
 // Chunks of more than UNROLL particles per thread read their positions twice (the histogram, then the placement).
-template <typename T, int UNROLL>
+// IDROW: as in k_bin_scatter.
+template <typename T, int UNROLL, bool IDROW = false>
 __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict__ q, int32_t stride,
                                                             const int32_t* __restrict__ gid, int32_t n, int32_t chunk,
                                                             Grid<T> g, int32_t nrows, int32_t cap_row,
@@ -760,7 +762,7 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
     if constexpr (sizeof(T) == 8) p.row = i;
     const size_t k = (size_t)r * cap_row + dst;
     tmp[k] = p;
-    tmp_row[k] = i;
+    if constexpr (!IDROW) tmp_row[k] = i;
   };
   if (keep) {
 #pragma unroll
@@ -792,8 +794,11 @@ __global__ void __launch_bounds__(BIN_THREADS) k_bin_bucket(const T* __restrict_
 // stays one run of the sorted array (cell_start keeps its meaning for every reader), and the class table
 // cls_start[(r * mx + cx) * IDC + class] (IDC M + 1 entries) gives where each class of the cell begins: entry e + 1 is
 // where the run of entry e ends.
+//
+// IDROW (BuildPlan::id_rows): the id of a particle is its input row, so tmp_row is not read, and sorted_row -- which
+// then also serves as the compact id array (sweep_args) -- is the one 4-byte array written; sorted_gid is left alone.
 constexpr int BIN_FINE_MAX_MX = 2048;
-template <typename T, bool FINE = false, int IDC = 0>
+template <typename T, bool FINE = false, int IDC = 0, bool IDROW = false>
 __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, const int32_t* __restrict__ row_start,
                                                    const Pos<T>* __restrict__ tmp, const int32_t* __restrict__ tmp_row,
                                                    int32_t* __restrict__ cell_start, Pos<T>* __restrict__ sorted,
@@ -833,7 +838,7 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
   };
   // triclinic (plain rows only: the fine-row and id-class builds are open-box): the row pass decided the x-cell from
   // the input coordinate and left it in the id slot; a tilted build has no slab ids, so the id is the input row
-  const bool tilt = !FINE && IDC == 0 && g.tilt;
+  const bool tilt = !FINE && IDC == 0 && !IDROW && g.tilt;
   auto bin_of = [&](const Pos<T>& p) {
     const int32_t c = tilt ? p.gid : xcell1(p.x);
     if constexpr (FINE) return quarter(p.z, g.ims[2]) * mx + c;
@@ -851,11 +856,12 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
     for (int u = 0; u < BC_KEEP; u++) {
       const int32_t k = min(beg + tid + u * 256, end - 1);
       pk[u] = src[k];
-      rk[u] = src_row[k];
+      if constexpr (!IDROW) rk[u] = src_row[k];
     }
 #pragma unroll
     for (int u = 0; u < BC_KEEP; u++) {
-      keep_in_flight(pk[u].x), keep_in_flight(pk[u].y), keep_in_flight(pk[u].z), keep_in_flight(pk[u].gid), keep_in_flight(rk[u]);
+      keep_in_flight(pk[u].x), keep_in_flight(pk[u].y), keep_in_flight(pk[u].z), keep_in_flight(pk[u].gid);
+      if constexpr (!IDROW) keep_in_flight(rk[u]);
       if constexpr (sizeof(T) == 8) keep_in_flight(pk[u].row);
     }
 #pragma unroll
@@ -909,14 +915,17 @@ __global__ void __launch_bounds__(256) k_bin_cells(Grid<T> g, int32_t nrows, con
     }
     sorted[dst] = p;
     sorted_row[dst] = row_of;
-    sorted_gid[dst] = p.gid;  // the ids alone, 4 bytes apart: what the expansion kernel stages
+    if constexpr (!IDROW) sorted_gid[dst] = p.gid;  // the ids alone, 4 bytes apart: what the expansion kernel stages
   };
   if (keep) {
 #pragma unroll
     for (int u = 0; u < BC_KEEP; u++)
-      if (beg + tid + u * 256 < end) place(pk[u], rk[u]);
+      if (beg + tid + u * 256 < end) place(pk[u], IDROW ? pk[u].gid : rk[u]);
   } else {
-    for (int32_t k = beg + tid; k < end; k += 256) place(src[k], src_row[k]);
+    for (int32_t k = beg + tid; k < end; k += 256) {
+      const Pos<T> p = src[k];
+      place(p, IDROW ? p.gid : src_row[k]);
+    }
   }
 }
 

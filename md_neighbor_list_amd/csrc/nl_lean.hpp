@@ -62,8 +62,9 @@ __device__ __forceinline__ void pipe_group(const SweepArgs<float>& a, const Pos<
   for (int k = 0; k < GC; k++) p.w[k] = words[k];
 }
 
-// The pair search of the single-batch cell c, whose stream is in `tile`.
-template <bool FULL, int NW = SWEEP_WAVES>
+// The pair search of the single-batch cell c, whose stream is in `tile`.  IDROW (BuildPlan::id_rows): the id of a
+// particle is its input row, so the rows of a group come with its particles from the staged stream.
+template <bool FULL, int NW = SWEEP_WAVES, bool IDROW = false>
 __device__ __forceinline__ void pipe_search(const SweepArgs<float>& a, const CellCtx& c, const Pos<float>* tile, int lane, int wave,
                                             PipePending& p) {
   constexpr int G = PIPE_G;
@@ -85,7 +86,9 @@ __device__ __forceinline__ void pipe_search(const SweepArgs<float>& a, const Cel
     pipe_flush<NW == SWEEP_WAVES>(a, p, lane, hi_plane_used(a.mask_nb, ntiles));  // (a wave with several groups: the previous one's words go out before the next search)
     const int32_t k = min(lane, gcount - 1);
     Pos<float> pi_l = tile[own + i0 + k];  // the group's i-particles come from the staged stream, not from memory
-    const int32_t row_l = a.sorted_row[ibeg + i0 + k];
+    int32_t row_l;
+    if constexpr (IDROW) row_l = pi_l.gid;
+    else row_l = a.sorted_row[ibeg + i0 + k];
     if (lane >= gcount) pi_l.x = 0, pi_l.y = 0, pi_l.z = 0, pi_l.gid = 0;
     const int32_t slot0 = ibeg + i0, self0 = own + i0;
     switch (gcount) {
@@ -109,7 +112,7 @@ __device__ __forceinline__ void pipe_search(const SweepArgs<float>& a, const Cel
 // number of group passes per cell by half as many waves, i.e. half as many cell tables, barriers and flushes (what a
 // wave does besides searching is half of its life when its search is one pass of 9 tiles).
 constexpr int LEAN_SMALL_CAP = SweepCfg<float>::CAP / 2;
-template <bool FULL, int NW = SWEEP_WAVES, int CAP = SweepCfg<float>::CAP>
+template <bool FULL, int NW = SWEEP_WAVES, int CAP = SweepCfg<float>::CAP, bool IDROW = false>
 __global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80))) k_sweep_lean_f32(SweepArgs<float> a) {
   if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   __shared__ __attribute__((aligned(32))) Pos<float> buf[CAP];
@@ -125,7 +128,7 @@ __global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   PipePending pend;
   pend.gcount = 0, pend.mine = 0, pend.row_l = 0, pend.slot0 = 0;
-  pipe_search<FULL, NW>(a, c, buf, lane, wave, pend);
+  pipe_search<FULL, NW, IDROW>(a, c, buf, lane, wave, pend);
   pipe_flush<NW == SWEEP_WAVES>(a, pend, lane, hi_plane_used(a.mask_nb, (c.total_j + WAVE - 1) / WAVE));
 }
 
@@ -238,7 +241,7 @@ __device__ __forceinline__ void class_search(const SweepArgs<float>& a, const Cl
       pipe_flush<NW == SWEEP_WAVES>(a, p, lane, hi);
       const int32_t kk = min(lane, gcount - 1);
       Pos<float> pi_l = tile[own + i0 + kk];  // from the staged stream
-      const int32_t row_l = a.sorted_row[slot_b + i0 + kk];
+      const int32_t row_l = pi_l.gid;  // (an id-class build has no caller ids: the id is the input row)
       if (lane >= gcount) pi_l.x = 0, pi_l.y = 0, pi_l.z = 0, pi_l.gid = 0;
       switch (gcount) {
         case 1: class_pipe_group<1>(a, tile, t0, tsplit, ntiles, lane, pi_l, p); break;
