@@ -458,7 +458,14 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream);
  * list was built from (or moved by less than the skin), same dtype and stride; f_dev: n x 4 values of that dtype,
  * {fx, fy, fz, pe_i} with pe_i = half the pair energies of particle i; pairs beyond rc_force (<= the list's cut-off)
  * are skipped; distances are taken as the list took them: between the coordinates as given (open box, the reference's
- * rule) or at the minimum image on the axes of the build's nl_set_periodic_axes mask, each component on its own.  After a NL_LIST_FULL build every row gathers its partners and
+ * rule) or at the minimum image on the axes of the build's nl_set_periodic_axes mask, each component on its own.
+ * Positions may lie up to one box length outside the box, as for the builds (positions that drift and are never wrapped,
+ * nl_update_list with nl_set_pair_images): the separation is taken with its rounding error and folded with rint,
+ * d -= L rint(d / L) in z, y, x order with the tilts, so a force does not depend on which image a coordinate sits in.
+ * The box is the build's, rounded to the position type like everything the library does with it.
+ * Tested contract (tests/test_lj_consumer.py): every component of every particle within c u S of an O(N^2) float64 sum,
+ * S the uncancelled sum of that component's pair terms, u the unit roundoff of the position type; rc_force is exact for
+ * pairs further than 64 ulp (in r) from it.  After a NL_LIST_FULL build every row gathers its partners and
  * writes its force once; after a NL_LIST_HALF build every pair is evaluated once and the reaction is added to the
  * partner with floating-point atomics (f_dev is zeroed first).  Enqueued on `stream` (NULL = the null stream);
  * waits for the build first. */
@@ -472,7 +479,7 @@ int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, dou
                          void* f_dev, void* stream);
 /* Typed Lennard-Jones for a list built with a type table: epsilon, sigma and rc_force of a pair are [t_i][t_j] of
  * ntypes x ntypes row-major, exactly symmetric matrices (sigma > 0, rc_force > 0, rc_force_ab <= rc_ab, finite
- * epsilon; else NL_ERR_ARG).  nl_set_lj_type_params copies them to the device synchronously; its ntypes must be the type
+ * epsilon; else NL_ERR_ARG).  A pair of types with rc_ab = 0 has no entries: its rc_force_ab is 0, and it adds nothing.  nl_set_lj_type_params copies them to the device synchronously; its ntypes must be the type
  * table's (NL_ERR_STATE without a table).  nl_lj_forces_typed(_enqueue) compute what nl_lj_forces(_enqueue) compute,
  * with the same lists, masks, NaN rule and ordering, from those parameters; NL_ERR_STATE while the table or the
  * parameters are missing, NL_ERR_ARG when they no longer match (ntypes, rc_force_ab > rc_ab), and the enqueue variant

@@ -20,31 +20,62 @@ template <typename T> __device__ __forceinline__ void lj_pair(T dx, T dy, T dz, 
   pe = eps4 * (s6 - (T)1) * s6;
 }
 
-// The image of a pair of the list's build.  Orthogonal box: one half-box test per periodic axis (L > 0; 0 = open axis).
-// Triclinic box (TRI: nl_set_box with a tilt): fold z, y, x in T with rint, as the skin check does in double -- one test per
-// axis is not enough there (after the z fold dy can exceed 1.5 Ly once yz is large).  Every component of the image within rc
-// is below L_d / 2, so this finds the image the list used.
+// The image of a pair of the list's build: d = r_i - r_j folded on the periodic axes (L > 0; 0 = open axis) in z, y, x order,
+// k_z = rint(dz / Lz), k_y = rint((dy - k_z yz) / Ly), k_x = rint((dx - k_z xz - k_y xy) / Lx) -- the rule of the skin check,
+// in T.  Positions may lie up to one box length outside the box, as for the builds (drifted and never re-wrapped: nl_update_list
+// with nl_set_pair_images), so a raw separation reaches +-3 L: one half-box test per axis is not enough, and neither is the
+// rounded raw separation, whose error (half an ulp of 3 L) would make the forces depend on the image the caller's coordinates
+// sit in.  So the separation is taken with its rounding error (two_diff: d + lo = r_i - r_j exactly), the lattice vector is
+// taken off d with fma, the largest term first (exact for k L: the result is a multiple of ulp(L) below L / 2), and lo is added
+// to the small result.  With a tilt a step can leave more than it found (dy = 3, k_z yz = -8.3: k_y = 1 and dy - Ly = -15.1, coarser
+// than dy's own grid), so there every term of y and x goes through sub_kl, which keeps the step's rounding error in lo as well;
+// z has no tilt and stays on the fma.  Every component of the image within rc is below L_d / 3 (mesh >= 3), so d / L is never near a
+// half-integer: the reciprocal (loop-invariant) picks the same k, and this is the image the list used.
 template <typename T> __device__ __forceinline__ T rint_t(T v) {
   if constexpr (sizeof(T) == 4) return rintf(v);
   else return rint(v);
 }
+template <typename T> __device__ __forceinline__ T fma_t(T a, T b, T c) {
+  if constexpr (sizeof(T) == 4) return fmaf(a, b, c);
+  else return fma(a, b, c);
+}
+template <typename T> __device__ __forceinline__ T two_diff(T a, T b, T& lo) {
+  const T d = a - b, bv = d - a;
+  lo = (a - (d - bv)) - (b + bv);
+  return d;
+}
+// d + lo -= k m, exactly up to the rounding of lo (k m = p + pe and d - p = d' + e, both without error)
+template <typename T> __device__ __forceinline__ void sub_kl(T k, T m, T& d, T& lo) {
+  const T p = k * m, pe = fma_t(k, m, -p);
+  T e;
+  d = two_diff(d, p, e);
+  lo += e - pe;
+}
 template <typename T, bool TRI>
-__device__ __forceinline__ void lj_image(T& dx, T& dy, T& dz, T Lx, T Ly, T Lz, T xy, T xz, T yz) {
-  if constexpr (TRI) {
-    if (Lz > (T)0) {
-      const T k = rint_t(dz / Lz);
-      dz = dz - k * Lz, dy = dy - k * yz, dx = dx - k * xz;
-    }
-    if (Ly > (T)0) {
-      const T k = rint_t(dy / Ly);
-      dy = dy - k * Ly, dx = dx - k * xy;
-    }
-    if (Lx > (T)0) dx = dx - rint_t(dx / Lx) * Lx;
-  } else {
-    if (Lx > (T)0) dx = dx > (T)0.5 * Lx ? dx - Lx : dx < (T)-0.5 * Lx ? dx + Lx : dx;
-    if (Ly > (T)0) dy = dy > (T)0.5 * Ly ? dy - Ly : dy < (T)-0.5 * Ly ? dy + Ly : dy;
-    if (Lz > (T)0) dz = dz > (T)0.5 * Lz ? dz - Lz : dz < (T)-0.5 * Lz ? dz + Lz : dz;
+__device__ __forceinline__ void lj_image(T xi, T yi, T zi, T xj, T yj, T zj, T& dx, T& dy, T& dz, T Lx, T Ly, T Lz, T xy, T xz,
+                                         T yz) {
+  if (!(Lx > (T)0 || Ly > (T)0 || Lz > (T)0)) {  // open box (uniform): the coordinates as given
+    dx = xi - xj, dy = yi - yj, dz = zi - zj;
+    return;
   }
+  T lx, ly, lz;
+  dx = two_diff(xi, xj, lx), dy = two_diff(yi, yj, ly), dz = two_diff(zi, zj, lz);
+  const T iLx = Lx > (T)0 ? (T)1 / Lx : (T)0, iLy = Ly > (T)0 ? (T)1 / Ly : (T)0, iLz = Lz > (T)0 ? (T)1 / Lz : (T)0;
+  const T kz = rint_t(dz * iLz);
+  T ty = dy, tx = dx;
+  if constexpr (TRI) ty = ty - kz * yz, tx = tx - kz * xz;
+  const T ky = rint_t(ty * iLy);
+  if constexpr (TRI) tx = tx - ky * xy;
+  const T kx = rint_t(tx * iLx);
+  dz = fma_t(-kz, Lz, dz);
+  if constexpr (TRI) {
+    sub_kl(ky, Ly, dy, ly), sub_kl(kz, yz, dy, ly);
+    sub_kl(kx, Lx, dx, lx), sub_kl(ky, xy, dx, lx), sub_kl(kz, xz, dx, lx);
+  } else {
+    dy = fma_t(-ky, Ly, dy);
+    dx = fma_t(-kx, Lx, dx);
+  }
+  dx += lx, dy += ly, dz += lz;
 }
 
 // Where a pair's parameters come from: the launch's scalars, or a table over the types of the pair (nl_set_lj_type_params).
@@ -99,10 +130,10 @@ __device__ __forceinline__ void lj_row(const T* __restrict__ q, int32_t stride, 
     load_xyz(q, stride, j, xj, yj, zj);
     T fx, fy, fz, pe;
     bool in;
-    T dx = xi - xj, dy = yi - yj, dz = zi - zj;
+    T dx, dy, dz;
     // minimum-image list (nl_set_periodic_axes): on a periodic axis (L > 0) the pair is taken at the image the list
     // found it at
-    lj_image<T, TRI>(dx, dy, dz, Lx, Ly, Lz, xy, xz, yz);
+    lj_image<T, TRI>(xi, yi, zi, xj, yj, zj, dx, dy, dz, Lx, Ly, Lz, xy, xz, yz);
     lj_pair<T>(dx, dy, dz, e4, s2, c2, fx, fy, fz, pe, in);
     ax += fx, ay += fy, az += fz, ae += (T)0.5 * pe;
     if (HALF && in) {  // Newton's third law: the partner's share
@@ -180,8 +211,10 @@ int lj_typed_check(nl_handle_t h, double skin) {
   if (!h->ty_types || !h->lj_par) return fail(h, NL_ERR_STATE);
   if (h->lj_ntypes != h->ty_ntypes) return fail(h, NL_ERR_ARG);
   const int32_t nt = h->ty_ntypes;
-  for (int32_t k = 0; k < nt * nt; k++)
+  for (int32_t k = 0; k < nt * nt; k++) {
+    if (h->ty_rc[k] == 0.0 && h->lj_rcf[k] == 0.0) continue;  // (a pair of types the list leaves out)
     if (!(h->lj_rcf[k] <= h->ty_rc[k] - skin)) return fail(h, NL_ERR_ARG);
+  }
   return NL_OK;
 }
 

@@ -301,7 +301,9 @@ int nl_set_lj_type_params(nl_handle_t h, int32_t ntypes, const double* epsilon, 
   for (int32_t a = 0; a < ntypes; a++)
     for (int32_t b = 0; b < ntypes; b++) {
       const int32_t k = a * ntypes + b, t = b * ntypes + a;
-      if (!std::isfinite(epsilon[k]) || !(sigma[k] > 0) || !std::isfinite(sigma[k]) || !(rc_force[k] > 0) ||
+      // (a pair of types the list leaves out, rc_ab = 0, takes rc_force_ab = 0: no entry, no force)
+      const bool unlisted = h->ty_rc[k] == 0.0 && rc_force[k] == 0.0;
+      if (!std::isfinite(epsilon[k]) || !(sigma[k] > 0) || !std::isfinite(sigma[k]) || !(rc_force[k] > 0 || unlisted) ||
           !(rc_force[k] <= h->ty_rc[k]) || epsilon[k] != epsilon[t] || sigma[k] != sigma[t] || rc_force[k] != rc_force[t])
         return fail(h, NL_ERR_ARG);
     }

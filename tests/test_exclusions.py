@@ -14,7 +14,7 @@ import pytest
 
 from md_neighbor_list_amd import inputs
 from tests.test_periodic_axes import positions, reference
-from tests.util import ROOT, canonical_csr, load_golden
+from tests.util import ROOT, canonical_csr, check_lj, lj_pair_magnitudes, lj_rows_off_the_band, load_golden
 
 BOX = (27.0, 24.0, 40.0)
 RC = 3.3
@@ -599,10 +599,10 @@ def test_lj_forces(dtype, full):
         pe = 4.0 * (s6 * s6 - s6)
         np.add.at(out[:, 3], rows, 0.5 * pe)
         np.add.at(out[:, 3], cols, 0.5 * pe)
-        return out
+        return out, lj_pair_magnitudes(n, rows, cols, d, r2), lj_rows_off_the_band(n, rows, cols, r2, rc, dtype)
 
     _, kp_w, lst_w = remove_pairs(kp, lst, pairs)
-    want, plain = lj(kp_w, lst_w), lj(kp, lst)
+    (want, S, off_band), plain = lj(kp_w, lst_w), lj(kp, lst)[0]
     nl = _handle(n, dtype, 0, full, rc, box)
     nl.set_exclusions(pairs, n)
     qd = _build(nl, q)
@@ -611,6 +611,8 @@ def test_lj_forces(dtype, full):
     tol = 2e-4 if dtype == np.float32 else 1e-11
     assert np.all(np.abs(got - want) <= tol * scale), (np.abs(got - want) / scale).max(axis=0)
     assert np.abs(plain - want).max() > 100 * tol * scale.max()
+    # and per particle and component within c u S (tests/test_lj_consumer.py), off the 64-ulp band of rc_force = rc
+    check_lj(got, want, S, dtype, rows=off_band)
 
 
 @pytest.mark.gpu

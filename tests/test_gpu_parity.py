@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from md_neighbor_list_amd import inputs
-from tests.util import GOLDEN, canonical_csr, golden_names, gpu_build, load_golden
+from tests.util import (GOLDEN, canonical_csr, check_lj, golden_names, gpu_build, lj_list_separations, lj_pair_magnitudes,
+                        lj_rows_off_the_band, load_golden)
 
 pytestmark = pytest.mark.gpu
 
@@ -497,10 +498,9 @@ def test_lj_forces_from_the_list(dtype, full, pbc):
     ref = _po().build_pbc(q, rc, box) if pbc else _po().build(q, rc, box)
     rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ref.key_pointer))
     cols = ref.sorted_list.astype(np.int64)
-    d = q[rows, :3].astype(np.float64) - q[cols, :3].astype(np.float64)
+    # (folded before it is rounded: the float64 difference across a face would carry half an ulp of L into the forces)
+    d = lj_list_separations(q, rows, cols, (*box, 0.0, 0.0, 0.0), 7 if pbc else 0)
     if pbc:
-        L = np.array(box, dtype=np.float64)
-        d -= L * np.round(d / L)
         assert np.any(np.abs(q[rows, :3].astype(np.float64) - q[cols, :3].astype(np.float64)).max(axis=1) > 16.0)
     r2 = (d * d).sum(axis=1)
     keep = r2 > 0.64
@@ -529,6 +529,10 @@ def test_lj_forces_from_the_list(dtype, full, pbc):
     scale = np.abs(want[ok]).max(axis=0)
     tol = 2e-4 if dtype == np.float32 else 1e-11
     assert np.all(np.abs(got[ok] - want[ok]) <= tol * scale), (np.abs(got[ok] - want[ok]) / scale).max(axis=0)
+    # and per particle and component, within c u S of the same sum (tests/test_lj_consumer.py); rc_force is the list's rc
+    # here, so particles with a partner within 64 ulp of it are left to the assertion above
+    S = lj_pair_magnitudes(n, rows, cols, d, r2)
+    check_lj(got, want, S, dtype, rows=ok & lj_rows_off_the_band(n, rows, cols, r2, rc, dtype))
 
 
 def test_md_loop_with_skin_rebuilds_and_resorting(monkeypatch):

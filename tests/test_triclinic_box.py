@@ -13,7 +13,7 @@ import itertools
 import numpy as np
 import pytest
 
-from tests.util import canonical_csr
+from tests.util import canonical_csr, check_lj, lj_list_separations, lj_pair_magnitudes, lj_rows_off_the_band
 
 CFG2_L = 101.594  # BASELINE config 2 box
 RC = 3.3
@@ -518,18 +518,8 @@ def test_graph_replay_across_set_box_and_resort():
     _check(nl, qd.cpu().numpy(), box2, 7, dtype)
 
 
-def _lj_reference(q, rows, parts, box, eps, sig, rcf):
-    p = q[:, :3].astype(np.float64)
-    d = p[rows] - p[parts]
-    Lx, Ly, Lz, xy, xz, yz = box
-    k = np.rint(d[:, 2] / Lz)
-    d[:, 2] -= k * Lz
-    d[:, 1] -= k * yz
-    d[:, 0] -= k * xz
-    k = np.rint(d[:, 1] / Ly)
-    d[:, 1] -= k * Ly
-    d[:, 0] -= k * xy
-    d[:, 0] -= np.rint(d[:, 0] / Lx) * Lx
+def _lj_reference(q, rows, parts, box, eps, sig, rcf, with_bound=False):
+    d = lj_list_separations(q, rows, parts, box, 7)  # (z, y, x order with the tilts; folded before it is rounded to float64)
     r2 = (d * d).sum(axis=1)
     inn = (r2 < rcf * rcf) & (r2 > 0)
     ir2 = np.where(inn, sig * sig / r2, 0.0)
@@ -542,6 +532,10 @@ def _lj_reference(q, rows, parts, box, eps, sig, rcf):
         np.add.at(f[:, c], parts, -fr * d[:, c])
     np.add.at(f[:, 3], rows, 0.5 * pe)
     np.add.at(f[:, 3], parts, 0.5 * pe)
+    if with_bound:  # (S of check_lj, and the particles off the 64-ulp band of rc_force)
+        ok = inn | (r2 >= rcf * rcf)
+        S = lj_pair_magnitudes(len(q), rows[ok], parts[ok], d[ok], r2[ok], eps, sig, inn[ok])
+        return f, S, lj_rows_off_the_band(len(q), rows[ok], parts[ok], r2[ok], rcf, q.dtype)
     return f
 
 
@@ -549,16 +543,21 @@ def _lj_reference(q, rows, parts, box, eps, sig, rcf):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("full", [False, True])
 def test_lj_forces_triclinic(dtype, full):
+    """Forces in a box with large tilts against float64 numpy over the replayed list, scalar and typed.  The box is not
+    representable in float32 and the library works with the box in the position type (the binning, the list and the
+    consumer's fold alike), so the reference folds with the box rounded to dtype: L differs from (float)L by up to 16 u of
+    a separation near 1, which across a face is far beyond c u S for the unthinned close pairs of this input."""
     torch = _torch()
     box = (20.3, 18.1, 19.4, 9.1, -6.2, 8.3)  # large tilts: the single half-box test would miss images
     q = positions(6000, RC, box, 7, np.float64, seed=61).astype(dtype)
     nl = _handle(box, dtype, 7, len(q), full=full)
     qd = _build(nl, q)
     rows, parts, _ = replay_pairs(q, RC, box, 7, dtype)
-    ref = _lj_reference(q, rows, parts, box, 1.0, 1.0, 2.5)
+    ref, S, off_band = _lj_reference(q, rows, parts, tuple(float(dtype(v)) for v in box), 1.0, 1.0, 2.5, with_bound=True)
     f = nl.lj_forces(qd, epsilon=1.0, sigma=1.0, rc_force=2.5).cpu().numpy().astype(np.float64)
     tol = 2e-3 if dtype == np.float32 else 1e-9
     assert np.allclose(f, ref, rtol=tol, atol=tol * (1.0 + np.abs(ref).max()))
+    check_lj(f, ref, S, dtype, rows=off_band)  # per particle and component within c u S (tests/test_lj_consumer.py)
     types = np.zeros(len(q), dtype=np.int32)
     types[::3] = 1
     nl.set_type_cutoffs(torch.from_numpy(types).cuda(), np.full((2, 2), RC))
@@ -566,6 +565,7 @@ def test_lj_forces_triclinic(dtype, full):
     nl.set_lj_type_params(np.ones((2, 2)), np.ones((2, 2)), np.full((2, 2), 2.5))
     ft = nl.lj_forces_typed(qd).cpu().numpy().astype(np.float64)
     assert np.allclose(ft, ref, rtol=tol, atol=tol * (1.0 + np.abs(ref).max()))
+    check_lj(ft, ref, S, dtype, rows=off_band)
 
 
 @pytest.mark.gpu

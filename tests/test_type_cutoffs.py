@@ -16,7 +16,8 @@ import pytest
 from md_neighbor_list_amd import inputs
 from tests.test_exclusions import _checksum, full_from_half, mixed_pairs, ref_list, remove_pairs
 from tests.test_periodic_axes import positions
-from tests.util import ROOT, canonical_csr, golden_names, load_golden
+from tests.util import (ROOT, canonical_csr, check_lj, golden_names, lj_list_separations, lj_pair_magnitudes,
+                        lj_rows_off_the_band, load_golden)
 
 BOX = (27.0, 24.0, 40.0)
 RC = 3.3
@@ -600,15 +601,12 @@ def test_errors_keep_the_old_table():
         nl.types()
 
 
-def _lj_ref(q, kp, lst, types, eps, sig, rcf, box, mask):
+def _lj_ref(q, kp, lst, types, eps, sig, rcf, box, mask, with_bound=False):
     n = len(q)
     rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(kp))
     cols = np.asarray(lst, dtype=np.int64)
     ti, tj = types[rows], types[cols]
-    d = q[rows, :3].astype(np.float64) - q[cols, :3].astype(np.float64)
-    for a in range(3):
-        if mask >> a & 1:
-            d[:, a] -= box[a] * np.round(d[:, a] / box[a])
+    d = lj_list_separations(q, rows, cols, (*box, 0.0, 0.0, 0.0), mask)  # (folded before it is rounded to float64)
     r2 = (d * d).sum(axis=1)
     inr = r2 < rcf[ti, tj] ** 2
     s2 = sig[ti, tj] ** 2 / r2
@@ -621,6 +619,9 @@ def _lj_ref(q, kp, lst, types, eps, sig, rcf, box, mask):
         np.add.at(out[:, c], cols, -fr * d[:, c])
     np.add.at(out[:, 3], rows, 0.5 * pe)
     np.add.at(out[:, 3], cols, 0.5 * pe)
+    if with_bound:  # (S of check_lj, and the particles off the 64-ulp band of their pairs' rc_force)
+        S = lj_pair_magnitudes(n, rows, cols, d, r2, eps[ti, tj], sig[ti, tj], inr)
+        return out, S, lj_rows_off_the_band(n, rows, cols, r2, rcf[ti, tj], q.dtype)
     return out
 
 
@@ -661,10 +662,11 @@ def test_lj_forces_typed(dtype, full, mask):
     nl.set_lj_type_params(eps, sig, rcf)
     got = nl.lj_forces_typed(qd).cpu().numpy().astype(np.float64)
     _, kp_w, lst_w = _want(q, rc, box, mask, False, dtype, types, rcm)
-    want = _lj_ref(q, kp_w, lst_w, types, eps, sig, rcf, box, mask)
+    want, S, off_band = _lj_ref(q, kp_w, lst_w, types, eps, sig, rcf, box, mask, with_bound=True)
     scale = np.abs(want).max(axis=0)
     tol = 2e-4 if dtype == np.float32 else 1e-11
     assert np.all(np.abs(got - want) <= tol * scale), (np.abs(got - want) / scale).max(axis=0)
+    check_lj(got, want, S, dtype, rows=off_band)  # per particle and component within c u S (tests/test_lj_consumer.py)
     # the enqueue variant: rc_force within rc_ab - skin
     nl.set_skin(0.5)
     nl.update(qd, sync=True)
@@ -674,5 +676,6 @@ def test_lj_forces_typed(dtype, full, mask):
     nl.set_lj_type_params(eps, sig, np.minimum(rcf, rcm - 0.5))
     f = nl.lj_forces_typed(qd, wait=False)
     torch.cuda.synchronize()
-    want2 = _lj_ref(q, kp_w, lst_w, types, eps, sig, np.minimum(rcf, rcm - 0.5), box, mask)
+    want2, S2, off_band2 = _lj_ref(q, kp_w, lst_w, types, eps, sig, np.minimum(rcf, rcm - 0.5), box, mask, with_bound=True)
     assert np.all(np.abs(f.cpu().numpy().astype(np.float64) - want2) <= tol * np.abs(want2).max(axis=0))
+    check_lj(f.cpu().numpy(), want2, S2, dtype, rows=off_band2)
