@@ -126,7 +126,9 @@ int nl_set_periodic(nl_handle_t h, int minimum_image);
  * Any mask but 0 runs the minimum-image kernels (the cost of mask 7).  Every axis still needs 3 cells (NL_ERR_MESH).
  * Slab builds: the box-end ranks' ghost layers are z-images only with bit 2 set.  With z open they are taken as given
  * and hold partners only of particles whose z lies outside [0, L) (filed into the wrapped layer); where every z lies
- * in [0, L) the caller may send them empty.  Side effects as nl_set_periodic: a pending
+ * in [0, L) the caller may send them empty.  The layer that owns a particle is its z cell index by the rule above: with
+ * bit 2 set the floor, so a particle at z = -0.3 cells belongs to the top layer's rank, with z open the truncation, which
+ * files it into layer 0 (NL_ERR_DOMAIN tells a caller who filed it otherwise).  Side effects as nl_set_periodic: a pending
  * build is finished, the next nl_update_list builds, and a changed mask drops the list.  Takes effect at the next
  * build; nl_get_periodic_axes returns the mask that the next build will use. */
 int nl_set_periodic_axes(nl_handle_t h, int mask);
@@ -189,7 +191,12 @@ int nl_make_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, 
  * in the w component of each position, as the bit pattern of an int32 (F32) / int64 (F64), which halves the
  * number of halo messages).  Rows are built for the
  * owned particles only: row r holds the global ids j > gid[r] within the cut-off, so that the union over ranks
- * is exactly the global half list.  z_lo = 0, z_hi = mesh_z, n_rows = n is the single-GPU build. */
+ * is exactly the global half list.  z_lo = 0, z_hi = mesh_z, n_rows = n is the single-GPU build.
+ * After nl_set_list_kind(NL_LIST_FULL): row r holds every global id other than gid[r] within the cut-off, ghosts
+ * included, so that the rows over all ranks are exactly the global full list (with a periodic mask each row decides in
+ * its own frame, as in a whole build).  Read it with nl_get_full_csr(64), nl_list_checksum and nl_number_of_pairs
+ * (entries / 2); nl_get_full_transposed indexes its rows by id and refuses a slab build, half or full (NL_ERR_STATE).
+ * Tested row by row against the global list on every search path: tests/test_slab_paths.py. */
 #define NL_GID_IN_W ((const int32_t*)1)
 int nl_make_list_slab(nl_handle_t h, const void* q_dev, int32_t q_stride, const int32_t* gid_dev, int32_t n_rows,
                       int32_t n, int32_t z_lo, int32_t z_hi, void* stream, int sync);
@@ -427,7 +434,9 @@ int nl_list_checksum(nl_handle_t h, uint64_t* checksum, int64_t* nentries);
  * CSR of a NL_LIST_FULL build (one coalesced pass), or derived on the device from the half list of a NL_LIST_HALF
  * build (scattered writes: about ten times slower).  Entries k >= count[i] hold -1 when the buffer is first
  * allocated or grown and whatever an earlier build left there afterwards (the reference fills -1 once in
- * Initialize and never again, neighlist_gpu.hpp:271).  *max_partners receives max_i count[i].  Synchronises. */
+ * Initialize and never again, neighlist_gpu.hpp:271).  *max_partners receives max_i count[i].  Synchronises.
+ * Whole single-device builds only: after a slab or distributed build, whose ids are global and not row indices,
+ * NL_ERR_STATE. */
 int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, const int32_t** count_dev, int64_t* row_stride,
                            int32_t* max_partners);
 

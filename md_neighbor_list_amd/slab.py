@@ -41,11 +41,13 @@ def split_layers(mesh_z: int, world: int):
     return out
 
 
-def z_layer(q: torch.Tensor, box, rc) -> torch.Tensor:
+def z_layer(q: torch.Tensor, box, rc, periodic_z: bool = False) -> torch.Tensor:
     """The reference's z cell index of every particle: (int32)(z * ims_z), one periodic wrap
     (GenHash + ApplyPBC, neighlist_cpu.hpp:51-66), with ims_z rounded to the position type as the class stores it
     (neighlist_cpu.hpp:12,409-411).  The library re-derives this on the device and flags any disagreement
-    (NL_ERR_DOMAIN), so this copy of the rule cannot silently drift."""
+    (NL_ERR_DOMAIN), so this copy of the rule cannot silently drift.
+    periodic_z: the handle's periodic mask has z in it (nl_set_periodic_axes, bit 2): the index is then the FLOOR of
+    z * ims_z, so a particle at -0.3 cells lies in the top layer, not in layer 0 as the reference's truncation files it."""
     mz = int(box[2] / rc)
     if q.dtype == torch.float32:
         ims = np.float32(1.0 / np.float64(np.float32(box[2] / mz)))
@@ -54,6 +56,8 @@ def z_layer(q: torch.Tensor, box, rc) -> torch.Tensor:
         ims = 1.0 / (box[2] / mz)
         t = q[:, 2] * torch.tensor(ims, dtype=torch.float64, device=q.device)
     iz = t.to(torch.int32)  # truncation toward zero
+    if periodic_z:
+        iz = torch.where((t < 0) & (iz.to(t.dtype) != t), iz - 1, iz)
     iz = torch.where(iz < 0, iz + mz, iz)
     iz = torch.where(iz >= mz, iz - mz, iz)
     return iz
@@ -114,15 +118,17 @@ def _staging():
     return dist.get_backend() != "nccl"
 
 
-def setup(q_global: torch.Tensor, gid_global: torch.Tensor | None, box, rc, rank=None, world=None) -> SlabState:
+def setup(q_global: torch.Tensor, gid_global: torch.Tensor | None, box, rc, rank=None, world=None,
+          periodic_z: bool = False) -> SlabState:
     """Initial scatter, outside the timed build (the reference copies positions to the device once before its
     timing loop, make_list.cu:119,124): every rank looks at the whole (synthetic) box and keeps its slab.
-    Also exchanges the ghost counts once so that the per-build exchange needs no size negotiation."""
+    Also exchanges the ghost counts once so that the per-build exchange needs no size negotiation.
+    periodic_z: as in z_layer (the handle's periodic mask has z in it)."""
     rank = dist.get_rank() if rank is None else rank
     world = dist.get_world_size() if world is None else world
     mz = int(box[2] / rc)
     z_lo, z_hi = split_layers(mz, world)[rank]
-    iz = z_layer(q_global, box, rc)
+    iz = z_layer(q_global, box, rc, periodic_z)
     if gid_global is None:
         gid_global = torch.arange(q_global.shape[0], dtype=torch.int32, device=q_global.device)
     own = (iz >= z_lo) & (iz < z_hi)
