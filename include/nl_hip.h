@@ -323,8 +323,36 @@ int nl_get_update_stats(nl_handle_t h, int64_t stats[2]);
  *     The relabelled table stays in the same device buffers, so a graph the caller captured keeps reading it.  A
  *     caller who permutes its arrays with nl_get_cell_order itself must set the table again.
  *   Builds refuse with NL_ERR_NOMEM while the pre-exclusion buffers could not be (re)allocated.
- *   Graph replays (nl_set_graph, nl_update_list): setting, clearing or relabelling the table captures again. */
+ *   Graph replays (nl_set_graph, nl_update_list): setting, clearing or relabelling the table captures again.
+ *   nl_set_exclusions_global: the table over the ids the list STORES, [0, n_ids), for decomposed runs: the topology in
+ *     global tags, the same on every rank, valid while particles migrate (what LAMMPS special lists and HOOMD exclusions
+ *     carry).  pairs_dev = device int32 [n_pairs][2] of ids; copied, checked (0 <= a, b < n_ids, a != b, else NL_ERR_ARG
+ *     and the old table is kept; duplicates and both orders allowed) and built on the device exactly as above, and as
+ *     synchronous.  n_ids is independent of n_max (at most 2147483000): every rank holds the offsets of ALL global ids,
+ *     4 bytes per id, plus 4 bytes per table entry (8 per distinct pair); the set-up needs another 12 bytes per id and 8
+ *     per entry while it runs.  n_pairs == 0 or NULL clears the table; NL_ERR_NOMEM leaves none; NL_ERR_STATE before
+ *     nl_initialize.
+ *     One table per handle: nl_set_exclusions and nl_set_exclusions_global replace each other's table, and the handle
+ *     remembers which kind it holds.  nl_get_exclusions returns either, with *n = n_ids for a global one.
+ *     The rule, in ids: a build with a global table leaves out exactly the entries (row id a, partner id b) with {a, b}
+ *     in the table, and changes nothing else.  Half slab build: the row of the smaller id loses the partner, on the rank
+ *     that owns that row; full slab build: every owned row loses the partner, ghost partners included.  So the union over
+ *     the ranks is the global filtered list entry for entry, and the ranks' nl_list_checksum values sum to its checksum.
+ *     number_of_partners, key_pointer, npairs / nentries, nl_number_of_pairs and nl_list_checksum describe the filtered
+ *     list; F32 and F64, every periodic mask, both offset widths, every search path.
+ *     Builds it applies to: nl_make_list_slab with any id form (NULL = identity, a gid array, NL_GID_IN_W), the _begin /
+ *     _finish pair, nl_make_list_distributed (no host synchronisation added), and whole builds, whose ids are their rows.
+ *     Where the ids are the rows (gid_dev == NULL) a build needs n_rows <= n_ids, else NL_ERR_ARG at the call.  With
+ *     caller ids the stage checks them: a ROW whose id lies outside [0, n_ids) invalidates the build, NL_ERR_ARG reported
+ *     where NL_ERR_DOMAIN is (the synchronous return, or the next synchronising call of an asynchronous build).  A
+ *     PARTNER id outside the range matches nothing and is kept.  The stage reads the row's id from gid_dev or from the
+ *     positions' w: both must stay valid until the build has finished (as they must for nl_list_checksum).
+ *     Together with a type table (whole builds only) the pairs go through the typed stage as an input-row table does.
+ *     nl_resort NEVER relabels a global table: its ids are the caller's names, not rows.  Capacity is counted before
+ *     exclusion as above (NL_ERR_CAPACITY, growth, and the message capacities of a distributed build are untouched).
+ *     A table set by nl_set_exclusions (input rows) keeps refusing slab, id and distributed builds with NL_ERR_STATE. */
 int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n);
+int nl_set_exclusions_global(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n_ids);
 int nl_get_exclusions(nl_handle_t h, const int32_t** offsets_dev, const int32_t** ids_dev, int32_t* n, int64_t* n_unique);
 
 /* ---------------------------------------------------------------------------------------------- type cut-offs */

@@ -59,6 +59,7 @@ PROTOTYPES = {
     "nl_update_list": (C.c_int, [_P, _P, _I32, _I32, _P, C.c_int]),
     "nl_get_update_stats": (C.c_int, [_P, C.POINTER(_I64 * 2)]),
     "nl_set_exclusions": (C.c_int, [_P, _P, _I64, _I32]),
+    "nl_set_exclusions_global": (C.c_int, [_P, _P, _I64, _I32]),
     "nl_get_exclusions": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I32), C.POINTER(_I64)]),
     "nl_set_type_cutoffs": (C.c_int, [_P, _P, _I32, _I32, C.POINTER(_D)]),
     "nl_get_types": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I32), C.POINTER(_I32)]),

@@ -230,7 +230,8 @@ struct nl_handle_s {
   // nl_set_exclusions (nl_exclude.inc): pairs left out of the list by a stage behind the search
   int32_t* ex_off = nullptr;       // the table: [ex_n + 1] row offsets, symmetric, per-row ascending, no duplicates
   int32_t* ex_ids = nullptr;       // (nullptr: no table)
-  int32_t ex_n = 0;                // particle count of the builds it applies to
+  int32_t ex_n = 0;                // particle count of the builds it applies to; a global table: its ids, [0, ex_n)
+  bool ex_global = false;          // nl_set_exclusions_global: the rows of the table are ids of the list, not input rows
   int64_t ex_unique = 0;           // distinct unordered pairs
   uint64_t ex_gen = 0;             // bumped by a set, a clear or a relabel (part of the graph key)
   int64_t ex_off_cap = 0, ex_ids_cap = 0;  // entries the table's two buffers hold (a table that fits is written in place)
@@ -308,6 +309,15 @@ int consumer_ready(nl_handle_t h, hipStream_t s, bool enqueue) {
 
 // A table that filters builds is set (exclusions, types or both): builds run the filter stage.
 bool filter_tables(nl_handle_t h) { return h->ex_ids || h->ty_types; }
+// ... and it is one over input rows: whole single-device builds only.  (A global exclusion table alone speaks in the ids
+// of the list, and filters slab, id and distributed builds too.)
+bool filter_rows_only(nl_handle_t h) { return h->ty_types || (h->ex_ids && !h->ex_global); }
+// The exclusion table does not cover a build of n_rows rows: an input-row table is for builds of its own n; a global one
+// must hold every row's id, which the host knows where the ids are the rows (caller ids are checked by the stage).
+bool excl_refuses(nl_handle_t h, const int32_t* gid, int32_t n_rows) {
+  if (!h->ex_ids) return false;
+  return h->ex_global ? !gid && n_rows > h->ex_n : n_rows != h->ex_n;
+}
 // Where the search kernels write the offsets and the list: the getters' buffers, or with a filter table the unfiltered
 // ones that the stage compacts from.
 void* search_kp(nl_handle_t h) { return h->plan.filter ? h->kp_pre : h->key_pointer; }
@@ -444,6 +454,7 @@ float floor_to_float(double v) {  // largest float <= v
 int status_to_error(uint32_t st) {
   if (st & ST_OUT_OF_BOX) return NL_ERR_OUT_OF_BOX;
   if (st & ST_DOMAIN) return NL_ERR_DOMAIN;
+  if (st & ST_ID_RANGE) return NL_ERR_ARG;  // (a row's id outside the global exclusion table)
   if (st & ST_INDEX_OVERFLOW) return NL_ERR_INDEX_OVERFLOW;
   if (st & ST_CAPACITY) return NL_ERR_CAPACITY;
   return NL_OK;
@@ -911,7 +922,7 @@ void launch_bin_cells(nl_handle_t h, const Grid<T>& g, int32_t grid, int32_t nro
 template <typename T>
 int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStream_t s, hipEvent_t* ev, int part = PART_ALL) {
   adopt_build(h, a, p);
-  if (p.filter && ((h->ex_ids && a.n != h->ex_n) || (h->ty_types && a.n != h->ty_n) || a.slab || a.gid || a.dyn))
+  if (p.filter && (excl_refuses(h, a.gid, a.n_rows) || (h->ty_types && a.n != h->ty_n) || (filter_rows_only(h) && (a.slab || a.gid || a.dyn))))
     return fail(h, NL_ERR_STATE);  // (checked by the entry points)
   if (p.images && (a.slab || a.gid || a.dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
   if (!stage_ready(h, p)) return fail(h, NL_ERR_NOMEM);  // (the search or a stage would write through a missing buffer)
@@ -1598,14 +1609,14 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
   } else if (mz - owned < 2) {
     return fail(h, NL_ERR_ARG);  // the two ghost layers would be the same layer
   }
-  // an exclusion or type table applies to whole single-device builds of its own particle count
-  if (filter_tables(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  // an input-row exclusion table or a type table applies to whole single-device builds of its own particle count
+  if (filter_rows_only(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
   // nl_set_box: slab and distributed builds need the box of nl_create, and a tilt needs both of its axes periodic
   if (box_changed(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
   if (!tilt_mask_ok(h)) return fail(h, NL_ERR_STATE);
   // nl_set_pair_images: the images are those of whole single-device builds, whose ids index the positions
   if (h->pair_images && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
-  if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);
+  if (excl_refuses(h, a.gid, n_rows) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = stage_reserve(h)) return rc;  // (again, if an allocation failed since a table or the flag was set)
   if (h->pending) {
@@ -1747,7 +1758,7 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream) {
   const int32_t n = h->n;
   if (n == 0) return NL_OK;
   if (h->ex_relabel) {  // the first re-sort after a build: the tables follow the particles, once
-    if (h->ex_ids && h->ex_n == n)
+    if (h->ex_ids && !h->ex_global && h->ex_n == n)  // (a global table's ids are the caller's names, not rows)
       if ((rc = excl_relabel(h))) return rc;
     if (h->ty_types && h->ty_n == n)
       if ((rc = types_relabel(h))) return rc;

@@ -2,11 +2,16 @@
 // the non-bonded list when it is built, so that the list is filtered once per build and every consumer sees the same list.
 //   The table   a symmetric CSR over input-order particle ids, per-row ascending, without duplicates; built on the device
 //               from the caller's pairs (k_excl_degree .. k_excl_pack), relabelled by the first nl_resort after a build.
+//               Or (nl_set_exclusions_global) the same CSR over the ids the list stores, [0, n_ids): the caller's names,
+//               never relabelled, the same on every rank of a decomposed run; 4 bytes of offsets per global id.
 //   The stage   behind the search of a build, on its stream: the search writes the unfiltered offsets and list into
 //               kp_pre / list_pre (search_kp, search_list); k_excl_count counts what each row keeps into `count`, the
 //               row scan turns that into key_pointer (its total into the meta words, META_KEPT), k_excl_compact copies
 //               the kept entries into `list`.  A wave per row; the row's excluded ids are broadcast with readlane, or
 //               binary-searched where a row has more than EXCL_BCAST of them.  Every kernel takes the update's gate.
+//   The row's id  indexes the table: the row number (whole builds, slab builds without ids: the instances of the
+//               input-row table), or with a global table gid[row] or the w component of the caller's positions
+//               (ExclIds, EXCL_ID_*): one dependent load per row.  An id outside [0, n_ids) flags ST_ID_RANGE.
 // Builds without a table launch none of this and use the buffers they always used.
 // Included at the end of nl_api.hip; the pieces it shares with the other stages: nl_stage.hpp.
 
@@ -32,19 +37,45 @@ template <typename OFF> struct ExclArgs {
   const uint32_t* __restrict__ gate;
 };
 
+// Where a row's id comes from (compile-time): the row number, or for a global table the caller's id of the row.
+enum { EXCL_ID_ROW = 0, EXCL_ID_GID = 1, EXCL_ID_W32 = 2, EXCL_ID_W64 = 3 };
+struct ExclIds {
+  const void* __restrict__ src;  // EXCL_ID_GID: int32 gid[n_rows]; EXCL_ID_W32 / _W64: the positions, stride 4, id bits in w
+  int32_t n_ids;                 // ids of the table: a row id outside [0, n_ids) fails the build
+  uint32_t* __restrict__ status;
+};
+
+// The id of a row, wave-uniform (the row is).  -1: outside the table (flagged once per row, by the count pass).
+template <int IDS, bool FLAG> __device__ __forceinline__ int32_t excl_row_id(const ExclIds& x, int32_t row, int lane) {
+  int32_t id;
+  if constexpr (IDS == EXCL_ID_GID) id = static_cast<const int32_t*>(x.src)[row];
+  else if constexpr (IDS == EXCL_ID_W32) id = __float_as_int(static_cast<const float*>(x.src)[(size_t)row * 4 + 3]);
+  else id = (int32_t)__double_as_longlong(static_cast<const double*>(x.src)[(size_t)row * 4 + 3]);
+  id = __builtin_amdgcn_readfirstlane(id);
+  if ((uint32_t)id < (uint32_t)x.n_ids) return id;
+  if (FLAG && lane == 0) atomicOr(x.status, ST_ID_RANGE);
+  return -1;
+}
+
 // Both passes of the stage, a wave per row.  Count: count[row] = entries of the unfiltered row that the table keeps; rows
 // without exclusions do not read the list.  COMPACT: list[kp[row] ...] = the kept entries in their order (ballot + mbcnt).
 // (Entries at or past the list capacity were never written: an overflowed build fails, and they are only not read.)
-template <typename OFF, bool COMPACT>
+template <typename OFF, bool COMPACT, int IDS = EXCL_ID_ROW>
 __device__ __forceinline__ void excl_pass(const ExclArgs<OFF>& a, int32_t* __restrict__ count, const OFF* __restrict__ kp,
-                                          int32_t* __restrict__ list) {
+                                          int32_t* __restrict__ list, const ExclIds& x = ExclIds{}) {
   if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
   const int lane = threadIdx.x & 63;
   const int32_t waves = gridDim.x * (STAGE_THREADS / WAVE);
   for (int32_t row = blockIdx.x * (STAGE_THREADS / WAVE) + (threadIdx.x >> 6); row < a.n_rows; row += waves) {
     const int64_t b = (int64_t)a.kp_pre[row], e = (int64_t)a.kp_pre[row + 1];
     const int64_t end = e < a.capacity ? e : a.capacity;
-    const int32_t xb = a.ex_off[row], ne = a.ex_off[row + 1] - xb;
+    int32_t xb, ne;
+    if constexpr (IDS == EXCL_ID_ROW) {
+      xb = a.ex_off[row], ne = a.ex_off[row + 1] - xb;
+    } else {  // (a row outside the table keeps everything; its build fails)
+      const int32_t id = excl_row_id<IDS, !COMPACT>(x, row, lane);
+      xb = id < 0 ? 0 : a.ex_off[id], ne = id < 0 ? 0 : a.ex_off[id + 1] - xb;
+    }
     int64_t kept = e - b, dst = 0;
     if constexpr (COMPACT) dst = (int64_t)kp[row];
     if (ne == 0) {
@@ -81,12 +112,35 @@ __global__ void __launch_bounds__(STAGE_THREADS) k_excl_compact(ExclArgs<OFF> a,
   excl_pass<OFF, true>(a, nullptr, kp, list);
 }
 
-// (declared at the top of nl_api.hip)
+// The same two passes with the table indexed by the caller's id of the row (a global table on a build with ids).
+template <typename OFF> struct ExclIdArgs {
+  ExclArgs<OFF> a;
+  ExclIds x;
+};
+template <typename OFF, int IDS> __global__ void __launch_bounds__(STAGE_THREADS) k_excl_count_id(ExclIdArgs<OFF> a, int32_t* __restrict__ count) {
+  excl_pass<OFF, false, IDS>(a.a, count, nullptr, nullptr, a.x);
+}
+template <typename OFF, int IDS>
+__global__ void __launch_bounds__(STAGE_THREADS) k_excl_compact_id(ExclIdArgs<OFF> a, const OFF* __restrict__ kp, int32_t* __restrict__ list) {
+  excl_pass<OFF, true, IDS>(a.a, nullptr, kp, list, a.x);
+}
+
+// (declared at the top of nl_api.hip)  The build's ids are its rows (every build of an input-row table; a global table
+// on a build without caller ids, whose rows the entry point has checked against n_ids): the row-indexed instances.
 int launch_exclude(nl_handle_t h, int32_t n_rows, hipStream_t s) {
   return dispatch_t_off(h, [&](auto, auto off) -> int {
     using OFF = decltype(off);
     const ExclArgs<OFF> a = {static_cast<const OFF*>(h->kp_pre), h->list_pre, n_rows, h->capacity, h->ex_off, h->ex_ids, h->gate};
-    return launch_passes<OFF>(h, n_rows, n_rows, s, a, k_excl_count<OFF>, k_excl_compact<OFF>);
+    if (!h->args.gid) return launch_passes<OFF>(h, n_rows, n_rows, s, a, k_excl_count<OFF>, k_excl_compact<OFF>);
+    const bool in_w = h->args.gid == NL_GID_IN_W;
+    const ExclIdArgs<OFF> ax = {a, ExclIds{in_w ? h->args.q : static_cast<const void*>(h->args.gid), h->ex_n, h->status}};
+    auto launch = [&](auto ids) {
+      constexpr int IDS = decltype(ids)::value;
+      return launch_passes<OFF>(h, n_rows, n_rows, s, ax, k_excl_count_id<OFF, IDS>, k_excl_compact_id<OFF, IDS>);
+    };
+    if (!in_w) return launch(std::integral_constant<int, EXCL_ID_GID>());
+    if (h->dtype == NL_F32) return launch(std::integral_constant<int, EXCL_ID_W32>());
+    return launch(std::integral_constant<int, EXCL_ID_W64>());
   });
 }
 
@@ -191,22 +245,36 @@ uint32_t excl_grid(int64_t items, int32_t per_block, int32_t max_blocks) {
 }
 
 // Builds a table from np pairs on the handle's stream and makes it the handle's; validate: pairs out of range or with
-// i == j are NL_ERR_ARG and leave the old table in place.  Synchronous.
-int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool validate) {
+// i == j are NL_ERR_ARG and leave the old table in place.  global: the rows are ids of the list (nl_set_exclusions_global),
+// as many as the caller names -- more than the handle's scan holds blocks for take a look-back array of their own.
+// Synchronous.
+int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool validate, bool global) {
   if (2 * np > 2147483000LL) return fail(h, NL_ERR_ARG);
   hipStream_t s = h->own_stream;
   const size_t rows = (size_t)n + 32, ents = 2 * (size_t)np + 16;
   int32_t *deg = nullptr, *off_raw = nullptr, *raw = nullptr, *srt = nullptr, *off_new = nullptr;
   uint32_t* bad = nullptr;
+  uint64_t* look = nullptr;
+  const int32_t scan_nb = (int32_t)(((int64_t)n + SCAN_BLOCK - 1) / SCAN_BLOCK);
   auto release = [&]() {
-    for (void* p : {(void*)deg, (void*)off_raw, (void*)raw, (void*)srt, (void*)off_new, (void*)bad})
+    for (void* p : {(void*)deg, (void*)off_raw, (void*)raw, (void*)srt, (void*)off_new, (void*)bad, (void*)look})
       if (p) (void)hipFree(p);
+  };
+  auto scan = [&](const int32_t* in, int32_t* out) -> int {
+    if (!look) return launch_scan(h, in, n, out, h->totals + 2, s);
+    hipLaunchKernelGGL(k_scan_chained<int32_t>, dim3(scan_nb), dim3(SCAN_THREADS), 0, s, in, (int64_t)n, look, scan_nb, h->totals + 2, out, h->status,
+                       static_cast<uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr));
+    return NL_OK;
   };
   auto run = [&]() -> int {
     if (hipMalloc(reinterpret_cast<void**>(&deg), 4 * rows) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&off_raw), 4 * rows) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&raw), 4 * ents) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&srt), 4 * ents) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&off_new), 4 * rows) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&bad), 16) != hipSuccess)
       return fail(h, NL_ERR_NOMEM);
+    if (n > SCAN_SMALL_MAX && scan_nb > h->scan_blocks) {  // (k_scan_chained leaves its array zero again)
+      if (hipMalloc(reinterpret_cast<void**>(&look), 8 * ((size_t)scan_nb + 1)) != hipSuccess) return fail(h, NL_ERR_NOMEM);
+      HIPCHK(h, hipMemsetAsync(look, 0, 8 * ((size_t)scan_nb + 1), s));
+    }
     HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
     HIPCHK(h, hipMemsetAsync(bad, 0, 16, s));
     const uint32_t pgrid = excl_grid(np, 256, 8 * h->num_cus), rgrid = excl_grid(n, 4, 16 * h->num_cus);
@@ -218,14 +286,14 @@ int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool 
       HIPCHK(h, hipStreamSynchronize(s));
       if (b) return fail(h, NL_ERR_ARG);
     }
-    if (int rc = launch_scan(h, deg, n, off_raw, h->totals + 2, s)) return rc;
+    if (int rc = scan(deg, off_raw)) return rc;
     HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
     if (np > 0) hipLaunchKernelGGL(k_excl_scatter, dim3(pgrid), dim3(256), 0, s, pairs, np, off_raw, deg, raw);
     if (n > 0) {
       hipLaunchKernelGGL(k_excl_sort_rows, dim3(rgrid), dim3(256), 0, s, off_raw, raw, n, srt);
       hipLaunchKernelGGL(k_excl_distinct, dim3(rgrid), dim3(256), 0, s, off_raw, srt, n, deg);
     }
-    if (int rc = launch_scan(h, deg, n, off_new, h->totals + 2, s)) return rc;
+    if (int rc = scan(deg, off_new)) return rc;
     if (n > 0) hipLaunchKernelGGL(k_excl_pack, dim3(rgrid), dim3(256), 0, s, off_raw, srt, off_new, n, raw);
     HIPCHK(h, hipGetLastError());
     int32_t entries = 0;
@@ -246,6 +314,7 @@ int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool 
       off_new = raw = nullptr;
     }
     h->ex_n = n;
+    h->ex_global = global;
     h->ex_unique = entries / 2;
     h->ex_gen++;
     return NL_OK;
@@ -261,6 +330,7 @@ void excl_clear(nl_handle_t h) {
   h->ex_off = h->ex_ids = nullptr;
   if (!h->ty_types) filter_release(h);
   h->ex_n = 0, h->ex_unique = 0;
+  h->ex_global = false;
   h->ex_off_cap = h->ex_ids_cap = 0;
   h->ex_gen++;
   h->buffers_epoch++;
@@ -281,18 +351,16 @@ int excl_relabel(nl_handle_t h) {
     hipLaunchKernelGGL(k_excl_inverse, dim3((n + 255) / 256), dim3(256), 0, s, h->sorted_row, n, inv);
     hipLaunchKernelGGL(k_excl_relabel, dim3((n + 255) / 256), dim3(256), 0, s, h->ex_off, h->ex_ids, inv, n, pairs);
     if (hipGetLastError() != hipSuccess) rc = fail(h, NL_ERR_HIP);
-    if (!rc) rc = excl_build(h, pairs, entries, n, false);
+    if (!rc) rc = excl_build(h, pairs, entries, n, false, false);
   }
   if (inv) (void)hipFree(inv);
   if (pairs) (void)hipFree(pairs);
   return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n) {
+// nl_set_exclusions (rows: n <= n_max) and nl_set_exclusions_global (ids: as many as the caller names; the row loops
+// count in int32, so below 2^31 - 647): one table per handle, of the kind set last.
+int excl_set(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n, bool global) {
   if (!h || n_pairs < 0) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (h->pending) (void)finish(h, false);
@@ -301,15 +369,28 @@ int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, 
     h->upd_valid = false;
     return NL_OK;
   }
-  if (n < 0 || n > h->n_max) return fail(h, NL_ERR_ARG);
+  if (n < 0 || (global ? n > 2147483000 : n > h->n_max)) return fail(h, NL_ERR_ARG);
+  if (!h->totals) return fail(h, NL_ERR_STATE);  // (the set-up scans with the handle's buffers: nl_initialize first)
   HIPCHK(h, hipDeviceSynchronize());  // (the caller's pairs may come from any stream)
-  if (int rc = excl_build(h, pairs_dev, n_pairs, n, true)) return rc;
+  if (int rc = excl_build(h, pairs_dev, n_pairs, n, true, global)) return rc;
   h->upd_valid = false;
   if (int rc = filter_reserve(h)) {  // no room for the pre-exclusion buffers: no table
     excl_clear(h);
     return rc;
   }
   return NL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nl_set_exclusions(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n) {
+  return excl_set(h, pairs_dev, n_pairs, n, false);
+}
+
+int nl_set_exclusions_global(nl_handle_t h, const int32_t* pairs_dev, int64_t n_pairs, int32_t n_ids) {
+  return excl_set(h, pairs_dev, n_pairs, n_ids, true);
 }
 
 int nl_get_exclusions(nl_handle_t h, const int32_t** offsets_dev, const int32_t** ids_dev, int32_t* n, int64_t* n_unique) {

@@ -25,8 +25,8 @@ constexpr int WAVE = 64;
 
 // bits of the device status word
 // (ST_ROW_OVERFLOW: a row of x-cells held more particles than its bucket in k_bin_bucket; the host runs the build
-// again with the two-pass binning)
-enum : uint32_t { ST_OUT_OF_BOX = 1u, ST_CAPACITY = 2u, ST_DOMAIN = 4u, ST_INDEX_OVERFLOW = 8u, ST_ROW_OVERFLOW = 16u };
+// again with the two-pass binning; ST_ID_RANGE: a row's id lies outside the global exclusion table, nl_exclude.inc)
+enum : uint32_t { ST_OUT_OF_BOX = 1u, ST_CAPACITY = 2u, ST_DOMAIN = 4u, ST_INDEX_OVERFLOW = 8u, ST_ROW_OVERFLOW = 16u, ST_ID_RANGE = 32u };
 
 // One cell-sorted particle. gid = the id written into neighbour rows and used for the i<j half-list rule.
 template <typename T> struct Pos;

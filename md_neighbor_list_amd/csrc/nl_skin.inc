@@ -148,7 +148,7 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
   if (!h) return NL_ERR_ARG;
   if (h->n_max <= 0 && n > 0) return fail(h, NL_ERR_STATE);
   if (n < 0 || n > h->n_max || (q_stride != 3 && q_stride != 4) || (!q_dev && n > 0)) return fail(h, NL_ERR_ARG);
-  if ((h->ex_ids && n != h->ex_n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);  // (nl_set_exclusions, nl_set_type_cutoffs)
+  if (excl_refuses(h, nullptr, n) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);  // (nl_set_exclusions, nl_set_type_cutoffs)
   if (!tilt_mask_ok(h)) return fail(h, NL_ERR_STATE);  // (nl_set_box: a tilt needs both of its axes periodic)
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;

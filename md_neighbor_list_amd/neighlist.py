@@ -193,10 +193,7 @@ class NeighListGPU:
         return int(st[0]), int(st[1])
 
     # ------------------------------------------------------------------ excluded pairs
-    def set_exclusions(self, pairs, particle_number):
-        """Leaves the pairs of ``pairs`` out of every later build (nl_set_exclusions): an ``(E, 2)`` int32/int64 tensor or
-        array of input-order particle indices (duplicates and both orders allowed) for builds of ``particle_number``
-        particles.  Bonded partners of a molecular model; capacity is still counted before exclusion."""
+    def _exclusion_pairs(self, pairs):
         if isinstance(pairs, torch.Tensor):
             t = pairs
         else:
@@ -207,9 +204,25 @@ class NeighListGPU:
             raise TypeError("pairs must be an (E, 2) int32 or int64 tensor or array")
         if t.dtype == torch.int64 and t.numel() and (int(t.min()) < -2**31 or int(t.max()) >= 2**31):
             raise ValueError("pairs hold an index outside the int32 range")  # (a cast would wrap it onto a valid id)
-        t = t.to(device=self.device, dtype=torch.int32).contiguous()
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def set_exclusions(self, pairs, particle_number):
+        """Leaves the pairs of ``pairs`` out of every later build (nl_set_exclusions): an ``(E, 2)`` int32/int64 tensor or
+        array of input-order particle indices (duplicates and both orders allowed) for builds of ``particle_number``
+        particles.  Bonded partners of a molecular model; capacity is still counted before exclusion."""
+        t = self._exclusion_pairs(pairs)
         check(self._lib.nl_set_exclusions(self._h, t.data_ptr() if t.shape[0] else None, int(t.shape[0]), int(particle_number)),
               "nl_set_exclusions")
+
+    def set_exclusions_global(self, pairs, n_ids):
+        """Leaves the pairs of ``pairs`` out of every later build, keyed by the ids the list stores
+        (nl_set_exclusions_global): an ``(E, 2)`` int32/int64 tensor or array of ids in ``[0, n_ids)`` -- the global
+        tags of a decomposed run, the same table on every rank.  Applies to slab builds (any id form), the begin /
+        finish pair, distributed builds and whole builds; replaces a table set by ``set_exclusions`` and is never
+        relabelled by ``resort()``.  The handle holds 4 bytes per global id."""
+        t = self._exclusion_pairs(pairs)
+        check(self._lib.nl_set_exclusions_global(self._h, t.data_ptr() if t.shape[0] else None, int(t.shape[0]), int(n_ids)),
+              "nl_set_exclusions_global")
 
     def clear_exclusions(self):
         """Drops the exclusion table: later builds list every pair again."""
