@@ -33,14 +33,18 @@ tools/make_list: tools/make_list.cpp include/neighlist_gpu.hpp include/nl_hip.h 
 oracle:
 	$(MAKE) -C oracle
 
-# CPU sanitizer build: the host shims over a host-memory stand-in of the C ABI, the input generator
-# and the oracle's restatement under AddressSanitizer + UndefinedBehaviorSanitizer.  CPU only -- never run on the GPU box.
+# CPU sanitizer build: the host shims over a host-memory stand-in of the C ABI, the input generator,
+# the oracle's restatement and the device-memory owner (nl_devbuf.hpp over stand-ins of hipMalloc / hipFree: only the HIP
+# headers, no runtime) under AddressSanitizer + UndefinedBehaviorSanitizer.  CPU only -- never run on the GPU box.
+# The program is every source under tests/sanitize, so a tree with another set of checks there builds with this rule too.
+ROCM ?= /opt/rocm
+SANSRC := $(wildcard tests/sanitize/*.cpp)
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1
 asan: build/sanitize_test
-build/sanitize_test: tests/sanitize/main.cpp tests/sanitize/abi_stub.cpp oracle/nl_oracle.c oracle/nl_oracle_impl.h $(CSRC)/nl_inputs.cpp include/neighlist_cpu.hpp include/neighlist_gpu.hpp include/nl_hip.h
+build/sanitize_test: $(SANSRC) $(CSRC)/nl_devbuf.hpp oracle/nl_oracle.c oracle/nl_oracle_impl.h $(CSRC)/nl_inputs.cpp include/neighlist_cpu.hpp include/neighlist_gpu.hpp include/nl_hip.h
 	@mkdir -p build
 	gcc $(SANFLAGS) -std=c11 -ffp-contract=off -fopenmp -Wall -Wextra -c -o build/san_oracle.o oracle/nl_oracle.c
-	$(CXX) $(SANFLAGS) -std=c++17 -Wall -Iinclude -o $@ tests/sanitize/main.cpp tests/sanitize/abi_stub.cpp $(CSRC)/nl_inputs.cpp build/san_oracle.o -fopenmp
+	$(CXX) $(SANFLAGS) -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I$(CSRC) -isystem $(ROCM)/include -o $@ $(SANSRC) $(CSRC)/nl_inputs.cpp build/san_oracle.o -fopenmp
 
 # ISA + resource usage of the kernels, for DESIGN.md / tuning
 asm:

@@ -12,6 +12,7 @@
 #include <new>
 #include <tuple>
 
+#include "nl_devbuf.hpp"
 #include "nl_kernels.hpp"
 #include "nl_stage.hpp"
 
@@ -123,7 +124,7 @@ struct nl_handle_s {
   // the rounding to T); L0 = the box of nl_create (slab and distributed builds need it unchanged)
   double xy = 0, xz = 0, yz = 0, shear[3] = {0, 0, 0}, L0[3] = {0, 0, 0};
   int64_t mesh_cells_cap = 0, mesh_rows_cap = 0;  // cells and rows of x-cells the per-cell / per-row buffers hold
-  double* lat_dev = nullptr;  // [LATTICE_CODES][3] lattice vectors of the box of the next build (Grid::lat, SweepArgs::lat)
+  DevBuf<double> lat_dev;  // [LATTICE_CODES][3] lattice vectors of the box of the next build (Grid::lat, SweepArgs::lat)
   float ims_f[3];
   double ims_d[3];
   float rc2_f = 0;
@@ -135,36 +136,35 @@ struct nl_handle_s {
   int list_kind = NL_LIST_HALF;
   int pbc = 0;               // axes of the minimum image, bit d = axis d (nl_set_periodic_axes); 0 = the open box
 
-  // device buffers
-  int32_t* rank = nullptr;
-  void* sorted = nullptr;
-  int32_t* sorted_row = nullptr;
-  int32_t* sorted_gid = nullptr;   // ids in cell order, compact
-  int32_t* count = nullptr;
-  void* key_pointer = nullptr;     // [n_rows + 1] int32 (the reference's type, neighlist_cpu.hpp:29) or, in a wide build, int64
-  void* kp_alt = nullptr;          // key_pointer converted to the other width on demand (nl_get_*_csr / nl_get_*_csr64)
+  // device buffers (DevBuf: each owns its allocation and knows the bytes and items it holds; freed with the handle)
+  DevBuf<int32_t> rank;
+  DevBuf<void> sorted;
+  DevBuf<int32_t> sorted_row;
+  DevBuf<int32_t> sorted_gid;     // ids in cell order, compact
+  DevBuf<int32_t> count;
+  DevBuf<void> key_pointer;        // [n_rows + 1] int32 (the reference's type, neighlist_cpu.hpp:29) or, in a wide build, int64
+  DevBuf<void> kp_alt;             // key_pointer converted to the other width on demand (nl_get_*_csr / nl_get_*_csr64)
   bool kp_alt_valid = false;
   int offset_width = 0;            // nl_set_offset_width: 0 = by capacity (int64 as soon as the list may exceed INT32_MAX), 32, 64
-  int32_t* progress = nullptr;
+  DevBuf<int32_t> progress;
   // two-level binning (k_bin_*)
   int32_t* row_count = nullptr;   // [nrows] zeroed per build, then row totals
-  int32_t* row_start = nullptr;   // [nrows + 1]
-  int32_t* blk_base = nullptr;    // [bin_blocks][nrows]
-  void* tmp_pos = nullptr;        // particles grouped by row
-  int32_t* tmp_row = nullptr;
+  DevBuf<int32_t> row_start;      // [nrows + 1]
+  DevBuf<int32_t> blk_base;       // [bin_blocks][nrows]
+  DevBuf<void> tmp_pos;           // particles grouped by row
+  DevBuf<int32_t> tmp_row;
   size_t tmp_slots = 0;           // entries of tmp_pos / tmp_row
   // one-pass binning of a whole build (k_bin_bucket): a bucket of cap_row slots per row of x-cells
-  int32_t* row_cursor = nullptr;  // [my * mz] fill levels of the buckets; zero between builds (k_bin_bucket resets them)
+  DevBuf<int32_t> row_cursor;     // [my * mz] fill levels of the buckets; zero between builds (k_bin_bucket resets them)
   int bucket_env = 1;             // NL_BIN_BUCKETS=0: always the two-pass binning (same-box A/B)
   int32_t bucket_scale = 1;       // cap_row multiplier: doubled when a row has overflowed its bucket
   bool bucket_off = false;        // the buckets outgrew their memory: the two-pass binning from then on
   int32_t bin_blocks = 0, bin_chunk = 0;
   bool bin_two_level = true;      // NL_BINNING=1 selects the atomic-rank path (k_hash/k_reorder)
-  void* base_sorted = nullptr;     // key_pointer of every sorted slot (mask expansion), same width as key_pointer
-  uint32_t* masks = nullptr;       // [n][64] hit bits of every sorted slot, between COUNT_MASKS and k_fill_masks
-  int32_t* full27_list = nullptr;
-  void* resort_buf = nullptr;      // scratch of nl_resort (32 bytes per particle), allocated on first use
-  size_t masks_bytes = 0;          // size of the masks allocation
+  DevBuf<void> base_sorted;        // key_pointer of every sorted slot (mask expansion), same width as key_pointer
+  DevBuf<uint32_t> masks;          // [n][64] hit bits of every sorted slot, between COUNT_MASKS and k_fill_masks
+  DevBuf<int32_t> full27_list;
+  DevBuf<void> resort_buf;         // scratch of nl_resort (32 bytes per particle), allocated on first use
   int rows_env = -1;               // NL_ROWS: -1 (default) = the fine-row search where the 27-cell path would need several LDS batches
                                    // per cell (denser than 40.3 particles per cell), 0 = never, 1..3 = RowsCfg<V - 1> wherever a
                                    // build qualifies (tests), 4 = wherever a build qualifies, RowsCfg by density (sweeps)
@@ -174,21 +174,21 @@ struct nl_handle_s {
                                    // (2 = persistent LDS-DMA sweeps, 4 / 5 = matrix-core searches: measured slower or a draw
                                    // in round 1 and removed)
   int num_cus = 256;
-  unsigned long long* dbg_buf = nullptr;
+  DevBuf<unsigned long long> dbg_buf;
   int dbg_flags = 0;  // diagnostics (NL_DEBUG_FLAGS)
-  int32_t* cell_count = nullptr;  // [ncell] followed by the status word
-  int32_t* cell_start = nullptr;  // [ncell + 1]
-  int32_t* cls_start = nullptr;   // id-class builds: [C ncell + 1] first slot of every (cell, class) (k_bin_cells<IDC>)
+  DevBuf<int32_t> cell_count;     // [ncell] followed by the status word
+  DevBuf<int32_t> cell_start;     // [ncell + 1]
+  DevBuf<int32_t> cls_start;      // id-class builds: [C ncell + 1] first slot of every (cell, class) (k_bin_cells<IDC>)
   int idclass_env = 2;            // NL_IDCLASS: classes of the id-class search where a build qualifies (2 or 4), 0 = never
-  uint64_t* scan_look = nullptr;  // k_scan_chained: [scan_blocks] entries + the two counters; all zero between launches
+  DevBuf<uint64_t> scan_look;     // k_scan_chained: [scan_blocks] entries + the two counters; all zero between launches
   int32_t scan_blocks = 0;
-  int64_t* totals = nullptr;  // [0] = particles (cell scan), [1] = pairs (row scan)
+  DevBuf<int64_t> totals;     // [0] = particles (cell scan), [1] = pairs (row scan)
   uint32_t* status = nullptr;
-  int32_t* list = nullptr;
+  DevBuf<int32_t> list;
   // transposed full list (compat output)
-  int32_t* t_list = nullptr;
-  int32_t* t_count = nullptr;
-  int32_t* t_cursor = nullptr;
+  DevBuf<int32_t> t_list;
+  DevBuf<int32_t> t_count;
+  DevBuf<int32_t> t_cursor;
   int64_t t_rows_cap = 0;
   int32_t t_max = 0;
   bool t_valid = false;
@@ -201,7 +201,7 @@ struct nl_handle_s {
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   GraphKey graph_key;
-  uint64_t buffers_epoch = 1;  // bumped by every (re)allocation
+  uint64_t buffers_epoch = 1;  // bumped by every (re)allocation and release of a buffer that builds use
   bool begun = false;  // nl_make_list_slab_begin has run, nl_make_list_slab_finish has not
   hipStream_t last_stream = nullptr;
   hipEvent_t ev[NL_NUM_STAGES + 1] = {};
@@ -219,44 +219,39 @@ struct nl_handle_s {
   // nl_update_list (nl_skin.inc): the Verlet-skin rebuild decision on the device
   double skin = 0;                 // nl_set_skin
   const uint32_t* gate = nullptr;  // while an update's build is enqueued: k_skin_check's `go` word (every launch waits on it)
-  void* snap = nullptr;            // the caller's positions at the last build an update performed (input order, q's stride)
-  size_t snap_bytes = 0;
-  uint32_t* skin_words = nullptr;  // [go, over, ticket, pad, updates (u64), builds (u64)] (SKIN_* in nl_skin.inc)
+  DevBuf<void> snap;               // the caller's positions at the last build an update performed (input order, q's stride)
+  DevBuf<uint32_t> skin_words;     // [go, over, ticket, pad, updates (u64), builds (u64)] (SKIN_* in nl_skin.inc)
   bool upd_valid = false;          // the last build was an update's, and nothing that forces a build happened since
   bool last_update = false;        // the build enqueued last is an update's (complete without finish())
   const void* upd_q = nullptr;     // positions, stride and n of that build
   int32_t upd_stride = 0, upd_n = 0;
 
   // nl_set_exclusions (nl_exclude.inc): pairs left out of the list by a stage behind the search
-  int32_t* ex_off = nullptr;       // the table: [ex_n + 1] row offsets, symmetric, per-row ascending, no duplicates
-  int32_t* ex_ids = nullptr;       // (nullptr: no table)
+  DevBuf<int32_t> ex_off;          // the table: [ex_n + 1] row offsets, symmetric, per-row ascending, no duplicates
+  DevBuf<int32_t> ex_ids;          // (nullptr: no table)
   int32_t ex_n = 0;                // particle count of the builds it applies to; a global table: its ids, [0, ex_n)
   bool ex_global = false;          // nl_set_exclusions_global: the rows of the table are ids of the list, not input rows
   int64_t ex_unique = 0;           // distinct unordered pairs
   uint64_t ex_gen = 0;             // bumped by a set, a clear or a relabel (part of the graph key)
-  int64_t ex_off_cap = 0, ex_ids_cap = 0;  // entries the table's two buffers hold (a table that fits is written in place)
   bool ex_relabel = false;         // a build ran since the last nl_resort: the next one relabels the tables, if any
-  void* kp_pre = nullptr;          // with a table (either): the offsets and the list the search writes, before the stage
-  int32_t* list_pre = nullptr;     // (one offset array and one list capacity, allocated only while a table is set)
-  int64_t pre_capacity = -1, pre_rows = -1;
+  DevBuf<void> kp_pre;             // with a table (either): the offsets and the list the search writes, before the stage
+  DevBuf<int32_t> list_pre;        // (one offset array and one list capacity, allocated only while a table is set)
 
   // nl_set_type_cutoffs (nl_types.inc): the cut-off of a pair from the types of its particles, in the same stage
-  int32_t* ty_types = nullptr;     // [ty_n] types in input order (nullptr: no table)
-  void* ty_rc2 = nullptr;          // [NL_MAX_TYPES][NL_MAX_TYPES] thresholds in the position type
+  DevBuf<int32_t> ty_types;        // [ty_n] types in input order (nullptr: no table)
+  DevBuf<void> ty_rc2;             // [NL_MAX_TYPES][NL_MAX_TYPES] thresholds in the position type
   int32_t ty_n = 0, ty_ntypes = 0;
-  int64_t ty_cap = 0;              // entries ty_types holds (a table that fits is written in place)
   double ty_rc[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // the caller's rc_ab, [ty_ntypes][ty_ntypes]
   uint64_t ty_gen = 0;             // bumped by a set, a clear or a relabel (part of the graph key)
-  void* lj_par = nullptr;          // nl_set_lj_type_params: [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2 in T
+  DevBuf<void> lj_par;             // nl_set_lj_type_params: [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2 in T
   int32_t lj_ntypes = 0;
   double lj_rcf[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // rc_force_ab, [lj_ntypes][lj_ntypes]
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
-  uint32_t* images = nullptr;      // [capacity] int8 {s_a, s_b, s_c, 0} per entry, at the entry's index in `list`
-  uint16_t* img_code = nullptr;    // [n_max] faces and wraps of every particle (k_image_codes)
-  uint32_t* img_words = nullptr;   // [wrapped, ticket, pad, pad] of the stage (IMG_* in nl_images.inc); zero between builds
-  int64_t img_capacity = -1, img_rows = -1;  // entries / particles the two buffers hold
+  DevBuf<uint32_t> images;         // [capacity] int8 {s_a, s_b, s_c, 0} per entry, at the entry's index in `list`
+  DevBuf<uint16_t> img_code;       // [n_max] faces and wraps of every particle (k_image_codes)
+  DevBuf<uint32_t> img_words;      // [wrapped, ticket, pad, pad] of the stage (IMG_* in nl_images.inc); zero between builds
 };
 
 namespace {
@@ -312,6 +307,13 @@ bool filter_tables(nl_handle_t h) { return h->ex_ids || h->ty_types; }
 // ... and it is one over input rows: whole single-device builds only.  (A global exclusion table alone speaks in the ids
 // of the list, and filters slab, id and distributed builds too.)
 bool filter_rows_only(nl_handle_t h) { return h->ty_types || (h->ex_ids && !h->ex_global); }
+// part: PART_ALL = the whole build; PART_BEGIN = everything that needs the OWNED particles only (slab builds: memset +
+// the binning pass over [0, n_rows)); PART_FINISH = the rest (the binning pass over the ghosts, search, scan,
+// expansion).  BEGIN + FINISH = ALL for the caller; between the two the halo exchange may still be writing the ghosts.
+enum { PART_ALL = 0, PART_BEGIN = 1, PART_FINISH = 2 };
+
+// Not a whole single-device build: a slab, caller ids, a distributed build, or one half of a build in two parts.
+bool partial_build(const BuildArgs& a, int part) { return a.slab || a.gid || a.dyn || part != PART_ALL; }
 // The exclusion table does not cover a build of n_rows rows: an input-row table is for builds of its own n; a global one
 // must hold every row's id, which the host knows where the ids are the rows (caller ids are checked by the stage).
 bool excl_refuses(nl_handle_t h, const int32_t* gid, int32_t n_rows) {
@@ -325,48 +327,56 @@ int32_t* search_list(nl_handle_t h) { return h->plan.filter ? h->list_pre : h->l
 // Entries of the last build's list (after the stage, if it ran); growth keeps using the unfiltered total.
 int64_t list_total(nl_handle_t h) { return h->plan.filter ? h->host->kept() : h->host->total(); }
 
-template <typename P> int dev_alloc(nl_handle_t h, P** p, size_t bytes) {
-  h->buffers_epoch++;  // a captured graph holds the old pointers
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    h->last_hip = (int)e;
-    return fail(h, e == hipErrorOutOfMemory ? NL_ERR_NOMEM : NL_ERR_HIP);
-  }
-  return NL_OK;
+// The handle's side of a DevBuf operation: the wrappers below (and follow) are the only places that bump buffers_epoch
+// for an allocation, and hip_status the only one that turns its result into last_hip and an nl_status.
+int hip_status(nl_handle_t h, hipError_t e) {
+  if (e == hipSuccess) return NL_OK;
+  (void)hipGetLastError();  // (taken here: the runtime keeps it, and the launch check of the next build would report it)
+  h->last_hip = (int)e;
+  return fail(h, e == hipErrorOutOfMemory ? NL_ERR_NOMEM : NL_ERR_HIP);
 }
+// Free, then allocate: the buffer is empty after a failure, and the epoch moves either way.
+template <typename T> int dev_alloc(nl_handle_t h, DevBuf<T>& b, size_t bytes, int64_t items = 0) {
+  h->buffers_epoch++;  // a captured graph holds the old pointers
+  return hip_status(h, b.replace(bytes, items));
+}
+// Allocate, then free: keeps the old buffer (and the epoch) where the new one cannot be had (nl_set_box: an error
+// leaves the handle as it was).
+template <typename T> int swap_alloc(nl_handle_t h, DevBuf<T>& b, size_t bytes, int64_t items = 0) {
+  const hipError_t e = b.replace_keeping(bytes, items);
+  if (e == hipSuccess) h->buffers_epoch++;  // a captured graph holds the old pointers
+  return hip_status(h, e);
+}
+// A buffer that no build touches (scratch of one call, kp_alt, resort_buf, lj_par): no graph of the handle holds it.
+template <typename T> int side_alloc(nl_handle_t h, DevBuf<T>& b, size_t bytes) { return hip_status(h, b.replace(bytes)); }
 
 // ---- the stages' buffers, which follow n_max and the list's capacity
 constexpr int IMG_WORDS = 4;  // words of h->img_words (IMG_* in nl_images.inc)
 
-// A buffer of `bytes` for `want` items, where it holds fewer; *held is -1 while the allocation is in flight (an error
-// leaves it there: the buffer is not ready).
-template <typename P> int follow(nl_handle_t h, P** p, int64_t* held, int64_t want, size_t bytes) {
-  if (*held >= want) return NL_OK;
-  *held = -1;
-  if (int rc = dev_alloc(h, p, bytes)) return rc;
-  *held = want;
-  return NL_OK;
+// A buffer of `bytes` for `want` items, where it holds fewer (an error leaves it empty: the buffer is not ready).
+template <typename T> int follow(nl_handle_t h, DevBuf<T>& b, int64_t want, size_t bytes) {
+  if (b.holds(want)) return NL_OK;
+  h->buffers_epoch++;  // (as dev_alloc)
+  return hip_status(h, b.ensure(want, bytes));
 }
 
 // The unfiltered offsets and list while a table filters builds (exclusions, types or both: one offset array, one list
 // capacity); nothing without one.
 int filter_reserve(nl_handle_t h) {
   if (!filter_tables(h)) return NL_OK;
-  if (int rc = follow(h, &h->kp_pre, &h->pre_rows, h->n_max, 8 * ((size_t)h->n_max + 32))) return rc;
-  return follow(h, &h->list_pre, &h->pre_capacity, h->capacity, 4 * ((size_t)h->capacity + 16));
+  if (int rc = follow(h, h->kp_pre, h->n_max, 8 * ((size_t)h->n_max + 32))) return rc;
+  return follow(h, h->list_pre, h->capacity, 4 * ((size_t)h->capacity + 16));
 }
 
 // The image stage's buffers while the flag is on: one word per entry of the list's capacity, one code per particle of n_max.
 int images_reserve(nl_handle_t h) {
   if (!h->pair_images) return NL_OK;
   if (!h->img_words) {
-    if (int rc = dev_alloc(h, &h->img_words, sizeof(uint32_t) * IMG_WORDS)) return rc;
+    if (int rc = dev_alloc(h, h->img_words, sizeof(uint32_t) * IMG_WORDS)) return rc;
     HIPCHK(h, hipMemset(h->img_words, 0, sizeof(uint32_t) * IMG_WORDS));
   }
-  if (int rc = follow(h, &h->img_code, &h->img_rows, h->n_max, 2 * ((size_t)h->n_max + 64))) return rc;
-  return follow(h, &h->images, &h->img_capacity, h->capacity, 4 * ((size_t)h->capacity + 16));
+  if (int rc = follow(h, h->img_code, h->n_max, 2 * ((size_t)h->n_max + 64))) return rc;
+  return follow(h, h->images, h->capacity, 4 * ((size_t)h->capacity + 16));
 }
 
 // Both: wherever n_max or the capacity changes, and again in front of a build (if an allocation failed since).
@@ -377,25 +387,18 @@ int stage_reserve(nl_handle_t h) {
 
 // The buffers that plan p's stages write through are there.
 bool stage_ready(nl_handle_t h, const BuildPlan& p) {
-  if (p.filter && !(h->kp_pre && h->list_pre && h->pre_rows >= (int64_t)h->n_max && h->pre_capacity >= h->capacity)) return false;
-  if (p.images && !(h->images && h->img_code && h->img_words && h->img_rows >= (int64_t)h->n_max && h->img_capacity >= h->capacity))
-    return false;
+  if (p.filter && !(h->kp_pre.holds(h->n_max) && h->list_pre.holds(h->capacity))) return false;
+  if (p.images && !(h->images.holds(h->capacity) && h->img_code.holds(h->n_max) && h->img_words)) return false;
   return true;
 }
 
 // The unfiltered buffers, once no table needs them.
 void filter_release(nl_handle_t h) {
-  for (void* b : {h->kp_pre, (void*)h->list_pre})
-    if (b) (void)hipFree(b);
-  h->kp_pre = nullptr, h->list_pre = nullptr;
-  h->pre_capacity = h->pre_rows = -1;
+  h->kp_pre.release(), h->list_pre.release();  // (no epoch here: the callers bump it)
 }
 
 void images_release(nl_handle_t h) {
-  for (void* b : {(void*)h->images, (void*)h->img_code, (void*)h->img_words})
-    if (b) (void)hipFree(b);
-  h->images = nullptr, h->img_code = nullptr, h->img_words = nullptr;
-  h->img_capacity = h->img_rows = -1;
+  h->images.release(), h->img_code.release(), h->img_words.release();
   h->buffers_epoch++;
 }
 
@@ -403,36 +406,23 @@ void images_release(nl_handle_t h) {
 // more cells or rows than they hold (nl_initialize allocates them all, nl_set_box only what a larger mesh needs), and cleared:
 // the status and meta words sit behind the histogram, at a place that moves with the number of cells, and every word of
 // them, of the row cursors and of the scan's look-back array must be zero before a build.
-// dev_alloc that keeps the old buffer where the new one cannot be had (nl_set_box: an error leaves the handle as it was)
-template <typename P> int swap_alloc(nl_handle_t h, P** p, size_t bytes) {
-  void* fresh = nullptr;
-  const hipError_t e = hipMalloc(&fresh, bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    h->last_hip = (int)e;
-    return fail(h, e == hipErrorOutOfMemory ? NL_ERR_NOMEM : NL_ERR_HIP);
-  }
-  h->buffers_epoch++;  // a captured graph holds the old pointers
-  if (*p) (void)hipFree(*p);
-  *p = static_cast<P*>(fresh);
-  return NL_OK;
-}
 int reserve_mesh(nl_handle_t h, size_t n) {
   int rc;
   const size_t rows_cap = std::max<size_t>((size_t)h->m[1] * h->m[2], (size_t)h->mesh_rows_cap);
   const size_t cells_cap = std::max<size_t>((size_t)h->ncell, (size_t)h->mesh_cells_cap);
   if (rows_cap > (size_t)h->mesh_rows_cap) {
-    if ((rc = swap_alloc(h, &h->row_start, 4 * (2 * rows_cap + 64)))) return rc;  // (two arrays: a split slab build has two passes)
-    if ((rc = swap_alloc(h, &h->blk_base, 4 * (rows_cap * (size_t)h->bin_blocks + 16)))) return rc;
-    if ((rc = swap_alloc(h, &h->row_cursor, 4 * (rows_cap + 16)))) return rc;
+    if ((rc = swap_alloc(h, h->row_start, 4 * (2 * rows_cap + 64)))) return rc;  // (two arrays: a split slab build has two passes)
+    if ((rc = swap_alloc(h, h->blk_base, 4 * (rows_cap * (size_t)h->bin_blocks + 16)))) return rc;
+    if ((rc = swap_alloc(h, h->row_cursor, 4 * (rows_cap + 16)))) return rc;
   }
   if (cells_cap > (size_t)h->mesh_cells_cap || rows_cap > (size_t)h->mesh_rows_cap) {
     // cells handed from one search kernel to another: half-shell -> 27-cell search, pipelined COUNT -> batched search
-    if ((rc = swap_alloc(h, &h->full27_list, 4 * (cells_cap + 16)))) return rc;
-    if ((rc = swap_alloc(h, &h->cell_count, 4 * (cells_cap + 64 + 2 * rows_cap)))) return rc;
-    if ((rc = swap_alloc(h, &h->cell_start, 4 * (4 * cells_cap + 32)))) return rc;  // (cell_start, or the fine-row table: 4 M + 1)
-    if ((rc = swap_alloc(h, &h->cls_start, 4 * (4 * cells_cap + 32)))) return rc;   // (the class table: up to 4 M + 1)
+    if ((rc = swap_alloc(h, h->full27_list, 4 * (cells_cap + 16)))) return rc;
+    if ((rc = swap_alloc(h, h->cell_count, 4 * (cells_cap + 64 + 2 * rows_cap)))) return rc;
+    if ((rc = swap_alloc(h, h->cell_start, 4 * (4 * cells_cap + 32)))) return rc;  // (cell_start, or the fine-row table: 4 M + 1)
+    if ((rc = swap_alloc(h, h->cls_start, 4 * (4 * cells_cap + 32)))) return rc;   // (the class table: up to 4 M + 1)
     const size_t nblk = std::max<size_t>(n, cells_cap) / SCAN_BLOCK + 2;
-    if ((rc = swap_alloc(h, &h->scan_look, 8 * (nblk + 1)))) return rc;
+    if ((rc = swap_alloc(h, h->scan_look, 8 * (nblk + 1)))) return rc;
     h->scan_blocks = (int32_t)nblk;
   }
   h->mesh_rows_cap = (int64_t)rows_cap, h->mesh_cells_cap = (int64_t)cells_cap;
@@ -571,7 +561,7 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.status = h->status;
   a.masks = h->masks;
   // (the two planes of the hit words, one array each inside the same allocation: 128 + 64 bytes per row)
-  a.masks_hi = reinterpret_cast<uint8_t*>(h->masks) + h->masks_bytes / MASK_ROW_BYTES * MASK_LO_BYTES;
+  a.masks_hi = reinterpret_cast<uint8_t*>(h->masks.get()) + h->masks.bytes() / MASK_ROW_BYTES * MASK_LO_BYTES;
   a.isplit = 1;
   a.mask_nb = h->plan.mask_nb;
   a.full27_list = h->full27_list;
@@ -711,23 +701,12 @@ template <typename T> void launch_sweep(nl_handle_t h, int mode, hipStream_t s) 
   else launch_sweep_kind<T, int32_t>(h, mode, s);
 }
 
-// part: PART_ALL = the whole build; PART_BEGIN = everything that needs the OWNED particles only (slab builds: memset +
-// the binning pass over [0, n_rows)); PART_FINISH = the rest (the binning pass over the ghosts, search, scan,
-// expansion).  BEGIN + FINISH = ALL for the caller; between the two the halo exchange may still be writing the ghosts.
-enum { PART_ALL = 0, PART_BEGIN = 1, PART_FINISH = 2 };
-
 // Mask rows for `nb` LDS batches per particle: allocated on first need (a half-shell handle that meets a minimum-image
 // or dense build; a first dense build).
 bool mask_rows_ready(nl_handle_t h, int64_t nb, size_t row_bytes = MASK_ROW_BYTES) {
   const size_t need = row_bytes * (size_t)nb * ((size_t)h->n_max + 64);  // (+64: the expansion kernels read whole row batches)
   if (need > h->dense_masks_limit) return false;
-  if (need > h->masks_bytes || !h->masks) {
-    if (dev_alloc(h, &h->masks, need) != NL_OK) {
-      h->masks_bytes = 0;
-      return false;
-    }
-    h->masks_bytes = need;
-  }
+  if (need > h->masks.bytes() || !h->masks) return dev_alloc(h, h->masks, need) == NL_OK;
   return true;
 }
 
@@ -763,12 +742,12 @@ template <typename T> int32_t bucket_cap(nl_handle_t h, int32_t n, int32_t mzl) 
     return 0;
   }
   if (slots > h->tmp_slots) {
-    if (dev_alloc(h, &h->tmp_pos, sizeof(Pos<T>) * slots) || dev_alloc(h, &h->tmp_row, sizeof(int32_t) * slots)) {
+    if (dev_alloc(h, h->tmp_pos, sizeof(Pos<T>) * slots) || dev_alloc(h, h->tmp_row, sizeof(int32_t) * slots)) {
       // no room: the two-pass binning, with the buffers it needs
       h->bucket_off = true;
       h->tmp_slots = 0;
       const size_t n_slots = (size_t)h->n_max + 16;
-      if (dev_alloc(h, &h->tmp_pos, sizeof(Pos<T>) * n_slots) == NL_OK && dev_alloc(h, &h->tmp_row, sizeof(int32_t) * n_slots) == NL_OK)
+      if (dev_alloc(h, h->tmp_pos, sizeof(Pos<T>) * n_slots) == NL_OK && dev_alloc(h, h->tmp_row, sizeof(int32_t) * n_slots) == NL_OK)
         h->tmp_slots = n_slots, h->last_error = NL_OK;
       return 0;
     }
@@ -922,9 +901,9 @@ void launch_bin_cells(nl_handle_t h, const Grid<T>& g, int32_t grid, int32_t nro
 template <typename T>
 int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStream_t s, hipEvent_t* ev, int part = PART_ALL) {
   adopt_build(h, a, p);
-  if (p.filter && (excl_refuses(h, a.gid, a.n_rows) || (h->ty_types && a.n != h->ty_n) || (filter_rows_only(h) && (a.slab || a.gid || a.dyn))))
+  if (p.filter && (excl_refuses(h, a.gid, a.n_rows) || (h->ty_types && a.n != h->ty_n) || (filter_rows_only(h) && partial_build(a, part))))
     return fail(h, NL_ERR_STATE);  // (checked by the entry points)
-  if (p.images && (a.slab || a.gid || a.dyn)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
+  if (p.images && partial_build(a, part)) return fail(h, NL_ERR_STATE);  // (checked by the entry points)
   if (!stage_ready(h, p)) return fail(h, NL_ERR_NOMEM);  // (the search or a stage would write through a missing buffer)
   if (part != PART_ALL && !p.split) {  // nothing to overlap on this path: BEGIN does nothing, FINISH is the whole build
     if (part == PART_BEGIN) return NL_OK;
@@ -998,7 +977,7 @@ int enqueue_build(nl_handle_t h, const BuildArgs& a, const BuildPlan& p, hipStre
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_HASH], s));
       if (n > 0) hipLaunchKernelGGL((k_hash<T>), dim3(nbp), dim3(256), 0, s, q, a.stride, n, g, h->cell_count, h->rank, h->status);
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_CELL_SCAN], s));
-      if (int rc = launch_scan(h, h->cell_count, (int64_t)h->m[0] * h->m[1] * a.mzl, h->cell_start, h->totals, s)) return rc;
+      if (int rc = launch_scan(h, h->cell_count, (int64_t)h->m[0] * h->m[1] * a.mzl, h->cell_start.get(), h->totals, s)) return rc;
       if (ev) HIPCHK(h, hipEventRecord(ev[NL_STAGE_REORDER], s));
       if (n > 0)
         hipLaunchKernelGGL((k_reorder<T>), dim3(nbp), dim3(256), 0, s, q, a.stride, a.gid, n, g, h->cell_start, h->rank,
@@ -1051,7 +1030,7 @@ int estimate_capacity(nl_handle_t h) {
   if (h->capacity_user) return NL_OK;
   const int64_t want = estimate_want(h);
   if (want > h->capacity) {
-    if (int rc = dev_alloc(h, &h->list, 4 * (size_t)want)) return rc;
+    if (int rc = dev_alloc(h, h->list, 4 * (size_t)want)) return rc;
     h->capacity = want;
   }
   return stage_reserve(h);
@@ -1061,7 +1040,7 @@ int grow_list(nl_handle_t h, int64_t need) {
   int64_t cap = std::max<int64_t>(need + need / 8 + 1024, h->capacity);
   // a list that an int32 key_pointer can still address stays below the switch to 64-bit offsets
   if (need <= 2147483647LL && cap > 2147483647LL && h->capacity <= 2147483647LL) cap = 2147483647LL;
-  int rc = dev_alloc(h, &h->list, sizeof(int32_t) * (size_t)cap);
+  int rc = dev_alloc(h, h->list, sizeof(int32_t) * (size_t)cap);
   if (rc) {
     h->capacity = 0;
     return rc;
@@ -1179,9 +1158,7 @@ int key_pointer_as(nl_handle_t h, int width, const void** out) {
   const int64_t cnt = (int64_t)h->n_rows + 1;
   if (!h->kp_alt) {
     HIPCHK(h, hipSetDevice(h->device));
-    void* p = nullptr;
-    if (hipMalloc(&p, 8 * ((size_t)h->n_max + 32)) != hipSuccess) return fail(h, NL_ERR_NOMEM);
-    h->kp_alt = p;
+    if (int rc = side_alloc(h, h->kp_alt, 8 * ((size_t)h->n_max + 32))) return rc;
     h->kp_alt_valid = false;
   }
   if (!h->kp_alt_valid) {
@@ -1335,7 +1312,7 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
   h->ncell = (int64_t)m[0] * m[1] * m[2];
   double lat0[LATTICE_CODES * 3];
   lattice_table(box_of(h), lat0);
-  if (hipMalloc(reinterpret_cast<void**>(&h->lat_dev), sizeof(lat0)) != hipSuccess ||
+  if (h->lat_dev.replace(sizeof(lat0)) != hipSuccess ||
       hipMemcpy(h->lat_dev, lat0, sizeof(lat0), hipMemcpyHostToDevice) != hipSuccess ||
       hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void**>(&h->host), sizeof(HostResult), hipHostMallocDefault) != hipSuccess) {
@@ -1368,18 +1345,13 @@ int nl_destroy(nl_handle_t h) {
   if (!h) return NL_ERR_ARG;
   (void)hipSetDevice(h->device);
   if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);
-  void* bufs[] = {h->snap, h->skin_words, h->rank, h->sorted, h->sorted_row, h->sorted_gid, h->count, h->key_pointer, h->kp_alt, h->progress, h->base_sorted, h->row_start, h->blk_base, h->tmp_pos, h->tmp_row, h->row_cursor, h->masks, h->full27_list, h->resort_buf, h->dbg_buf, h->cell_count,
-                  h->cell_start, h->cls_start, h->scan_look, h->totals, h->list, h->t_list, h->t_count, h->t_cursor,
-                  h->ex_off, h->ex_ids, h->kp_pre, h->list_pre, h->ty_types, h->ty_rc2, h->lj_par, h->lat_dev, h->images, h->img_code, h->img_words};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
   if (h->host) (void)hipHostFree(h->host);
   for (auto& e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
   if (h->graph) (void)hipGraphDestroy(h->graph);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
+  delete h;  // (the device buffers: every DevBuf member frees its own)
   return NL_OK;
 }
 
@@ -1395,20 +1367,20 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   const size_t n = (size_t)n_max;
   const size_t pos_bytes = h->dtype == NL_F32 ? sizeof(Pos<float>) : sizeof(Pos<double>);
   int rc;
-  if ((rc = dev_alloc(h, &h->rank, 4 * (n + 16)))) return rc;
-  if ((rc = dev_alloc(h, &h->sorted, pos_bytes * (n + 16)))) return rc;
-  if ((rc = dev_alloc(h, &h->sorted_row, 4 * (n + 64)))) return rc;  // (+64: k_fill_masks reads whole row batches)
-  if ((rc = dev_alloc(h, &h->sorted_gid, 4 * (n + 16)))) return rc;
-  if ((rc = dev_alloc(h, &h->count, 4 * (n + 32)))) return rc;
+  if ((rc = dev_alloc(h, h->rank, 4 * (n + 16)))) return rc;
+  if ((rc = dev_alloc(h, h->sorted, pos_bytes * (n + 16)))) return rc;
+  if ((rc = dev_alloc(h, h->sorted_row, 4 * (n + 64)))) return rc;  // (+64: k_fill_masks reads whole row batches)
+  if ((rc = dev_alloc(h, h->sorted_gid, 4 * (n + 16)))) return rc;
+  if ((rc = dev_alloc(h, h->count, 4 * (n + 32)))) return rc;
   // (zero once: a build that leaves out k_sweep_list_f32 -- and then runs again -- scans the stale counts of the cells it
   // listed, which must be counts of earlier builds, never garbage)
   HIPCHK(h, hipMemset(h->count, 0, 4 * (n + 32)));
-  if ((rc = dev_alloc(h, &h->key_pointer, 8 * (n + 32)))) return rc;  // int32 or int64 offsets (BuildPlan::wide)
-  if (h->kp_alt) (void)hipFree(h->kp_alt), h->kp_alt = nullptr;
+  if ((rc = dev_alloc(h, h->key_pointer, 8 * (n + 32)))) return rc;  // int32 or int64 offsets (BuildPlan::wide)
+  h->kp_alt.release();
   h->kp_alt_valid = false;
-  if (h->resort_buf) (void)hipFree(h->resort_buf), h->resort_buf = nullptr;
-  if ((rc = dev_alloc(h, &h->progress, 4 * (n + 16)))) return rc;
-  if ((rc = dev_alloc(h, &h->base_sorted, 8 * (n + 64)))) return rc;  // (dense builds only: k_fill_dense)
+  h->resort_buf.release();
+  if ((rc = dev_alloc(h, h->progress, 4 * (n + 16)))) return rc;
+  if ((rc = dev_alloc(h, h->base_sorted, 8 * (n + 64)))) return rc;  // (dense builds only: k_fill_dense)
   // chunk per block: 4096 particles, 8192 from half a million on (cfg 2: binning 60.7 -> 55.9 us, cfg 3 64.7 -> 58.0;
   // 16384: 65.7), more for very large N so that blk_base stays small
   h->bin_chunk = n >= (1 << 19) ? 8192 : 4096;
@@ -1416,20 +1388,18 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   while ((n + h->bin_chunk - 1) / h->bin_chunk > 1024) h->bin_chunk *= 2;
   h->bin_blocks = (int32_t)((n + h->bin_chunk - 1) / h->bin_chunk);
   if (h->bin_blocks < 1) h->bin_blocks = 1;
-  if ((rc = dev_alloc(h, &h->tmp_pos, pos_bytes * (n + 16)))) return rc;
-  if ((rc = dev_alloc(h, &h->tmp_row, 4 * (n + 16)))) return rc;
+  if ((rc = dev_alloc(h, h->tmp_pos, pos_bytes * (n + 16)))) return rc;
+  if ((rc = dev_alloc(h, h->tmp_row, 4 * (n + 16)))) return rc;
   h->tmp_slots = n + 16;  // (the buckets of the one-pass binning grow them on first use)
-  if (h->sweep_variant >= 3) {
-    if ((rc = dev_alloc(h, &h->masks, (size_t)MASK_ROW_BYTES * (n + 64)))) return rc;
-    h->masks_bytes = (size_t)MASK_ROW_BYTES * (n + 64);
-  }
-  if ((rc = dev_alloc(h, &h->dbg_buf, 8 * (64 + 4 * 4096)))) return rc;
+  if (h->sweep_variant >= 3)
+    if ((rc = dev_alloc(h, h->masks, (size_t)MASK_ROW_BYTES * (n + 64)))) return rc;
+  if ((rc = dev_alloc(h, h->dbg_buf, 8 * (64 + 4 * 4096)))) return rc;
   HIPCHK(h, hipMemset(h->dbg_buf, 0, 8 * (64 + 4 * 4096)));
-  if ((rc = dev_alloc(h, &h->totals, 8 * 4))) return rc;
+  if ((rc = dev_alloc(h, h->totals, 8 * 4))) return rc;
   HIPCHK(h, hipMemset(h->totals, 0, 32));
-  for (int32_t** b : {&h->row_start, &h->blk_base, &h->row_cursor, &h->full27_list, &h->cell_count, &h->cell_start, &h->cls_start})
-    if (*b) (void)hipFree(*b), *b = nullptr;  // (all of them anew, without holding the old ones meanwhile)
-  if (h->scan_look) (void)hipFree(h->scan_look), h->scan_look = nullptr;
+  for (DevBuf<int32_t>* b : {&h->row_start, &h->blk_base, &h->row_cursor, &h->full27_list, &h->cell_count, &h->cell_start, &h->cls_start})
+    b->release();  // (all of them anew, without holding the old ones meanwhile)
+  h->scan_look.release();
   h->mesh_cells_cap = h->mesh_rows_cap = 0;
   if ((rc = reserve_mesh(h, n))) return rc;
   h->n_max = n_max;
@@ -1510,7 +1480,7 @@ int nl_set_box(nl_handle_t h, double Lx, double Ly, double Lz, double xy, double
     if (!h->capacity_user) {  // estimate_capacity for the new volume, keeping the old list where it cannot grow
       const int64_t want = estimate_want(h);
       if (want > h->capacity) {
-        if (int rc = swap_alloc(h, &h->list, 4 * (size_t)want)) return restore(rc);
+        if (int rc = swap_alloc(h, h->list, 4 * (size_t)want)) return restore(rc);
         h->capacity = want;
       }
     }
@@ -1567,7 +1537,7 @@ int nl_set_capacity(nl_handle_t h, int64_t max_pairs) {
   if (h->pending) (void)finish(h, false);
   h->built = false;
   h->upd_valid = false;
-  int rc = dev_alloc(h, &h->list, 4 * (size_t)(max_pairs + 16));
+  int rc = dev_alloc(h, h->list, 4 * (size_t)(max_pairs + 16));
   if (rc) {
     h->capacity = 0;
     return rc;
@@ -1610,12 +1580,12 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
     return fail(h, NL_ERR_ARG);  // the two ghost layers would be the same layer
   }
   // an input-row exclusion table or a type table applies to whole single-device builds of its own particle count
-  if (filter_rows_only(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  if (filter_rows_only(h) && partial_build(a, part)) return fail(h, NL_ERR_STATE);
   // nl_set_box: slab and distributed builds need the box of nl_create, and a tilt needs both of its axes periodic
-  if (box_changed(h) && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  if (box_changed(h) && partial_build(a, part)) return fail(h, NL_ERR_STATE);
   if (!tilt_mask_ok(h)) return fail(h, NL_ERR_STATE);
   // nl_set_pair_images: the images are those of whole single-device builds, whose ids index the positions
-  if (h->pair_images && (a.slab || a.gid || a.dyn || part != PART_ALL)) return fail(h, NL_ERR_STATE);
+  if (h->pair_images && partial_build(a, part)) return fail(h, NL_ERR_STATE);
   if (excl_refuses(h, a.gid, n_rows) || (h->ty_types && n != h->ty_n)) return fail(h, NL_ERR_ARG);
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = stage_reserve(h)) return rc;  // (again, if an allocation failed since a table or the flag was set)
@@ -1764,11 +1734,8 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream) {
       if ((rc = types_relabel(h))) return rc;
     h->ex_relabel = false;
   }
-  if (!h->resort_buf) {
-    void* p = nullptr;
-    if (hipMalloc(&p, 32 * ((size_t)h->n_max + 16)) != hipSuccess) return fail(h, NL_ERR_NOMEM);
-    h->resort_buf = p;
-  }
+  if (!h->resort_buf)
+    if ((rc = side_alloc(h, h->resort_buf, 32 * ((size_t)h->n_max + 16)))) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (s != h->last_stream) HIPCHK(h, hipStreamSynchronize(h->last_stream));
   const uint32_t* src = static_cast<const uint32_t*>(array_dev);

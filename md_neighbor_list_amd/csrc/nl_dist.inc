@@ -46,13 +46,13 @@ struct nl_comm_s {
   nl_sendrecv_fn fn = nullptr;
   void* user = nullptr;
   // message buffers: [header element | cap particles] each; send: down (my bottom layer), up; recv: from below, from above
-  void* send_buf[2] = {nullptr, nullptr};
-  void* recv_buf[2] = {nullptr, nullptr};
+  DevBuf<void> send_buf[2];
+  DevBuf<void> recv_buf[2];
   int64_t scap[2] = {0, 0}, rcap[2] = {0, 0};  // negotiated capacities (particles) of the four messages
   int64_t salloc[2] = {0, 0}, ralloc[2] = {0, 0};  // particles the buffers have room for
   size_t elem = 0;           // bytes per particle (and of the header element)
   int32_t need = HALO_MESSAGES;    // messages whose capacity has to be (re)negotiated before the next build
-  int32_t* counts_dev = nullptr;   // [0..1] packed counts (bottom, top), [2..3] ghost counts (from below, from above), [4] flags
+  DevBuf<int32_t> counts_dev;      // [0..1] packed counts (bottom, top), [2..3] ghost counts (from below, from above), [4] flags
   int32_t* counts_host = nullptr;  // pinned mirror, copied with every build
   bool check_pending = false;      // an asynchronous build's flags have not been looked at yet
   void* stage_host = nullptr;      // host staging of the callback transport
@@ -166,7 +166,7 @@ int comm_alloc(nl_comm_t c) {
   if (hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking) != hipSuccess) return NL_ERR_HIP;
   for (hipEvent_t* e : {&c->ev_ready, &c->ev_done, &c->ev_sent, &c->ev_unpacked, &c->ev_result})
     if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return NL_ERR_HIP;
-  if (hipMalloc(reinterpret_cast<void**>(&c->counts_dev), 8 * sizeof(int32_t)) != hipSuccess) return NL_ERR_NOMEM;
+  if (c->counts_dev.replace(8 * sizeof(int32_t)) != hipSuccess) return NL_ERR_NOMEM;
   if (hipMemset(c->counts_dev, 0, 8 * sizeof(int32_t)) != hipSuccess) return NL_ERR_HIP;
   if (hipHostMalloc(reinterpret_cast<void**>(&c->counts_host), 8 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return NL_ERR_NOMEM;
   memset(c->counts_host, 0, 8 * sizeof(int32_t));
@@ -184,15 +184,11 @@ int comm_grow(nl_comm_t c, size_t elem) {
   }
   for (int k = 0; k < 2; k++) {
     if (c->scap[k] > c->salloc[k]) {
-      if (c->send_buf[k]) (void)hipFree(c->send_buf[k]);
-      c->send_buf[k] = nullptr;
-      if (hipMalloc(&c->send_buf[k], ((size_t)c->scap[k] + 1) * c->elem + 64) != hipSuccess) return NL_ERR_NOMEM;
+      if (c->send_buf[k].replace(((size_t)c->scap[k] + 1) * c->elem + 64) != hipSuccess) return NL_ERR_NOMEM;
       c->salloc[k] = c->scap[k];
     }
     if (c->rcap[k] > c->ralloc[k]) {
-      if (c->recv_buf[k]) (void)hipFree(c->recv_buf[k]);
-      c->recv_buf[k] = nullptr;
-      if (hipMalloc(&c->recv_buf[k], ((size_t)c->rcap[k] + 1) * c->elem + 64) != hipSuccess) return NL_ERR_NOMEM;
+      if (c->recv_buf[k].replace(((size_t)c->rcap[k] + 1) * c->elem + 64) != hipSuccess) return NL_ERR_NOMEM;
       c->ralloc[k] = c->rcap[k];
     }
   }
@@ -244,17 +240,12 @@ int nl_comm_destroy(nl_comm_t c) {
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->comm && c->p_CommDestroy) (void)c->p_CommDestroy(c->comm);
   if (c->last_h && c->last_h->args.dyn_host == c->counts_host) c->last_h->args.dyn_host = nullptr, c->last_h->args.dyn = nullptr;
-  for (int k = 0; k < 2; k++) {
-    if (c->send_buf[k]) (void)hipFree(c->send_buf[k]);
-    if (c->recv_buf[k]) (void)hipFree(c->recv_buf[k]);
-  }
-  if (c->counts_dev) (void)hipFree(c->counts_dev);
   if (c->counts_host) (void)hipHostFree(c->counts_host);
   if (c->stage_host) (void)hipHostFree(c->stage_host);
   for (hipEvent_t e : {c->ev_ready, c->ev_done, c->ev_sent, c->ev_unpacked, c->ev_result})
     if (e) (void)hipEventDestroy(e);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-  delete c;
+  delete c;  // (the message buffers and counts_dev: each DevBuf frees its own)
   return NL_OK;
 }
 

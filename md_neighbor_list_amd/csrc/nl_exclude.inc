@@ -252,86 +252,70 @@ int excl_build(nl_handle_t h, const int32_t* pairs, int64_t np, int32_t n, bool 
   if (2 * np > 2147483000LL) return fail(h, NL_ERR_ARG);
   hipStream_t s = h->own_stream;
   const size_t rows = (size_t)n + 32, ents = 2 * (size_t)np + 16;
-  int32_t *deg = nullptr, *off_raw = nullptr, *raw = nullptr, *srt = nullptr, *off_new = nullptr;
-  uint32_t* bad = nullptr;
-  uint64_t* look = nullptr;
+  DevBuf<int32_t> deg, off_raw, raw, srt, off_new;  // (freed on every way out)
+  DevBuf<uint32_t> bad;
+  DevBuf<uint64_t> look;
   const int32_t scan_nb = (int32_t)(((int64_t)n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-  auto release = [&]() {
-    for (void* p : {(void*)deg, (void*)off_raw, (void*)raw, (void*)srt, (void*)off_new, (void*)bad, (void*)look})
-      if (p) (void)hipFree(p);
-  };
   auto scan = [&](const int32_t* in, int32_t* out) -> int {
     if (!look) return launch_scan(h, in, n, out, h->totals + 2, s);
     hipLaunchKernelGGL(k_scan_chained<int32_t>, dim3(scan_nb), dim3(SCAN_THREADS), 0, s, in, (int64_t)n, look, scan_nb, h->totals + 2, out, h->status,
                        static_cast<uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr));
     return NL_OK;
   };
-  auto run = [&]() -> int {
-    if (hipMalloc(reinterpret_cast<void**>(&deg), 4 * rows) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&off_raw), 4 * rows) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&raw), 4 * ents) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&srt), 4 * ents) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&off_new), 4 * rows) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&bad), 16) != hipSuccess)
-      return fail(h, NL_ERR_NOMEM);
-    if (n > SCAN_SMALL_MAX && scan_nb > h->scan_blocks) {  // (k_scan_chained leaves its array zero again)
-      if (hipMalloc(reinterpret_cast<void**>(&look), 8 * ((size_t)scan_nb + 1)) != hipSuccess) return fail(h, NL_ERR_NOMEM);
-      HIPCHK(h, hipMemsetAsync(look, 0, 8 * ((size_t)scan_nb + 1), s));
-    }
-    HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
-    HIPCHK(h, hipMemsetAsync(bad, 0, 16, s));
-    const uint32_t pgrid = excl_grid(np, 256, 8 * h->num_cus), rgrid = excl_grid(n, 4, 16 * h->num_cus);
-    if (np > 0) hipLaunchKernelGGL(k_excl_degree, dim3(pgrid), dim3(256), 0, s, pairs, np, n, deg, bad);
-    HIPCHK(h, hipGetLastError());
-    if (validate) {
-      uint32_t b = 0;
-      HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(h, hipStreamSynchronize(s));
-      if (b) return fail(h, NL_ERR_ARG);
-    }
-    if (int rc = scan(deg, off_raw)) return rc;
-    HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
-    if (np > 0) hipLaunchKernelGGL(k_excl_scatter, dim3(pgrid), dim3(256), 0, s, pairs, np, off_raw, deg, raw);
-    if (n > 0) {
-      hipLaunchKernelGGL(k_excl_sort_rows, dim3(rgrid), dim3(256), 0, s, off_raw, raw, n, srt);
-      hipLaunchKernelGGL(k_excl_distinct, dim3(rgrid), dim3(256), 0, s, off_raw, srt, n, deg);
-    }
-    if (int rc = scan(deg, off_new)) return rc;
-    if (n > 0) hipLaunchKernelGGL(k_excl_pack, dim3(rgrid), dim3(256), 0, s, off_raw, srt, off_new, n, raw);
-    HIPCHK(h, hipGetLastError());
-    int32_t entries = 0;
-    HIPCHK(h, hipMemcpyAsync(&entries, off_new + n, 4, hipMemcpyDeviceToHost, s));
+  int rc;
+  if ((rc = side_alloc(h, deg, 4 * rows)) || (rc = side_alloc(h, off_raw, 4 * rows)) || (rc = side_alloc(h, raw, 4 * ents)) ||
+      (rc = side_alloc(h, srt, 4 * ents)) || (rc = side_alloc(h, off_new, 4 * rows)) || (rc = side_alloc(h, bad, 16)))
+    return rc;
+  if (n > SCAN_SMALL_MAX && scan_nb > h->scan_blocks) {  // (k_scan_chained leaves its array zero again)
+    if ((rc = side_alloc(h, look, 8 * ((size_t)scan_nb + 1)))) return rc;
+    HIPCHK(h, hipMemsetAsync(look, 0, 8 * ((size_t)scan_nb + 1), s));
+  }
+  HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
+  HIPCHK(h, hipMemsetAsync(bad, 0, 16, s));
+  const uint32_t pgrid = excl_grid(np, 256, 8 * h->num_cus), rgrid = excl_grid(n, 4, 16 * h->num_cus);
+  if (np > 0) hipLaunchKernelGGL(k_excl_degree, dim3(pgrid), dim3(256), 0, s, pairs, np, n, deg, bad);
+  HIPCHK(h, hipGetLastError());
+  if (validate) {
+    uint32_t b = 0;
+    HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    if (h->ex_ids && (int64_t)n + 1 <= h->ex_off_cap && (int64_t)entries <= h->ex_ids_cap) {
-      // into the buffers the table has: a graph the caller captured (an update, forces) keeps finding it there -- a
-      // relabel always fits (same n, same entries)
-      HIPCHK(h, hipMemcpyAsync(h->ex_off, off_new, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
-      HIPCHK(h, hipMemcpyAsync(h->ex_ids, raw, 4 * (size_t)entries, hipMemcpyDeviceToDevice, s));
-      HIPCHK(h, hipStreamSynchronize(s));
-    } else {  // the new table replaces the old one
-      h->buffers_epoch++;
-      if (h->ex_off) (void)hipFree(h->ex_off);
-      if (h->ex_ids) (void)hipFree(h->ex_ids);
-      h->ex_off = off_new, h->ex_ids = raw;
-      h->ex_off_cap = (int64_t)rows, h->ex_ids_cap = (int64_t)ents;
-      off_new = raw = nullptr;
-    }
-    h->ex_n = n;
-    h->ex_global = global;
-    h->ex_unique = entries / 2;
-    h->ex_gen++;
-    return NL_OK;
-  };
-  const int rc = run();
-  release();
-  return rc;
+    if (b) return fail(h, NL_ERR_ARG);
+  }
+  if ((rc = scan(deg, off_raw))) return rc;
+  HIPCHK(h, hipMemsetAsync(deg, 0, 4 * rows, s));
+  if (np > 0) hipLaunchKernelGGL(k_excl_scatter, dim3(pgrid), dim3(256), 0, s, pairs, np, off_raw, deg, raw);
+  if (n > 0) {
+    hipLaunchKernelGGL(k_excl_sort_rows, dim3(rgrid), dim3(256), 0, s, off_raw, raw, n, srt);
+    hipLaunchKernelGGL(k_excl_distinct, dim3(rgrid), dim3(256), 0, s, off_raw, srt, n, deg);
+  }
+  if ((rc = scan(deg, off_new))) return rc;
+  if (n > 0) hipLaunchKernelGGL(k_excl_pack, dim3(rgrid), dim3(256), 0, s, off_raw, srt, off_new, n, raw);
+  HIPCHK(h, hipGetLastError());
+  int32_t entries = 0;
+  HIPCHK(h, hipMemcpyAsync(&entries, off_new + n, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (h->ex_ids && 4 * ((size_t)n + 1) <= h->ex_off.bytes() && 4 * (size_t)entries <= h->ex_ids.bytes()) {
+    // into the buffers the table has: a graph the caller captured (an update, forces) keeps finding it there -- a
+    // relabel always fits (same n, same entries)
+    HIPCHK(h, hipMemcpyAsync(h->ex_off, off_new, 4 * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->ex_ids, raw, 4 * (size_t)entries, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+  } else {  // the new table replaces the old one
+    h->buffers_epoch++;
+    h->ex_off.adopt(off_new), h->ex_ids.adopt(raw);
+  }
+  h->ex_n = n;
+  h->ex_global = global;
+  h->ex_unique = entries / 2;
+  h->ex_gen++;
+  return NL_OK;
 }
 
 void excl_clear(nl_handle_t h) {
-  for (void* b : {h->ex_off, h->ex_ids})
-    if (b) (void)hipFree(b);
-  h->ex_off = h->ex_ids = nullptr;
+  h->ex_off.release(), h->ex_ids.release();
   if (!h->ty_types) filter_release(h);
   h->ex_n = 0, h->ex_unique = 0;
   h->ex_global = false;
-  h->ex_off_cap = h->ex_ids_cap = 0;
   h->ex_gen++;
   h->buffers_epoch++;
 }
@@ -340,22 +324,16 @@ void excl_clear(nl_handle_t h) {
 int excl_relabel(nl_handle_t h) {
   const int32_t n = h->ex_n;
   const int64_t entries = 2 * h->ex_unique;
-  int32_t *inv = nullptr, *pairs = nullptr;
+  DevBuf<int32_t> inv, pairs;
   hipStream_t s = h->own_stream;
   HIPCHK(h, hipDeviceSynchronize());  // (replays of a graph the caller captured may still read the table)
-  int rc = NL_OK;
-  if (hipMalloc(reinterpret_cast<void**>(&inv), 4 * ((size_t)n + 16)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&pairs), 8 * ((size_t)entries + 16)) != hipSuccess) {
-    rc = fail(h, NL_ERR_NOMEM);
-  } else if (n > 0) {
-    hipLaunchKernelGGL(k_excl_inverse, dim3((n + 255) / 256), dim3(256), 0, s, h->sorted_row, n, inv);
-    hipLaunchKernelGGL(k_excl_relabel, dim3((n + 255) / 256), dim3(256), 0, s, h->ex_off, h->ex_ids, inv, n, pairs);
-    if (hipGetLastError() != hipSuccess) rc = fail(h, NL_ERR_HIP);
-    if (!rc) rc = excl_build(h, pairs, entries, n, false, false);
-  }
-  if (inv) (void)hipFree(inv);
-  if (pairs) (void)hipFree(pairs);
-  return rc;
+  if (int rc = side_alloc(h, inv, 4 * ((size_t)n + 16))) return rc;
+  if (int rc = side_alloc(h, pairs, 8 * ((size_t)entries + 16))) return rc;
+  if (n == 0) return NL_OK;
+  hipLaunchKernelGGL(k_excl_inverse, dim3((n + 255) / 256), dim3(256), 0, s, h->sorted_row, n, inv);
+  hipLaunchKernelGGL(k_excl_relabel, dim3((n + 255) / 256), dim3(256), 0, s, h->ex_off, h->ex_ids, inv, n, pairs);
+  if (hipGetLastError() != hipSuccess) return fail(h, NL_ERR_HIP);
+  return excl_build(h, pairs, entries, n, false, false);
 }
 
 // nl_set_exclusions (rows: n <= n_max) and nl_set_exclusions_global (ids: as many as the caller names; the row loops

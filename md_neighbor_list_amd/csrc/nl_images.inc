@@ -264,7 +264,7 @@ int nl_get_pair_images(nl_handle_t h, const int8_t** images_dev, int64_t* nentri
   int rc = nl_synchronize(h);
   if (rc) return rc;
   if (!h->plan.images) return fail(h, NL_ERR_STATE);
-  if (images_dev) *images_dev = reinterpret_cast<const int8_t*>(h->images);
+  if (images_dev) *images_dev = reinterpret_cast<const int8_t*>(h->images.get());
   if (nentries) *nentries = list_total(h);
   return NL_OK;
 }

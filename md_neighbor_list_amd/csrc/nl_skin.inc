@@ -169,13 +169,10 @@ int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n
   }
   if (force) {
     const size_t need = (h->dtype == NL_F32 ? 4 : 8) * 4 * ((size_t)h->n_max + 1);
-    if (h->snap_bytes < need) {
-      h->snap_bytes = 0;
-      if (int rc = dev_alloc(h, &h->snap, need)) return rc;
-      h->snap_bytes = need;
-    }
+    if (h->snap.bytes() < need)
+      if (int rc = dev_alloc(h, h->snap, need)) return rc;
     if (!h->skin_words) {
-      if (int rc = dev_alloc(h, &h->skin_words, sizeof(uint32_t) * SKIN_WORDS)) return rc;
+      if (int rc = dev_alloc(h, h->skin_words, sizeof(uint32_t) * SKIN_WORDS)) return rc;
       HIPCHK(h, hipMemset(h->skin_words, 0, sizeof(uint32_t) * SKIN_WORDS));
     }
   }

@@ -159,7 +159,7 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
     // buffer is not reallocated (and refilled with -1) whenever the longest row grows by one
     const int64_t rows = std::max<int32_t>(mx, 200);
     if (rows * (int64_t)std::max(n, 1) > h->t_rows_cap) {
-      if ((rc = dev_alloc(h, &h->t_list, 4 * (size_t)(rows * std::max(n, 1))))) return rc;
+      if ((rc = dev_alloc(h, h->t_list, 4 * (size_t)(rows * std::max(n, 1))))) return rc;
       h->t_rows_cap = rows * std::max(n, 1);
       HIPCHK(h, hipMemsetAsync(h->t_list, 0xFF, 4 * (size_t)h->t_rows_cap, s));  // -1 fill, once (neighlist_gpu.hpp:271)
     }
@@ -168,7 +168,7 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
       // build) and done by the tiled kernel, whose other workgroups leave at once
       const int32_t nblk = (n + 63) / 64;
       if (!h->t_cursor)
-        if ((rc = dev_alloc(h, &h->t_cursor, 4 * ((size_t)h->n_max + 16)))) return rc;
+        if ((rc = dev_alloc(h, h->t_cursor, 4 * ((size_t)h->n_max + 16)))) return rc;
       int32_t* const big = h->t_cursor + 1;  // [-1] = count
       HIPCHK(h, hipMemsetAsync(h->t_cursor, 0, 4, s));
       hipLaunchKernelGGL(k_csr_to_transposed_flat, dim3(nblk), dim3(256), 0, s, kp32, h->list, n, (int64_t)n, h->t_list, big);
@@ -184,8 +184,8 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
     hipStream_t s = h->own_stream;
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
     if (!h->t_count) {
-      if ((rc = dev_alloc(h, &h->t_count, 4 * ((size_t)h->n_max + 16)))) return rc;
-      if ((rc = dev_alloc(h, &h->t_cursor, 4 * ((size_t)h->n_max + 16)))) return rc;
+      if ((rc = dev_alloc(h, h->t_count, 4 * ((size_t)h->n_max + 16)))) return rc;
+      if ((rc = dev_alloc(h, h->t_cursor, 4 * ((size_t)h->n_max + 16)))) return rc;
     }
     const int32_t nb = (n + 255) / 256, nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
     int32_t mx = 0;
@@ -200,7 +200,7 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
     }
     const int64_t rows = std::max<int32_t>(mx, 1);
     if (rows * (int64_t)std::max(n, 1) > h->t_rows_cap) {
-      if ((rc = dev_alloc(h, &h->t_list, 4 * (size_t)(rows * std::max(n, 1))))) return rc;
+      if ((rc = dev_alloc(h, h->t_list, 4 * (size_t)(rows * std::max(n, 1))))) return rc;
       h->t_rows_cap = rows * std::max(n, 1);
     }
     if (n > 0) {

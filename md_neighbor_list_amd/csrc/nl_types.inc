@@ -176,10 +176,8 @@ int launch_filter(nl_handle_t h, int32_t n_rows, hipStream_t s) {
 }
 
 void types_clear(nl_handle_t h) {
-  for (void* b : {(void*)h->ty_types, h->ty_rc2})
-    if (b) (void)hipFree(b);
-  h->ty_types = nullptr, h->ty_rc2 = nullptr;
-  h->ty_n = 0, h->ty_ntypes = 0, h->ty_cap = 0;
+  h->ty_types.release(), h->ty_rc2.release();
+  h->ty_n = 0, h->ty_ntypes = 0;
   h->ty_gen++;
   h->buffers_epoch++;
   if (!h->ex_ids) filter_release(h);
@@ -189,19 +187,18 @@ void types_clear(nl_handle_t h) {
 // the same buffer (a graph the caller captured keeps reading it).
 int types_relabel(nl_handle_t h) {
   const int32_t n = h->ty_n;
-  int32_t* tmp = nullptr;
+  DevBuf<int32_t> tmp;
   hipStream_t s = h->own_stream;
   HIPCHK(h, hipDeviceSynchronize());  // (replays of a graph the caller captured may still read the types)
-  if (hipMalloc(reinterpret_cast<void**>(&tmp), 4 * ((size_t)n + 16)) != hipSuccess) return fail(h, NL_ERR_NOMEM);
+  if (int rc = side_alloc(h, tmp, 4 * ((size_t)n + 16))) return rc;
   int rc = NL_OK;
   if (n > 0) {
-    hipLaunchKernelGGL(k_gather_words<1>, dim3((n + 255) / 256), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(h->ty_types),
-                       h->sorted_row, n, reinterpret_cast<uint32_t*>(tmp));
+    hipLaunchKernelGGL(k_gather_words<1>, dim3((n + 255) / 256), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(h->ty_types.get()),
+                       h->sorted_row, n, reinterpret_cast<uint32_t*>(tmp.get()));
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h->ty_types, tmp, 4 * (size_t)n, hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
       rc = fail(h, NL_ERR_HIP);
   }
-  (void)hipFree(tmp);
   h->ty_gen++;
   return rc;
 }
@@ -228,38 +225,28 @@ int nl_set_type_cutoffs(nl_handle_t h, const int32_t* types_dev, int32_t n, int3
   HIPCHK(h, hipDeviceSynchronize());  // (the caller's types may come from any stream)
   hipStream_t s = h->own_stream;
   {
-    uint32_t* bad = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&bad), 16) != hipSuccess) return fail(h, NL_ERR_NOMEM);
+    DevBuf<uint32_t> bad;
+    if (int rc = side_alloc(h, bad, 16)) return rc;
     uint32_t b = 0;
-    hipError_t e = hipMemsetAsync(bad, 0, 16, s);
-    if (e == hipSuccess && n > 0) {
+    HIPCHK(h, hipMemsetAsync(bad, 0, 16, s));
+    if (n > 0) {
       hipLaunchKernelGGL(k_type_check, dim3((uint32_t)std::max(1, std::min((n + 255) / 256, 8 * h->num_cus))), dim3(256), 0, s, types_dev, n, ntypes, bad);
-      e = hipGetLastError();
+      HIPCHK(h, hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(bad);
-    HIPCHK(h, e);
+    HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
     if (b) return fail(h, NL_ERR_ARG);
   }
   // the table, in its buffers where they hold it (a graph the caller captured keeps reading them)
   const bool f32 = h->dtype == NL_F32;
   const size_t thr_bytes = (f32 ? 4 : 8) * (size_t)NL_MAX_TYPES * NL_MAX_TYPES;
-  if (!h->ty_types || h->ty_cap < (int64_t)n) {
-    void* old = h->ty_types;
-    int32_t* p = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&p), 4 * ((size_t)h->n_max + 16)) != hipSuccess) return fail(h, NL_ERR_NOMEM);
-    if (old) (void)hipFree(old);
-    h->ty_types = p, h->ty_cap = h->n_max;
-    h->buffers_epoch++;
-  }
-  if (!h->ty_rc2) {
-    if (hipMalloc(&h->ty_rc2, thr_bytes) != hipSuccess) {
+  if (!h->ty_types.holds(n))
+    if (int rc = swap_alloc(h, h->ty_types, 4 * ((size_t)h->n_max + 16), h->n_max)) return rc;
+  if (!h->ty_rc2)
+    if (int rc = swap_alloc(h, h->ty_rc2, thr_bytes)) {
       types_clear(h);
-      return fail(h, NL_ERR_NOMEM);
+      return rc;
     }
-    h->buffers_epoch++;
-  }
   double thr_d[NL_MAX_TYPES * NL_MAX_TYPES] = {};
   float thr_f[NL_MAX_TYPES * NL_MAX_TYPES] = {};
   for (int32_t a = 0; a < ntypes; a++)
@@ -313,7 +300,7 @@ int nl_set_lj_type_params(nl_handle_t h, int32_t ntypes, const double* epsilon, 
   const size_t bytes = (f32 ? 4 : 8) * 3 * (size_t)NT2;
   if (!h->lj_par) {
     HIPCHK(h, hipDeviceSynchronize());
-    if (hipMalloc(&h->lj_par, bytes) != hipSuccess) return fail(h, NL_ERR_NOMEM);
+    if (int rc = side_alloc(h, h->lj_par, bytes)) return rc;
   }
   double pd[3 * NT2] = {};
   float pf[3 * NT2] = {};

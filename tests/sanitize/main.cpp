@@ -1,7 +1,9 @@
 // tests/sanitize/main.cpp -- TEST INFRASTRUCTURE: runs the host shims (include/neighlist_cpu.hpp, include/neighlist_gpu.hpp),
 // the input generator (md_neighbor_list_amd/csrc/nl_inputs.cpp) and the oracle's C restatement (oracle/nl_oracle.c) under
 // AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (`make asan`; tests/test_sanitizers.py).  The shims talk to
-// tests/sanitize/abi_stub.cpp instead of libnl_hip.so.  Exit code 0 = every check passed and no sanitizer report.
+// tests/sanitize/abi_stub.cpp instead of libnl_hip.so.  And the owner of the library's device memory
+// (md_neighbor_list_amd/csrc/nl_devbuf.hpp) over stand-ins of hipMalloc / hipFree: tests/sanitize/devbuf_checks.cpp.
+// Exit code 0 = every check passed and no sanitizer report.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -25,6 +27,8 @@ void nl_oracle_canonicalize(int64_t, const int64_t*, int32_t*);
 uint64_t nl_oracle_hash(int64_t, const int64_t*, const int32_t*);
 void nl_oracle_free(void*);
 }
+
+int devbuf_checks();  // tests/sanitize/devbuf_checks.cpp: the checks that failed
 
 static int failures = 0;
 #define CHECK(cond)                                                      \
@@ -182,10 +186,11 @@ int main() {
   gpu_class<V4f, float>(1200, 13.0, 3.3);
   gpu_class<V4d, double>(900, 12.0, 3.0);
   oracle_edges();
+  failures += devbuf_checks();
   if (failures) {
     std::fprintf(stderr, "sanitize_test: %d check(s) FAILED\n", failures);
     return 1;
   }
-  std::printf("sanitize_test: all checks passed (shims, input generator, oracle restatement under ASan + UBSan)\n");
+  std::printf("sanitize_test: all checks passed (shims, input generator, oracle restatement, device-memory owner under ASan + UBSan)\n");
   return 0;
 }
