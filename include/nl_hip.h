@@ -241,7 +241,8 @@ int nl_make_list_slab_finish(nl_handle_t h, void* stream, int sync);
  *   layer outgrew its message (that one reports NL_ERR_CAPACITY at its synchronisation; with sync == 1 it renegotiates and
  *   repeats itself), exchange the counts through the host.
  * nl_distributed_ghosts: the ghost counts of the last build (rows [n_owned, n_owned + lo) and the hi rows behind); waits for
- *   that build. */
+ *   that build.
+ * Tested per rank, row by row against the global list, on every search path, mask and capacity edge: tests/test_distributed_paths.py. */
 typedef struct nl_comm_s* nl_comm_t;
 #define NL_UNIQUE_ID_BYTES 128
 typedef int (*nl_sendrecv_fn)(void* user, int peer_to, const void* send, size_t send_bytes, int peer_from, void* recv,

@@ -94,8 +94,9 @@ class DistributedNeighList:
 
     def scatter(self, q_global: torch.Tensor, box, rc, gid_global=None, slack=1.5):
         """Keeps this rank's slab of a (synthetic) global box: owned particles first, the global id in the w component,
-        room for the ghosts behind them.  Outside the timed build, like slab.setup."""
-        iz = slab.z_layer(q_global, box, rc)
+        room for the ghosts behind them.  Outside the timed build, like slab.setup.  Filed by the library's own rule: the
+        floor of the z cell index where the handle's mask has z periodic, the reference's truncation where it is open."""
+        iz = slab.z_layer(q_global, box, rc, periodic_z=self.nl.periodic_axes[2])
         own = (iz >= self.z_lo) & (iz < self.z_hi)
         if gid_global is None:
             gid_global = torch.arange(q_global.shape[0], dtype=torch.int32, device=q_global.device)

@@ -20,7 +20,8 @@ from md_neighbor_list_amd import inputs, slab
 from tests.test_periodic_axes import reference as padded_reference
 
 RC = 3.3
-BOXES = {"A": (10.5, 10.5, 24.0), "B": (17.0, 13.5, 20.5), "C": (17.0, 17.0, 27.5)}
+BOXES = {"A": (10.5, 10.5, 24.0), "B": (17.0, 13.5, 20.5), "C": (17.0, 17.0, 27.5),
+         "D": (10.5, 10.5, 10.5), "E": (10.5, 10.5, 13.5)}  # D = 3 x 3 x 3, E = 3 x 3 x 4: tests/test_distributed_paths.py
 DECOMPS = {
     "A1": ("A", ((0, 1), (1, 4), (4, 7))),  # a one-layer slab at the box bottom (z_first = -1); the top slab's upper ghost is layer 0
     "A2": ("A", ((0, 5), (5, 7))),          # mz - owned = 2: each rank's two ghost layers are the other rank's end layers
@@ -63,7 +64,7 @@ def make_input(box_name, per_cell, dtype_name, kind="uniform", extra=0):
     dt = np.dtype(dtype_name).type
     m = mesh(box)
     n = per_cell * m[0] * m[1] * m[2]
-    seed = 1000 * "ABC".index(box_name) + per_cell + (500 if dt == np.float64 else 0)
+    seed = 1000 * "ABCDE".index(box_name) + per_cell + (500 if dt == np.float64 else 0)
     q, _ = inputs.uniform_box(n, dtype=dt, seed=seed, box=box)
     rng = np.random.default_rng(seed + 7)
     ms = [b / k for b, k in zip(box, m)]
@@ -134,8 +135,12 @@ def _symmetrised(kp, lst):
 def global_list(key, mask, full):
     """(counts[n], key_pointer[n + 1], list) of the undivided box, per-row ascending, from the oracle alone.
     key: the arguments of make_input."""
-    q = make_input(*key)
-    box, po = BOXES[key[0]], _po()
+    return list_of(make_input(*key), BOXES[key[0]], mask, full)
+
+
+def list_of(q, box, mask, full):
+    """global_list for any positions: (counts[n], key_pointer[n + 1], list), per-row ascending, from the oracle alone."""
+    po = _po()
     if mask == 0:
         h = po.build(q, RC, box)
         return _symmetrised(h.key_pointer, h.sorted_list) if full else _canonical(h.key_pointer, h.sorted_list)
