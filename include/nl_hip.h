@@ -70,7 +70,9 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
 
 /* Replaces Initialize(N) (neighlist_gpu.hpp:268-287, neighlist_cpu.hpp:408-415): allocates every per-particle and
  * per-cell buffer for up to n_max particles.  The pair-list capacity defaults to an estimate from the number
- * density (1.3 x the ideal-gas half count + slack); see nl_set_capacity. Call once, or again to grow. */
+ * density (1.3 x the ideal-gas half count + slack); see nl_set_capacity. Call once, or again to grow.  A second call
+ * drops the list and every buffer sized by the old n_max (the transposed list among them); exclusion and type tables
+ * are kept: they go on filtering builds of their own n and refuse others (NL_ERR_ARG) until they are set again. */
 int nl_initialize(nl_handle_t h, int32_t n_max);
 
 /* Pair-list capacity in entries (int32 each).  A synchronous build grows the list by itself; an asynchronous
@@ -463,9 +465,16 @@ int nl_list_checksum(nl_handle_t h, uint64_t* checksum, int64_t* nentries);
  * CSR of a NL_LIST_FULL build (one coalesced pass), or derived on the device from the half list of a NL_LIST_HALF
  * build (scattered writes: about ten times slower).  Entries k >= count[i] hold -1 when the buffer is first
  * allocated or grown and whatever an earlier build left there afterwards (the reference fills -1 once in
- * Initialize and never again, neighlist_gpu.hpp:271).  *max_partners receives max_i count[i].  Synchronises.
+ * Initialize and never again, neighlist_gpu.hpp:271); after a NL_LIST_HALF build the buffer is filled anew by every
+ * fetch that follows a build.  nl_initialize and nl_set_list_kind drop the buffer: the next fetch allocates and fills
+ * it.  *row_stride is the n of the last build and changes with it (the buffer is kept while it holds rows x n
+ * entries); *max_partners receives max_i count[i].  A second call after the same build returns the same pointers
+ * without running a kernel.  Synchronises.
  * Whole single-device builds only: after a slab or distributed build, whose ids are global and not row indices,
- * NL_ERR_STATE. */
+ * NL_ERR_STATE.
+ * Tested (tests/test_handle_resize.py) on one handle across nl_initialize growth and builds of 0 to 12 000 particles,
+ * from half and full builds: counts, sorted columns, shape, padding where promised and the pair-set hash against the
+ * oracle; blocks of one build on both sides of the flat kernel's LDS piece; kind switches; wide offsets. */
 int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, const int32_t** count_dev, int64_t* row_stride,
                            int32_t* max_partners);
 

@@ -1379,6 +1379,9 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   h->kp_alt.release();
   h->kp_alt_valid = false;
   h->resort_buf.release();
+  // the transposed list and its per-particle counts and cursors (nl_get_full_transposed: sized by n_max on first use)
+  h->t_list.release(), h->t_count.release(), h->t_cursor.release();
+  h->t_rows_cap = 0;
   if ((rc = dev_alloc(h, h->progress, 4 * (n + 16)))) return rc;
   if ((rc = dev_alloc(h, h->base_sorted, 8 * (n + 64)))) return rc;  // (dense builds only: k_fill_dense)
   // chunk per block: 4096 particles, 8192 from half a million on (cfg 2: binning 60.7 -> 55.9 us, cfg 3 64.7 -> 58.0;

@@ -167,8 +167,8 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
       // flat kernel first; the blocks whose 64 rows exceed its LDS piece are listed (in t_cursor, unused after a full
       // build) and done by the tiled kernel, whose other workgroups leave at once
       const int32_t nblk = (n + 63) / 64;
-      if (!h->t_cursor)
-        if ((rc = dev_alloc(h, h->t_cursor, 4 * ((size_t)h->n_max + 16)))) return rc;
+      // (one int per particle of n_max, as the half path sizes it: nblk + 1 <= n_max + 16; nl_initialize releases it)
+      if ((rc = follow(h, h->t_cursor, h->n_max, 4 * ((size_t)h->n_max + 16)))) return rc;
       int32_t* const big = h->t_cursor + 1;  // [-1] = count
       HIPCHK(h, hipMemsetAsync(h->t_cursor, 0, 4, s));
       hipLaunchKernelGGL(k_csr_to_transposed_flat, dim3(nblk), dim3(256), 0, s, kp32, h->list, n, (int64_t)n, h->t_list, big);
@@ -183,10 +183,10 @@ extern "C" int nl_get_full_transposed(nl_handle_t h, const int32_t** list_dev, c
   if (!h->t_valid) {
     hipStream_t s = h->own_stream;
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
-    if (!h->t_count) {
-      if ((rc = dev_alloc(h, h->t_count, 4 * ((size_t)h->n_max + 16)))) return rc;
-      if ((rc = dev_alloc(h, h->t_cursor, 4 * ((size_t)h->n_max + 16)))) return rc;
-    }
+    // one count and one cursor per particle of the handle's n_max (nl_initialize releases both: a handle that has grown
+    // since the last fetch gets them anew)
+    if ((rc = follow(h, h->t_count, h->n_max, 4 * ((size_t)h->n_max + 16)))) return rc;
+    if ((rc = follow(h, h->t_cursor, h->n_max, 4 * ((size_t)h->n_max + 16)))) return rc;
     const int32_t nb = (n + 255) / 256, nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
     int32_t mx = 0;
     if (n > 0) {

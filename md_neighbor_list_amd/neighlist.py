@@ -418,7 +418,10 @@ class NeighListGPU:
         check(self._lib.nl_synchronize(self._h), "nl_synchronize")
 
     def neigh_list(self):
-        """neighlist_gpu.hpp:468-474: full list, transposed, ``[k, i]`` = k-th neighbour of i, -1 padded."""
+        """neighlist_gpu.hpp:468-474: full list, transposed, ``[k, i]`` = k-th neighbour of i for ``k < count[i]``
+        (nl_get_full_transposed); the number of columns is the n of the last build.  Entries ``k >= count[i]`` hold -1
+        after a half build, and after a full build when the buffer was just allocated or grown (the first fetch, one
+        after ``Initialize`` or ``set_full_list``) -- otherwise whatever an earlier build left there."""
         lst, cnt, stride, mx = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int32()
         check(self._lib.nl_get_full_transposed(self._h, C.byref(lst), C.byref(cnt), C.byref(stride), C.byref(mx)),
               "nl_get_full_transposed")

@@ -107,6 +107,19 @@ int devbuf_checks() {
     CHECK(g.ensure(12, 48) == hipErrorOutOfMemory && !g && !g.holds(0) && g.items() == 0 && live == 0);
     CHECK(g.ensure(12, 48) == hipSuccess && g.holds(12));  // (and the next call tries again)
   }
+  {  // sized by n_max on first use and re-checked with holds() by every later use, released when the handle is initialised
+    // again (the counts and cursors of nl_get_full_transposed): taken for n_max = 300, it never serves n_max = 6000
+    DevBuf<int32_t> t;
+    auto first_use = [&t](int64_t n_max) { return t.ensure(n_max, 4 * ((size_t)n_max + 16)); };
+    CHECK(first_use(300) == hipSuccess && t.items() == 300 && t.bytes() == 4 * 316);
+    t.get()[315] = 1;
+    CHECK(!t.holds(6000));  // (with or without the release in between)
+    CHECK(first_use(6000) == hipSuccess && t.items() == 6000 && t.bytes() == 4 * 6016 && live == 1);
+    t.get()[5999] = 1;  // (what the kernels write for a build of 6000: inside, or ASan reports it)
+    t.release();  // nl_initialize
+    CHECK(!t.holds(0) && live == 0);
+    CHECK(first_use(300) == hipSuccess && t.bytes() == 4 * 316 && live == 1);  // (a handle made smaller: a small one again)
+  }
   {  // move-assignment onto a buffer that holds something; move construction; self-adoption
     DevBuf<int32_t> a, b;
     CHECK(a.replace(40, 10) == hipSuccess && b.replace(80, 20) == hipSuccess && live == 2);
