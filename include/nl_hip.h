@@ -287,7 +287,8 @@ int nl_synchronize(nl_handle_t h);
  *   the caller is capturing, an update enqueues plain launches; one that the host would have to force (first build,
  *   growth) or that would wait for another stream is NL_ERR_STATE there.  Slab and distributed builds have no update.
  *   nl_get_update_stats: stats[0] = updates enqueued, stats[1] = builds they performed (device counters, including the
- *   replays of captured updates); waits for the device. */
+ *   replays of captured updates); waits for the device.
+ * Tested on every search path, binning, offset width and list kind, skipped updates byte for byte: tests/test_update_paths.py. */
 int nl_set_skin(nl_handle_t h, double skin);
 int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, void* stream, int sync);
 int nl_get_update_stats(nl_handle_t h, int64_t stats[2]);

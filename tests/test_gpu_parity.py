@@ -360,7 +360,7 @@ def _full_from_half(h):
 @pytest.mark.parametrize("case", [
     (50000, (36.84, 36.84, 36.84), 3.3, 51),  # hit-mask path
     (9000, (25.0, 14.0, 19.0), 3.1, 52),      # non-cubic
-    (40000, (20.0, 20.0, 20.0), 3.3, 53),     # rho 5: two full sweeps / multi-batch re-search
+    (40000, (20.0, 20.0, 20.0), 3.3, 53),     # rho 5 (185 per cell): hit masks over five LDS batches, the dense build
 ])
 def test_full_list_matches_the_symmetrised_oracle(case, dtype):
     """NL_LIST_FULL (the reference GPU kernels' contract: every j != i within the cut-off, kernel_impl.cuh:24-33):
@@ -375,6 +375,8 @@ def test_full_list_matches_the_symmetrised_oracle(case, dtype):
     nl = NeighListGPU(rc, *box, dtype=torch.float32 if dtype == np.float32 else torch.float64, full_list=True)
     nl.Initialize(n)
     nl.MakeNeighList(torch.from_numpy(q).cuda(), n)
+    if n == 40000:  # (the densest input of this file: a five-row dense-mask build in both position types)
+        assert nl.build_info()["masks"] and nl.build_info()["mask_rows"] == 5, nl.build_info()
     kp, lst, cnt = (t.cpu().numpy() for t in nl.full_csr())
     assert nl.number_of_pairs() == int(want_kp[-1]) and nl.half_number_of_pairs() * 2 == int(want_kp[-1])
     assert np.array_equal(cnt, want_cnt)
