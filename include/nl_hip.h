@@ -183,7 +183,9 @@ int nl_destroy(nl_handle_t h);
  * The build is ordered after everything already queued on that stream (the kernel that produced q, a halo
  * exchange) and nothing else: positions written on ANOTHER stream must be fenced by the caller.  sync != 0 waits for the build and returns its status; sync == 0 only
  * enqueues (the reference's timing loop, make_list.cu:124-127) and errors surface at the next nl_synchronize /
- * getter.  tblock_size and smem_hei of the reference select among its CUDA variants and have no counterpart. */
+ * getter.  tblock_size and smem_hei of the reference select among its CUDA variants and have no counterpart.
+ * Tested against the oracle at the mesh sizes where the build changes its binning, its row tables are full and its
+ * scans take more than 64 blocks (needles, plates, dilute cubes): tests/test_mesh_limits.py. */
 int nl_make_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, void* stream, int sync);
 
 /* Slab (domain-decomposed) build, SURVEY.md section 8e -- no reference counterpart (the reference is single GPU).
@@ -556,8 +558,11 @@ int nl_debug_occupancy(int32_t out[8]); /* LDS per CU/block (KiB), occupancy API
  * dense build: one per LDS batch of the stencil stream), info[6] = 0, or 1 + c when the build took the fine-row search
  * (nl_rows.hpp; c = its LDS configuration 0..2) -- the table nl_get_sorted returns is then the fine-row table,
  * info[7] = 1 when the build used the small instances of the COUNT sweep and the expansion (sparse boxes: 2 waves /
- * 1 wave per cell, half the LDS buffer), else 0; bits 8.. of info[7] = C when the build took the id-class search
- * (k_sweep_class_f32: C = 2 or 4 classes of ids; NL_IDCLASS), else 0. */
+ * 1 wave per cell, half the LDS buffer), else 0; bits 8..15 of info[7] = C when the build took the id-class search
+ * (k_sweep_class_f32: C = 2 or 4 classes of ids; NL_IDCLASS), else 0; bits 16..17 of info[7] = the binning the build
+ * took: 0 = two passes over rows of x-cells, 1 = one pass into row buckets, 2 = atomic ranks into the cell histogram
+ * (NL_BINNING=1, and every mesh of more than 12288 rows of x-cells or more than 4096 cells a row; such a build has no
+ * fine rows and no id classes).  Asserted on both sides of those limits, lists against the oracle: tests/test_mesh_limits.py. */
 int nl_get_build_info(nl_handle_t h, int32_t info[8]);
 /* How the builds of this handle ran: stats[0] = builds run again because a row of x-cells overflowed its bucket in the
  * one-pass binning, stats[1] = builds run again because cells whose stencil exceeds the LDS buffer were there while the

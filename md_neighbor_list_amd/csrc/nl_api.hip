@@ -1832,7 +1832,9 @@ int nl_get_build_info(nl_handle_t h, int32_t info[8]) {
   info[4] = p.wide ? 64 : 32;
   info[5] = p.mask_nb;
   info[6] = p.search == SEARCH_ROWS ? 1 + p.rows_v : 0;  // fine-row search: the cell table of nl_get_sorted is the fine-row table
-  info[7] = (p.small ? 1 : 0) | p.idc << 8;  // (bits 8..: classes of an id-class build)
+  // (bits 8..15: classes of an id-class build; bits 16..17: the binning, 0 = two-pass, 1 = bucket, 2 = atomic rank)
+  const int32_t binning = p.binning == BINNING_TWO_PASS ? 0 : p.binning == BINNING_BUCKET ? 1 : 2;
+  info[7] = (p.small ? 1 : 0) | p.idc << 8 | binning << 16;
   info[0] = p.search != SEARCH_SWEEPS ? 1 : 0;
   info[1] = h->sweep_variant;
   info[2] = h->dtype == NL_F32 ? SweepCfg<float>::CAP : SweepCfg<double>::CAP;
