@@ -538,6 +538,41 @@ int nl_set_lj_type_params(nl_handle_t h, int32_t ntypes, const double* epsilon, 
 int nl_lj_forces_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
 int nl_lj_forces_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
 
+/* The totals that belong to those forces: the virial tensor W, the potential energy U and the number of interacting pairs,
+ * for a pressure P = N k_B T / V + (W_xx + W_yy + W_zz) / (3 V).  out_dev: 8 doubles on the device, for both position
+ * types: {W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}.  The rule:
+ *   - The sum runs over the entries (row i, partner j) of the list of the last build: the filtered list where an
+ *     exclusion or type table is set.
+ *   - For each entry d comes from the image rule and fx, fy, fz, pe, in from the pair function of nl_lj_forces (lj_image,
+ *     lj_pair), with the same rc_force and parameter handling.
+ *   - The entry's terms are computed in the position type, one rounding each, without contraction: fx dx, fy dy, fz dz,
+ *     fx dy, fx dz, fy dz; pe (the pair's full energy); 1 if in (0 < r^2 < rc_force^2), else nothing.
+ *   - Each term is converted to double and summed in double.
+ *   - After a NL_LIST_HALF build every entry counts once, after a NL_LIST_FULL build 1/2 (exact), so both list kinds
+ *     report W_ab = sum over pairs d_a F_b, U = sum over pairs u(r), n_in = the number of pairs within rc_force.
+ *   - Sign: d = r_i - r_j and F the force on i, so repulsion gives positive diagonal terms (the LAMMPS convention).
+ *   - Ordering, the state required, the rc_force <= rc test (<= rc - skin for the enqueue variants) and the typed
+ *     variants' conditions are exactly those of the four force calls; slab and distributed builds: NL_ERR_STATE.
+ *   - Where the enqueue variants find a non-zero status word all 8 values are NaN; the error itself surfaces at the next
+ *     nl_synchronize.  n == 0 gives 8 zeros.
+ *   - Reproducible: no floating-point atomics anywhere, every sum has a fixed order.  Two calls on the same list and
+ *     positions on the same device give the same 8 doubles, bit for bit.  (Half and full builds of the same input order
+ *     their sums differently and agree within the bound below, not bit for bit.)
+ *   - Rows are dealt to one wave each over a grid of min(ceil(n / 4), NL_VIRIAL_BLOCKS) blocks of 4 waves; each block
+ *     leaves one partial of 8 doubles in a scratch buffer of the handle, which a second kernel adds up.  The first call
+ *     allocates that buffer: on a stream that is being captured it returns NL_ERR_STATE (call once before the capture).
+ *     Calls on one handle share it, so they must be ordered against each other, as everything else on a handle.
+ *   - The enqueue variants copy nothing from the host and can be captured, as nl_lj_forces_enqueue.
+ * Tested contract (tests/test_lj_virial.py): every component within c_W u S of an O(N^2) float64 sum,
+ * S that component's uncancelled sum; n_in exact where no pair lies within 2^-17 (relative, r^2) of a cut-off. */
+#define NL_VIRIAL_BLOCKS 2048
+int nl_lj_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
+                 double* out_dev, void* stream);
+int nl_lj_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
+                         double* out_dev, void* stream);
+int nl_lj_virial_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+int nl_lj_virial_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------- introspection */
 
 int nl_get_mesh(nl_handle_t h, int32_t mesh[3], int64_t* ncell);

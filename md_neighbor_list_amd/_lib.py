@@ -66,6 +66,10 @@ PROTOTYPES = {
     "nl_set_lj_type_params": (C.c_int, [_P, _I32, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
     "nl_lj_forces_typed": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_lj_forces_typed_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_lj_virial": (C.c_int, [_P, _P, _I32, _D, _D, _D, _P, _P]),
+    "nl_lj_virial_enqueue": (C.c_int, [_P, _P, _I32, _D, _D, _D, _P, _P]),
+    "nl_lj_virial_typed": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_lj_virial_typed_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_set_pair_images": (C.c_int, [_P, C.c_int]),
     "nl_get_pair_images": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64)]),
     "nl_pair_vectors": (C.c_int, [_P, _P, _I32, _P, _P]),

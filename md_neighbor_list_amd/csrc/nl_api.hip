@@ -246,6 +246,7 @@ struct nl_handle_s {
   DevBuf<void> lj_par;             // nl_set_lj_type_params: [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2 in T
   int32_t lj_ntypes = 0;
   double lj_rcf[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // rc_force_ab, [lj_ntypes][lj_ntypes]
+  DevBuf<double> vir_part;         // nl_lj_virial (nl_virial.inc): [NL_VIRIAL_BLOCKS][8] block partials, allocated by the first call
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -1950,3 +1951,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_exclude.inc"
 #include "nl_types.inc"
 #include "nl_images.inc"
+#include "nl_virial.inc"

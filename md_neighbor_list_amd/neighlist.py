@@ -514,6 +514,41 @@ class NeighListGPU:
               "nl_lj_forces" if wait else "nl_lj_forces_enqueue")
         return f
 
+    def _virial_out(self, q, out):
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        w = torch.empty(8, dtype=torch.float64, device=self.device) if out is None else out
+        if w.shape != (8,) or w.dtype != torch.float64 or not w.is_contiguous() or w.device != q.device:
+            raise TypeError("out must be a contiguous float64 tensor of 8 on the list's device")
+        return w, torch.cuda.current_stream(self.device).cuda_stream
+
+    def lj_virial(self, q, epsilon=1.0, sigma=1.0, rc_force=None, wait=True, out=None):
+        """The totals that belong to lj_forces (nl_lj_virial): a float64 device tensor
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}`` for both dtypes, W_ab = sum over pairs d_a F_b (d = r_i - r_j, F on
+        i: repulsion is positive), U the potential energy, n_in the pairs within rc_force; the same for a half and a full
+        list, without floating-point atomics and bit for bit reproducible.
+        Pressure: ``P = N kT / V + (w[0] + w[1] + w[2]) / (3 V)``.
+        ``wait``, ``rc_force`` and ``out`` (a float64 tensor of 8) as for lj_forces; with ``wait=False``
+        (nl_lj_virial_enqueue) a list whose build failed gives 8 NaN.  The first call allocates scratch: make it before
+        a graph capture."""
+        w, stream = self._virial_out(q, out)
+        if rc_force is None:
+            rc_force = self.search_length if wait else self.search_length - self.skin
+        fn = self._lib.nl_lj_virial if wait else self._lib.nl_lj_virial_enqueue
+        check(fn(self._h, q.data_ptr(), q.shape[1], float(epsilon), float(sigma), float(rc_force), w.data_ptr(), stream),
+              "nl_lj_virial" if wait else "nl_lj_virial_enqueue")
+        return w
+
+    def lj_virial_typed(self, q, wait=True, out=None):
+        """lj_virial with the parameters of set_lj_type_params, per pair of types (nl_lj_virial_typed); ``wait=False``:
+        nl_lj_virial_typed_enqueue."""
+        w, stream = self._virial_out(q, out)
+        fn = self._lib.nl_lj_virial_typed if wait else self._lib.nl_lj_virial_typed_enqueue
+        check(fn(self._h, q.data_ptr(), q.shape[1], w.data_ptr(), stream),
+              "nl_lj_virial_typed" if wait else "nl_lj_virial_typed_enqueue")
+        return w
+
     # ------------------------------------------------------------------ periodic re-sorting (SORT_FREQ)
     def cell_order(self):
         """order[s] = input index of the particle at cell-ordered slot s of the last build (nl_get_cell_order; the

@@ -19,8 +19,10 @@ The rebuild trigger (--trigger):
           is enqueued without a host sync; --graph captures one whole step (integrate, update, forces) into a
           torch.cuda.graph and replays it.  The re-sort reads update_stats() every SORT_CHECK steps.
 
+--pressure prints P = N kT / V + tr W / (3 V) at the end, W from nl_lj_virial on the loop's list (V: the whole box).
+
 usage: tools/md_loop.py [--cells 12] [--steps 400] [--dtype f64] [--trigger host|device] [--graph]
-                        [--periodic none|xyz|xy]
+                        [--periodic none|xyz|xy] [--pressure]
 """
 import argparse
 import os
@@ -160,6 +162,13 @@ class Simulation:
     def energy(self):
         return float(self.f[:, 3].sum() + 0.5 * self.v.square().sum())
 
+    def pressure(self):
+        """(P, U) from nl_lj_virial on the current list: P = N kT / V + tr W / (3 V) with N kT = sum v^2 / 3."""
+        self.nl.synchronize()  # (the device trigger's last update may sit on a captured step's stream)
+        w = self.nl.lj_virial(self.q, 1.0, 1.0, rc_force=self.rc)
+        volume = float(np.prod(self.edges))
+        return float(self.v.square().sum() / 3.0 + w[:3].sum() / 3.0) / volume, float(w[6])
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -170,6 +179,7 @@ def main():
     ap.add_argument("--graph", action="store_true", help="device trigger: replay one captured step")
     ap.add_argument("--periodic", default="none", choices=["none", "xyz", "xy"],
                     help="minimum image: none (a droplet in an open box), xyz (a crystal filling the box), xy (a film)")
+    ap.add_argument("--pressure", action="store_true", help="print the pressure and the potential energy from nl_lj_virial")
     args = ap.parse_args()
     a, box = 1.56, 4.0 * args.cells
     dt_np = np.float32 if args.dtype == "f32" else np.float64
@@ -193,6 +203,9 @@ def main():
     print(f"N={len(q)} periodic={args.periodic} trigger={args.trigger}{'+graph' if args.graph else ''} steps={args.steps} builds={sim.build_count()} "
           f"re-sorts={sim.sorts} E0={e0:.6f} E1={e1:.6f} "
           f"drift={(e1 - e0) / abs(e0):.2e} {1e3 * dt / args.steps:.3f} ms/step")
+    if args.pressure:
+        p, u = sim.pressure()
+        print(f"P={p:.6f} U={u:.6f} (nl_lj_virial)")
 
 
 if __name__ == "__main__":
