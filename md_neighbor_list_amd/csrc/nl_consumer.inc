@@ -5,7 +5,9 @@
 //   half list: every pair once, the reaction goes to f[j] with floating-point atomics.
 // nl_lj_forces takes one epsilon, sigma and rc_force; nl_lj_forces_typed takes them per pair of types (nl_types.inc sets the
 // tables).  One kernel body (lj_row) and one launch serve both.
-// Included at the end of nl_api.hip.
+// What the totals of nl_virial.inc share with the forces is written once, here (DESIGN.md section 8l): the arguments of a
+// launch (LjArgs, lj_args), the walk of a row up to the pair's values (lj_row_pairs over lj_image and lj_pair), and what
+// an entry point checks before its launch (lj_call).  Included at the end of nl_api.hip.
 
 namespace {
 
@@ -89,22 +91,24 @@ template <typename T> struct LjByType {
   const T* __restrict__ par;  // [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2
 };
 
-// one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i.  status (the enqueue
-// variants, which do not wait for the build): the build's status word; a list whose build failed gives NaN forces.
+// What every kernel over the pairs of the list receives (k_lj*, k_lj_virial*).  status (the enqueue variants, which do not
+// wait for the build): the build's status word, nullptr otherwise.
+template <typename T, typename OFF> struct LjArgs {
+  const T* __restrict__ q;
+  int32_t stride;
+  const OFF* __restrict__ kp;
+  const int32_t* __restrict__ list;
+  int32_t n;
+  const uint32_t* __restrict__ status;
+  T Lx, Ly, Lz, xy, xz, yz;
+};
+
+// The pairs of one row, a wave per row: on_pair(j, dx, dy, dz, fx, fy, fz, pe, in) for every entry of the row, with the
+// separation at the image the list found the pair at (minimum-image list, nl_set_periodic_axes: folded on the periodic axes,
+// L > 0) and the values of lj_pair.
 // By type: lane t < ntypes holds eps4, sig2 and rcf2 of (t_row, t), an entry picks them by its partner's type with ds_bpermute.
-template <typename T, bool HALF, typename OFF, bool TRI, typename PAR>
-__device__ __forceinline__ void lj_row(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp, const int32_t* __restrict__ list,
-                                       int32_t n, const PAR& p, T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status,
-                                       T xy, T xz, T yz) {
-  const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (row >= n) return;
-  if (status && *status != 0u) {  // (uniform: every row of the launch takes this branch)
-    if (lane == 0) {
-      const T nan = (T)NAN;
-      f[(size_t)row * 4 + 0] = nan, f[(size_t)row * 4 + 1] = nan, f[(size_t)row * 4 + 2] = nan, f[(size_t)row * 4 + 3] = nan;
-    }
-    return;
-  }
+template <typename T, typename OFF, bool TRI, typename PAR, typename F>
+__device__ __forceinline__ void lj_row_pairs(const LjArgs<T, OFF>& a, const PAR& p, int32_t row, int32_t lane, F&& on_pair) {
   T eps4, sig2, rcf2;  // scalars: the pair's; by type: this lane's entries of the row's type
   if constexpr (PAR::typed) {
     constexpr int NT2 = NL_MAX_TYPES * NL_MAX_TYPES;
@@ -114,12 +118,11 @@ __device__ __forceinline__ void lj_row(const T* __restrict__ q, int32_t stride, 
     eps4 = p.eps4, sig2 = p.sig2, rcf2 = p.rcf2;
   }
   T xi, yi, zi;
-  load_xyz(q, stride, row, xi, yi, zi);
-  T ax = 0, ay = 0, az = 0, ae = 0;
-  const OFF b = kp[row], e = kp[row + 1];
+  load_xyz(a.q, a.stride, row, xi, yi, zi);
+  const OFF b = a.kp[row], e = a.kp[row + 1];
   for (OFF k = b + lane; (PAR::typed ? k - lane : k) < e; k += 64) {  // (by type: every lane stays for the bpermute)
     const bool valid = !PAR::typed || k < e;
-    const int32_t j = valid ? list[k] : row;
+    const int32_t j = valid ? a.list[k] : row;
     T e4 = eps4, s2 = sig2, c2 = rcf2;
     if constexpr (PAR::typed) {
       const int32_t tj = p.types[j] & (NL_MAX_TYPES - 1);
@@ -127,14 +130,30 @@ __device__ __forceinline__ void lj_row(const T* __restrict__ q, int32_t stride, 
       if (!valid) continue;
     }
     T xj, yj, zj;
-    load_xyz(q, stride, j, xj, yj, zj);
-    T fx, fy, fz, pe;
+    load_xyz(a.q, a.stride, j, xj, yj, zj);
+    T dx, dy, dz, fx, fy, fz, pe;
     bool in;
-    T dx, dy, dz;
-    // minimum-image list (nl_set_periodic_axes): on a periodic axis (L > 0) the pair is taken at the image the list
-    // found it at
-    lj_image<T, TRI>(xi, yi, zi, xj, yj, zj, dx, dy, dz, Lx, Ly, Lz, xy, xz, yz);
+    lj_image<T, TRI>(xi, yi, zi, xj, yj, zj, dx, dy, dz, a.Lx, a.Ly, a.Lz, a.xy, a.xz, a.yz);
     lj_pair<T>(dx, dy, dz, e4, s2, c2, fx, fy, fz, pe, in);
+    on_pair(j, dx, dy, dz, fx, fy, fz, pe, in);
+  }
+}
+
+// one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i.  A list whose build failed
+// (status) gives NaN forces.
+template <typename T, bool HALF, typename OFF, bool TRI, typename PAR>
+__device__ __forceinline__ void lj_row(const LjArgs<T, OFF>& a, const PAR& p, T* __restrict__ f) {
+  const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (row >= a.n) return;
+  if (a.status && *a.status != 0u) {  // (uniform: every row of the launch takes this branch)
+    if (lane == 0) {
+      const T nan = (T)NAN;
+      f[(size_t)row * 4 + 0] = nan, f[(size_t)row * 4 + 1] = nan, f[(size_t)row * 4 + 2] = nan, f[(size_t)row * 4 + 3] = nan;
+    }
+    return;
+  }
+  T ax = 0, ay = 0, az = 0, ae = 0;
+  lj_row_pairs<T, OFF, TRI>(a, p, row, lane, [&](int32_t j, T, T, T, T fx, T fy, T fz, T pe, bool in) {
     ax += fx, ay += fy, az += fz, ae += (T)0.5 * pe;
     if (HALF && in) {  // Newton's third law: the partner's share
       atomicAdd(&f[(size_t)j * 4 + 0], -fx);
@@ -142,7 +161,7 @@ __device__ __forceinline__ void lj_row(const T* __restrict__ q, int32_t stride, 
       atomicAdd(&f[(size_t)j * 4 + 2], -fz);
       atomicAdd(&f[(size_t)j * 4 + 3], (T)0.5 * pe);
     }
-  }
+  });
   ax = wave_sum(ax), ay = wave_sum(ay), az = wave_sum(az), ae = wave_sum(ae);
   if (lane == 0) {
     if (HALF) {
@@ -157,19 +176,27 @@ __device__ __forceinline__ void lj_row(const T* __restrict__ q, int32_t stride, 
 }
 
 template <typename T, bool HALF, typename OFF, bool TRI>
-__global__ void __launch_bounds__(256) k_lj(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
-                                            const int32_t* __restrict__ list, int32_t n, T eps4, T sig2, T rcf2,
-                                            T* __restrict__ f, T Lx, T Ly, T Lz, const uint32_t* __restrict__ status,
-                                            T xy, T xz, T yz) {
-  lj_row<T, HALF, OFF, TRI>(q, stride, kp, list, n, LjScalars<T>{eps4, sig2, rcf2}, f, Lx, Ly, Lz, status, xy, xz, yz);
+__global__ void __launch_bounds__(256) k_lj(LjArgs<T, OFF> a, LjScalars<T> p, T* __restrict__ f) {
+  lj_row<T, HALF, OFF, TRI>(a, p, f);
 }
 template <typename T, bool HALF, typename OFF, bool TRI>
-__global__ void __launch_bounds__(256) k_lj_typed(const T* __restrict__ q, int32_t stride, const OFF* __restrict__ kp,
-                                                  const int32_t* __restrict__ list, int32_t n, const int32_t* __restrict__ types,
-                                                  const T* __restrict__ par, T* __restrict__ f, T Lx, T Ly, T Lz,
-                                                  const uint32_t* __restrict__ status, T xy, T xz, T yz) {
-  lj_row<T, HALF, OFF, TRI>(q, stride, kp, list, n, LjByType<T>{types, par}, f, Lx, Ly, Lz, status, xy, xz, yz);
+__global__ void __launch_bounds__(256) k_lj_typed(LjArgs<T, OFF> a, LjByType<T> p, T* __restrict__ f) {
+  lj_row<T, HALF, OFF, TRI>(a, p, f);
 }
+
+// The arguments of a launch over the handle's list (lj_launch, virial_launch).  Box lengths for the minimum image on the
+// axes of the list's build; 0 = open axis (the reference's distances, neighlist_cpu.hpp:219-223).  The box and the mask
+// are the build's (BuildPlan::box, BuildPlan::pbc), not what nl_set_box or nl_set_periodic_axes may have set since; the
+// launches take the triclinic instances where that box has a tilt (BuildPlan::tilt).
+// lj_scalars, lj_by_type: the parameters of a launch, the scalars rounded to T once.
+template <typename T, typename OFF> LjArgs<T, OFF> lj_args(nl_handle_t h, const void* q_dev, int32_t stride, const uint32_t* status) {
+  const Box& b = h->plan.box;
+  const int pbc = h->plan.pbc;
+  return {static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer), h->list, h->n, status,
+          (pbc & 1) ? (T)b.L[0] : (T)0, (pbc & 2) ? (T)b.L[1] : (T)0, (pbc & 4) ? (T)b.L[2] : (T)0, (T)b.xy, (T)b.xz, (T)b.yz};
+}
+template <typename T> LjScalars<T> lj_scalars(const double* lj) { return {(T)(4.0 * lj[0]), (T)(lj[1] * lj[1]), (T)(lj[2] * lj[2])}; }
+template <typename T> LjByType<T> lj_by_type(nl_handle_t h) { return {h->ty_types, static_cast<const T*>(h->lj_par)}; }
 
 // lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables.
 int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, void* f_dev, hipStream_t s, const uint32_t* status) {
@@ -179,23 +206,12 @@ int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj
     using T = decltype(t);
     using OFF = decltype(off);
     const int32_t nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
-    // box lengths for the minimum image on the axes of the list's build; 0 = open axis (the reference's distances,
-    // neighlist_cpu.hpp:219-223)
-    // (the build's box, BuildPlan::box, and its tilt: triclinic instances where it has one)
-    const Box& b = h->plan.box;
-    const T Lx = (h->plan.pbc & 1) ? (T)b.L[0] : (T)0, Ly = (h->plan.pbc & 2) ? (T)b.L[1] : (T)0, Lz = (h->plan.pbc & 4) ? (T)b.L[2] : (T)0;
-    const T xy = (T)b.xy, xz = (T)b.xz, yz = (T)b.yz;
-    const T* q = static_cast<const T*>(q_dev);
-    const OFF* kp = static_cast<const OFF*>(h->key_pointer);
+    const LjArgs<T, OFF> a = lj_args<T, OFF>(h, q_dev, stride, status);
     T* f = static_cast<T*>(f_dev);
     auto launch = [&](auto half, auto tri) {
       constexpr bool H = decltype(half)::value, R = decltype(tri)::value;
-      if (lj)
-        hipLaunchKernelGGL((k_lj<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, q, stride, kp, h->list, n, (T)(4.0 * lj[0]), (T)(lj[1] * lj[1]),
-                           (T)(lj[2] * lj[2]), f, Lx, Ly, Lz, status, xy, xz, yz);
-      else
-        hipLaunchKernelGGL((k_lj_typed<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, q, stride, kp, h->list, n, h->ty_types,
-                           static_cast<const T*>(h->lj_par), f, Lx, Ly, Lz, status, xy, xz, yz);
+      if (lj) hipLaunchKernelGGL((k_lj<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, a, lj_scalars<T>(lj), f);
+      else hipLaunchKernelGGL((k_lj_typed<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, a, lj_by_type<T>(h), f);
     };
     if (!h->plan.full) HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
     if (h->plan.tilt) h->plan.full ? launch(std::false_type(), std::true_type()) : launch(std::true_type(), std::true_type());
@@ -218,46 +234,50 @@ int lj_typed_check(nl_handle_t h, double skin) {
   return NL_OK;
 }
 
+// The eight entry points (nl_lj_forces, nl_lj_virial, each _typed and _enqueue): the checks, then launch(...).
+//   the arguments (NL_ERR_ARG, a null handle included);
+//   synchronous: consumer_ready, then the reach -- rc_force within the list's rc, or lj_typed_check;
+//   enqueue (no wait: stream-ordered behind the update, or completed build, whose list it reads): the reach less the skin
+//   (what a list reused within the skin guarantees) first, then consumer_ready; the kernel takes the build's status word.
+template <typename OUT>
+int lj_call(nl_handle_t h, const void* q_dev, int32_t q_stride, const double* lj, OUT* out_dev, void* stream, bool enqueue,
+            int (*launch)(nl_handle_t, const void*, int32_t, const double*, OUT*, hipStream_t, const uint32_t*)) {
+  if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4) || (lj && (!(lj[2] > 0) || !(lj[1] > 0)))) return fail(h, NL_ERR_ARG);
+  const hipStream_t s = (hipStream_t)stream;
+  const auto reach = [&](double skin) -> int {
+    if (!lj) return lj_typed_check(h, skin);
+    return lj[2] <= h->rc - skin ? NL_OK : fail(h, NL_ERR_ARG);  // the list does not reach that far (rc - 0.0 is rc, exactly)
+  };
+  if (enqueue) {
+    if (int rc = reach(h->skin)) return rc;
+    if (int rc = consumer_ready(h, s, true)) return rc;
+  } else {
+    if (int rc = consumer_ready(h, s, false)) return rc;
+    if (int rc = reach(0.0)) return rc;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  return launch(h, q_dev, q_stride, lj, out_dev, s, enqueue ? h->status : nullptr);
+}
+
 }  // namespace
 
 extern "C" {
 
 int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force, void* f_dev,
                  void* stream) {
-  if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4) || !(rc_force > 0) || !(sigma > 0)) return fail(h, NL_ERR_ARG);
-  if (int rc = consumer_ready(h, (hipStream_t)stream, false)) return rc;
-  if (rc_force > h->rc) return fail(h, NL_ERR_ARG);  // the list does not reach that far
-  HIPCHK(h, hipSetDevice(h->device));
   const double lj[3] = {epsilon, sigma, rc_force};
-  return lj_launch(h, q_dev, q_stride, lj, f_dev, (hipStream_t)stream, nullptr);
+  return lj_call(h, q_dev, q_stride, lj, f_dev, stream, false, lj_launch);
 }
-
-// nl_lj_forces without the wait: stream-ordered behind the update (or completed build) whose list it reads.
 int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
                          void* f_dev, void* stream) {
-  if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4) || !(rc_force > 0) || !(sigma > 0)) return fail(h, NL_ERR_ARG);
-  if (!(rc_force <= h->rc - h->skin)) return fail(h, NL_ERR_ARG);  // beyond what a list reused within the skin guarantees
-  if (int rc = consumer_ready(h, (hipStream_t)stream, true)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
   const double lj[3] = {epsilon, sigma, rc_force};
-  return lj_launch(h, q_dev, q_stride, lj, f_dev, (hipStream_t)stream, h->status);
+  return lj_call(h, q_dev, q_stride, lj, f_dev, stream, true, lj_launch);
 }
-
 int nl_lj_forces_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream) {
-  if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
-  if (int rc = consumer_ready(h, (hipStream_t)stream, false)) return rc;
-  if (int rc = lj_typed_check(h, 0.0)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  return lj_launch(h, q_dev, q_stride, nullptr, f_dev, (hipStream_t)stream, nullptr);
+  return lj_call(h, q_dev, q_stride, nullptr, f_dev, stream, false, lj_launch);
 }
-
-// nl_lj_forces_typed without the wait, as nl_lj_forces_enqueue.
 int nl_lj_forces_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream) {
-  if (!h || !q_dev || !f_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
-  if (int rc = lj_typed_check(h, h->skin)) return rc;
-  if (int rc = consumer_ready(h, (hipStream_t)stream, true)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  return lj_launch(h, q_dev, q_stride, nullptr, f_dev, (hipStream_t)stream, h->status);
+  return lj_call(h, q_dev, q_stride, nullptr, f_dev, stream, true, lj_launch);
 }
 
 }  // extern "C"

@@ -231,6 +231,16 @@ int pair_vectors_launch(nl_handle_t h, const void* q_dev, int32_t stride, void* 
   });
 }
 
+// nl_pair_vectors; enqueue: without the wait, stream-ordered behind the update (or completed build) whose list it reads.
+int pair_vectors_call(nl_handle_t h, const void* q_dev, int32_t q_stride, void* out_dev, hipStream_t s, bool enqueue) {
+  if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
+  if (!h->pair_images) return fail(h, NL_ERR_STATE);
+  if (int rc = consumer_ready(h, s, enqueue)) return rc;
+  if (!h->plan.images) return fail(h, NL_ERR_STATE);
+  HIPCHK(h, hipSetDevice(h->device));
+  return pair_vectors_launch(h, q_dev, q_stride, out_dev, s, enqueue ? h->status : nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -270,22 +280,10 @@ int nl_get_pair_images(nl_handle_t h, const int8_t** images_dev, int64_t* nentri
 }
 
 int nl_pair_vectors(nl_handle_t h, const void* q_dev, int32_t q_stride, void* out_dev, void* stream) {
-  if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
-  if (!h->pair_images) return fail(h, NL_ERR_STATE);
-  if (int rc = consumer_ready(h, (hipStream_t)stream, false)) return rc;
-  if (!h->plan.images) return fail(h, NL_ERR_STATE);
-  HIPCHK(h, hipSetDevice(h->device));
-  return pair_vectors_launch(h, q_dev, q_stride, out_dev, (hipStream_t)stream, nullptr);
+  return pair_vectors_call(h, q_dev, q_stride, out_dev, (hipStream_t)stream, false);
 }
-
-// nl_pair_vectors without the wait: stream-ordered behind the update (or completed build) whose list it reads.
 int nl_pair_vectors_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* out_dev, void* stream) {
-  if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4)) return fail(h, NL_ERR_ARG);
-  if (!h->pair_images) return fail(h, NL_ERR_STATE);
-  if (int rc = consumer_ready(h, (hipStream_t)stream, true)) return rc;
-  if (!h->plan.images) return fail(h, NL_ERR_STATE);
-  HIPCHK(h, hipSetDevice(h->device));
-  return pair_vectors_launch(h, q_dev, q_stride, out_dev, (hipStream_t)stream, h->status);
+  return pair_vectors_call(h, q_dev, q_stride, out_dev, (hipStream_t)stream, true);
 }
 
 }  // extern "C"

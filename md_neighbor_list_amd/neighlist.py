@@ -286,17 +286,7 @@ class NeighListGPU:
     def lj_forces_typed(self, q, wait=True, out=None):
         """lj_forces with the parameters of set_lj_type_params, per pair of types (nl_lj_forces_typed); ``wait=False``:
         nl_lj_forces_typed_enqueue (rc_force within cut-off - skin).  Returns ``(n, 4) = {fx, fy, fz, pe_i}``."""
-        n = self._check_q(q, None)
-        if n != self._n:
-            raise ValueError("q must hold the particles the list was built from")
-        f = torch.empty((n, 4), dtype=self.dtype, device=self.device) if out is None else out
-        if f.shape != (n, 4) or f.dtype != self.dtype or not f.is_contiguous():
-            raise TypeError("out must be a contiguous (n, 4) tensor of the list's dtype")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        fn = self._lib.nl_lj_forces_typed if wait else self._lib.nl_lj_forces_typed_enqueue
-        check(fn(self._h, q.data_ptr(), q.shape[1], f.data_ptr(), stream),
-              "nl_lj_forces_typed" if wait else "nl_lj_forces_typed_enqueue")
-        return f
+        return self._lj("nl_lj_forces_typed", q, (), wait, out)
 
     # ------------------------------------------------------------------ pair images
     def set_pair_images(self, on=True):
@@ -500,28 +490,29 @@ class NeighListGPU:
         build.  ``wait=False`` (nl_lj_forces_enqueue): no wait for the build, stream-ordered behind the last update();
         rc_force must then be <= cut-off - skin, and a list whose build failed gives NaN.  ``out``: an (n, 4) tensor
         to write into (graph capture)."""
-        n = self._check_q(q, None)
-        if n != self._n:
-            raise ValueError("q must hold the particles the list was built from")
-        f = torch.empty((n, 4), dtype=self.dtype, device=self.device) if out is None else out
-        if f.shape != (n, 4) or f.dtype != self.dtype or not f.is_contiguous():
-            raise TypeError("out must be a contiguous (n, 4) tensor of the list's dtype")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if rc_force is None:
-            rc_force = self.search_length if wait else self.search_length - self.skin
-        fn = self._lib.nl_lj_forces if wait else self._lib.nl_lj_forces_enqueue
-        check(fn(self._h, q.data_ptr(), q.shape[1], float(epsilon), float(sigma), float(rc_force), f.data_ptr(), stream),
-              "nl_lj_forces" if wait else "nl_lj_forces_enqueue")
-        return f
+        return self._lj("nl_lj_forces", q, (epsilon, sigma, rc_force), wait, out)
 
-    def _virial_out(self, q, out):
+    def _lj(self, name, q, lj, wait, out):
+        """What lj_forces, lj_virial and their typed forms share: the output (``(n, 4)`` of the list's dtype, or 8 float64
+        for a virial), the stream, the pick of ``name`` or ``name``_enqueue and the call.  lj: (epsilon, sigma, rc_force),
+        or () for the typed forms."""
         n = self._check_q(q, None)
         if n != self._n:
             raise ValueError("q must hold the particles the list was built from")
-        w = torch.empty(8, dtype=torch.float64, device=self.device) if out is None else out
-        if w.shape != (8,) or w.dtype != torch.float64 or not w.is_contiguous() or w.device != q.device:
-            raise TypeError("out must be a contiguous float64 tensor of 8 on the list's device")
-        return w, torch.cuda.current_stream(self.device).cuda_stream
+        if "virial" in name:
+            o = torch.empty(8, dtype=torch.float64, device=self.device) if out is None else out
+            if o.shape != (8,) or o.dtype != torch.float64 or not o.is_contiguous() or o.device != q.device:
+                raise TypeError("out must be a contiguous float64 tensor of 8 on the list's device")
+        else:
+            o = torch.empty((n, 4), dtype=self.dtype, device=self.device) if out is None else out
+            if o.shape != (n, 4) or o.dtype != self.dtype or not o.is_contiguous():
+                raise TypeError("out must be a contiguous (n, 4) tensor of the list's dtype")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if lj and lj[2] is None:
+            lj = (lj[0], lj[1], self.search_length if wait else self.search_length - self.skin)
+        name += "" if wait else "_enqueue"
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], *(float(v) for v in lj), o.data_ptr(), stream), name)
+        return o
 
     def lj_virial(self, q, epsilon=1.0, sigma=1.0, rc_force=None, wait=True, out=None):
         """The totals that belong to lj_forces (nl_lj_virial): a float64 device tensor
@@ -532,22 +523,12 @@ class NeighListGPU:
         ``wait``, ``rc_force`` and ``out`` (a float64 tensor of 8) as for lj_forces; with ``wait=False``
         (nl_lj_virial_enqueue) a list whose build failed gives 8 NaN.  The first call allocates scratch: make it before
         a graph capture."""
-        w, stream = self._virial_out(q, out)
-        if rc_force is None:
-            rc_force = self.search_length if wait else self.search_length - self.skin
-        fn = self._lib.nl_lj_virial if wait else self._lib.nl_lj_virial_enqueue
-        check(fn(self._h, q.data_ptr(), q.shape[1], float(epsilon), float(sigma), float(rc_force), w.data_ptr(), stream),
-              "nl_lj_virial" if wait else "nl_lj_virial_enqueue")
-        return w
+        return self._lj("nl_lj_virial", q, (epsilon, sigma, rc_force), wait, out)
 
     def lj_virial_typed(self, q, wait=True, out=None):
         """lj_virial with the parameters of set_lj_type_params, per pair of types (nl_lj_virial_typed); ``wait=False``:
         nl_lj_virial_typed_enqueue."""
-        w, stream = self._virial_out(q, out)
-        fn = self._lib.nl_lj_virial_typed if wait else self._lib.nl_lj_virial_typed_enqueue
-        check(fn(self._h, q.data_ptr(), q.shape[1], w.data_ptr(), stream),
-              "nl_lj_virial_typed" if wait else "nl_lj_virial_typed_enqueue")
-        return w
+        return self._lj("nl_lj_virial_typed", q, (), wait, out)
 
     # ------------------------------------------------------------------ periodic re-sorting (SORT_FREQ)
     def cell_order(self):

@@ -8,7 +8,7 @@ Contract tested (include/nl_hip.h, nl_lj_virial):
   * half and full lists report the same totals; two calls return the same 64 bytes.
 
 c_W = VIR_C = 4 x the largest per-row ratio |emulated row sum - float64 row sum| / (u S_row) that a float32 numpy
-emulation of the kernel's arithmetic reaches (emulate_pairs: the steps of lj_emulate; virial_emulate: the six products
+emulation of the kernel's arithmetic reaches (emulate_pairs, which lj_emulate sums too; virial_emulate: the six products
 and the energy in float32, one rounding each, converted and added in double as the kernel adds them) over the nine
 inputs of EMULATED, both list kinds, three summation orders; test_emulation_gives_c recomputes the maximum.  The totals
 are double sums of such row values, so the per-row bound carries over by the triangle inequality; the factor 4 is section
@@ -170,8 +170,8 @@ def test_reference_is_the_strain_derivative_of_its_energy():
 
 
 def test_emulation_is_lj_emulate():
-    """emulate_pairs restates the steps of tests.util lj_emulate: with one entry per row, where nothing is summed, the
-    two give the same bits on every box form."""
+    """tests.util lj_emulate is emulate_pairs and a row sum: with one entry per row, where nothing is summed, it returns
+    f = {fx, fy, fz, pe / 2} of the pair's values, bit for bit, on every box form."""
     for box, drift, par in (("tilt", True, "typed32"), ("xyz", True, "scalar"), ("open", False, "scalar")):
         box6, mask = LJ_BOXES[box]
         types, _, eps, sig, rcf = _par(par)
@@ -330,6 +330,34 @@ def test_reproducible(box, drift, par, dtype):
         got[full] = a
     assert np.all(np.abs(got[False][:7] - got[True][:7]) <= 2 * VIR_C * lj_unit(dtype) * S)
     assert got[False][7] == got[True][7]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("full", [False, True])
+@pytest.mark.parametrize("box", ["xyz", "tilt"])
+def test_one_type_is_the_scalar_path(box, full, dtype):
+    """The by-type walk with a single type is the scalar walk, bit for bit: on one handle and one list, lj_virial and
+    lj_virial_typed return the same 64 bytes and, after a full build, lj_forces and lj_forces_typed the same forces (the
+    half list's atomics fix no order).  The parameters are not representable in float32, so both paths round them on the
+    host; at rc = 3.6 rows are longer than 64 entries, so the 64-lane loop turns more than once and its last turn is
+    ragged: lanes past the row's end stay in for the pick."""
+    torch = _torch()
+    eps, sig, rc = 0.7, 1.05, RC_LISTS[2]
+    nl = _handle(box, dtype, full, rc)
+    nl.Initialize(N)
+    nl.set_type_cutoffs(np.zeros(N, dtype=np.int32), [[rc]])
+    qd = torch.from_numpy(_input(box, False).astype(dtype)).cuda()
+    nl.MakeNeighList(qd, N)
+    nl.set_lj_type_params([[eps]], [[sig]], [[RCF]])
+    rows = np.diff((nl.full_csr()[0] if full else nl.key_pointer()).cpu().numpy())
+    assert rows.max() > 64 and (rows % 64 != 0).any()
+    w = nl.lj_virial(qd, eps, sig, rc_force=RCF).cpu().numpy()
+    assert np.isfinite(w).all() and w[7] > N
+    assert w.tobytes() == nl.lj_virial_typed(qd).cpu().numpy().tobytes() and len(w.tobytes()) == 64
+    if full:
+        f = nl.lj_forces(qd, eps, sig, rc_force=RCF).cpu().numpy()
+        assert np.isfinite(f).all() and f.tobytes() == nl.lj_forces_typed(qd).cpu().numpy().tobytes()
 
 
 @pytest.mark.gpu

@@ -168,12 +168,12 @@ def check_lj(got, want, S, dtype, c=LJ_C, rows=None):
                             f"|got - want| = {r[i, col]:.4g} u S, allowed {c:g} (worst per column {r.max(axis=0)})")
 
 
-def lj_emulate(q, box6, mask, eps, sig, rcf, T, rng, pairs, types=None):
-    """The arithmetic of lj_pair and lj_image (csrc/nl_consumer.inc) in the position type T with numpy: one rounding per
-    operation, no FMA, over the ordered pairs of `pairs`; every particle's terms are added in a random order, as the half
-    list's atomics and the wave reduction fix none.  Returns f[n, 4] in T."""
+def emulate_pairs(q, box6, mask, eps, sig, rcf, T, pairs, types=None):
+    """lj_image and lj_pair (csrc/nl_consumer.inc) in the position type T with numpy over the ordered pairs (I, J) of
+    `pairs`: one rounding per operation and no FMA beyond the kernel's own, up to the pair's values
+    (dx, dy, dz, fx, fy, fz, pe, in) in T.  What the consumer's kernels do with them: lj_emulate, tests.virial_util
+    virial_emulate."""
     T = np.dtype(T).type
-    n = len(q)
     I, J = pairs[0], pairs[1]
     p = np.asarray(q)[:, :3].astype(T)
     a, b = p[I], -p[J]
@@ -219,7 +219,18 @@ def lj_emulate(q, box6, mask, eps, sig, rcf, T, rng, pairs, types=None):
     ir2 = np.where(inn, sig2 / safe, T(0))
     s6 = ir2 * ir2 * ir2
     fr = np.where(inn, T(6) * eps4 * (s6 + s6 - T(1)) * s6 / safe, T(0))
-    term = np.stack([fr * dx, fr * dy, fr * dz, T(0.5) * (eps4 * (s6 - T(1)) * s6)], axis=1)
+    out = (dx, dy, dz, fr * dx, fr * dy, fr * dz, eps4 * (s6 - T(1)) * s6, inn)
+    assert all(v.dtype == np.dtype(T) for v in out[:7])
+    return out
+
+
+def lj_emulate(q, box6, mask, eps, sig, rcf, T, rng, pairs, types=None):
+    """The row body of k_lj over emulate_pairs' values, f = {fx, fy, fz, pe / 2} summed per particle in T: every particle's
+    terms are added in a random order, as the half list's atomics and the wave reduction fix none.  Returns f[n, 4] in T."""
+    T = np.dtype(T).type
+    n, I = len(q), pairs[0]
+    _, _, _, fx, fy, fz, pe, _ = emulate_pairs(q, box6, mask, eps, sig, rcf, T, pairs, types=types)
+    term = np.stack([fx, fy, fz, T(0.5) * pe], axis=1)
     assert term.dtype == np.dtype(T)
     order = np.lexsort((rng.random(len(I)), I))
     Is, term = I[order], term[order]

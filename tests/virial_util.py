@@ -2,7 +2,7 @@
 arithmetic in the position type, and the bound |got - want| <= VIR_C u S per component."""
 import numpy as np
 
-from tests.util import _lj_par, lj_pairs, lj_unit
+from tests.util import _lj_par, emulate_pairs, lj_pairs, lj_unit  # noqa: F401 (emulate_pairs: for the importers of this module)
 
 # 4 x the largest per-row ratio of test_emulation_gives_c (virial_emulate over EMULATED, both list kinds, three orders)
 VIR_C = 47.6
@@ -72,61 +72,6 @@ def check_virial(got, want, S, dtype, c=VIR_C, count=True):
     assert r[k] <= c, f"{COLS[k]}: |got - want| = {r[k]:.4g} u S, allowed {c:g} (all: {np.round(r, 3)}; got {got}, want {want})"
     if count:
         assert got[7] == want[7], f"n_in: got {got[7]}, want {want[7]}"
-
-
-def emulate_pairs(q, box6, mask, eps, sig, rcf, T, pairs, types=None):
-    """lj_image and lj_pair (csrc/nl_consumer.inc) in the position type T over the ordered pairs (I, J): the steps of
-    tests.util lj_emulate, one rounding per operation and no FMA beyond the kernel's own, up to the pair's values
-    (dx, dy, dz, fx, fy, fz, pe, in) in T.  test_emulation_is_lj_emulate holds the two against each other."""
-    T = np.dtype(T).type
-    I, J = pairs[0], pairs[1]
-    p = np.asarray(q)[:, :3].astype(T)
-    a, b = p[I], -p[J]
-    d = a + b
-    bv = d - a
-    lo = (a - (d - bv)) + (b - bv)
-    dx, dy, dz = d[:, 0].copy(), d[:, 1].copy(), d[:, 2].copy()
-    L = [T(box6[a]) if mask >> a & 1 else T(0) for a in range(3)]
-    xy, xz, yz = (T(v) for v in box6[3:])
-
-    def fnma(k, m, v):
-        return (v.astype(np.longdouble) - k.astype(np.longdouble) * np.longdouble(m)).astype(T)
-
-    def sub_kl(k, m, v, lo):
-        pr = k * m
-        pe = (k.astype(np.longdouble) * np.longdouble(m) - pr.astype(np.longdouble)).astype(T)
-        s = v - pr
-        bv = s - v
-        return s, lo + (((v - (s - bv)) - (pr + bv)) - pe)
-
-    if mask:
-        iL = [T(1) / v if v > 0 else T(0) for v in L]
-        kz = np.rint(dz * iL[2])
-        ky = np.rint((dy - kz * yz) * iL[1])
-        kx = np.rint(((dx - kz * xz) - ky * xy) * iL[0])
-        dz = fnma(kz, L[2], dz)
-        lx, ly = lo[:, 0], lo[:, 1]
-        if xy != 0 or xz != 0 or yz != 0:
-            dy, ly = sub_kl(ky, L[1], dy, ly)
-            dy, ly = sub_kl(kz, yz, dy, ly)
-            dx, lx = sub_kl(kx, L[0], dx, lx)
-            dx, lx = sub_kl(ky, xy, dx, lx)
-            dx, lx = sub_kl(kz, xz, dx, lx)
-        else:
-            dy, dx = fnma(ky, L[1], dy), fnma(kx, L[0], dx)
-        dx, dy, dz = dx + lx, dy + ly, dz + lo[:, 2]
-    types = None if types is None else np.asarray(types, dtype=np.int64)
-    e, s, c = (_lj_par(v, types, I, J) for v in (eps, sig, rcf))
-    eps4, sig2, rcf2 = (4.0 * e).astype(T), (s * s).astype(T), (c * c).astype(T)
-    r2 = dx * dx + dy * dy + dz * dz
-    inn = (r2 < rcf2) & (r2 > 0)
-    safe = np.where(inn, r2, T(1))
-    ir2 = np.where(inn, sig2 / safe, T(0))
-    s6 = ir2 * ir2 * ir2
-    fr = np.where(inn, T(6) * eps4 * (s6 + s6 - T(1)) * s6 / safe, T(0))
-    out = (dx, dy, dz, fr * dx, fr * dy, fr * dz, eps4 * (s6 - T(1)) * s6, inn)
-    assert all(v.dtype == np.dtype(T) for v in out[:7])
-    return out
 
 
 def virial_emulate(n, I, vals, rng):
