@@ -573,6 +573,52 @@ int nl_lj_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, dou
 int nl_lj_virial_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 int nl_lj_virial_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 
+/* The pair-distance histogram of the list, the counts behind a radial distribution function g(r): for everybody
+ * (nl_pair_histogram) or per unordered pair of types (nl_pair_histogram_typed).  The rule:
+ *   - Entries.  The sum runs over the entries (row i, partner j) of the list of the last build: the filtered list where an
+ *     exclusion or type table is set.  After a NL_LIST_HALF build every entry counts, after a NL_LIST_FULL build only the
+ *     entries with j > i: both kinds count every stored pair once, in the row of the smaller id, and a half and a full
+ *     build of the same input give the same counters, bit for bit.
+ *   - Distance.  d = r_i - r_j at the image of nl_lj_forces (lj_image: folded on the periodic axes of the build's mask in z,
+ *     y, x order with the tilts; positions up to one box length outside the box).  r2 = (dx dx + dy dy) + dz dz in the
+ *     position type T, without FMA.
+ *   - Bins, uniform in r.  In double e_k = (k r_max) / nbins for k = 0 .. nbins, and E_k is the largest T <= e_k e_k (the
+ *     rounding of the builds' rc^2 and of the type table's thresholds); E_0 = 0.  An entry falls into bin b iff
+ *     E_b <= r2 < E_{b+1}.  r2 >= E_nbins is counted nowhere, and neither is a NaN r2 (the call returns all the same).
+ *     A coincident pair (r2 == 0) falls into bin 0 -- unlike the Lennard-Jones calls, whose pair function leaves r2 == 0 out.
+ *   - Output.  hist_dev: nslots x nbins uint64_t on the device, row-major, for both position types.  The call ADDS to it:
+ *     the caller zeroes it and owns it, so many frames accumulate.  Untyped: nslots = 1.  Typed: nslots = ntypes (ntypes +
+ *     1) / 2 and an entry goes to slot(a, b) = a (2 ntypes - a + 1) / 2 + (b - a), a = min(t_i, t_j), b = max(t_i, t_j),
+ *     the types those of nl_set_type_cutoffs.  No Lennard-Jones parameters are needed.
+ *   - Reach.  r_max > 0 and finite, 1 <= nbins <= NL_HIST_MAX_BINS, else NL_ERR_ARG.  Untyped: r_max <= rc, and with a
+ *     type table r_max <= min_ab rc_ab (a table with some rc_ab = 0 therefore refuses the untyped call: NL_ERR_ARG).  Typed:
+ *     NL_ERR_STATE without a type table; r_max <= rc_ab for every pair of types with rc_ab > 0; a pair with rc_ab = 0 has
+ *     no entries and its slot stays as it was.  The enqueue variants: the same limits less the skin, as
+ *     nl_lj_forces_enqueue.
+ *   - Ordering and state: those of nl_lj_forces and nl_lj_forces_enqueue, checks in the same order; slab and distributed
+ *     builds are NL_ERR_STATE; n == 0 adds nothing.  Where an enqueue variant finds a non-zero status word it adds
+ *     nothing; the error itself surfaces at the next nl_synchronize.
+ *   - Capture.  The enqueue variants copy nothing from the host and no call ever allocates (every block computes the
+ *     edges itself, into LDS): they can be captured from the first call on.
+ *   - Exact and reproducible.  Integer counters only, 64 bits wide in LDS and in hist_dev: none can wrap for any list the
+ *     library can build, 64-bit offsets included.  Two calls on the same list and positions add the same values.
+ *   - One wave per row over a grid of at most 2048 blocks of 4 waves.  Where nslots x nbins <= NL_HIST_LDS_COUNTERS a block
+ *     counts in LDS and adds its non-zero counters to hist_dev at its end; a larger histogram is added to hist_dev entry
+ *     by entry.  Both give the same counters.
+ * Tested contract (tests/test_pair_histogram.py): equal, bin by bin, to an O(N^2) float64 count that
+ * uses no list wherever no pair lies within 2^-17 (fp32; 2^-46 fp64; relative, r^2) of an edge; elsewhere the cumulative
+ * counts are bracketed by the pairs surely below each edge and those within its band. */
+#define NL_HIST_MAX_BINS 4096
+#define NL_HIST_LDS_COUNTERS 4096
+int nl_pair_histogram(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, int32_t nbins, uint64_t* hist_dev,
+                      void* stream);
+int nl_pair_histogram_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, int32_t nbins,
+                              uint64_t* hist_dev, void* stream);
+int nl_pair_histogram_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, int32_t nbins, uint64_t* hist_dev,
+                            void* stream);
+int nl_pair_histogram_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, int32_t nbins,
+                                    uint64_t* hist_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------- introspection */
 
 int nl_get_mesh(nl_handle_t h, int32_t mesh[3], int64_t* ncell);

@@ -70,6 +70,10 @@ PROTOTYPES = {
     "nl_lj_virial_enqueue": (C.c_int, [_P, _P, _I32, _D, _D, _D, _P, _P]),
     "nl_lj_virial_typed": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_lj_virial_typed_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_pair_histogram": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
+    "nl_pair_histogram_enqueue": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
+    "nl_pair_histogram_typed": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
+    "nl_pair_histogram_typed_enqueue": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_set_pair_images": (C.c_int, [_P, C.c_int]),
     "nl_get_pair_images": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64)]),
     "nl_pair_vectors": (C.c_int, [_P, _P, _I32, _P, _P]),

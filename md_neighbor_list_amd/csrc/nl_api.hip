@@ -1952,3 +1952,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_types.inc"
 #include "nl_images.inc"
 #include "nl_virial.inc"
+#include "nl_histogram.inc"

@@ -530,6 +530,61 @@ class NeighListGPU:
         nl_lj_virial_typed_enqueue."""
         return self._lj("nl_lj_virial_typed", q, (), wait, out)
 
+    def _ntypes(self):
+        """ntypes of the handle's type table (nl_get_types; NL_ERR_STATE without one)."""
+        ptr, n, nt = C.c_void_p(), C.c_int32(), C.c_int32()
+        check(self._lib.nl_get_types(self._h, C.byref(ptr), C.byref(n), C.byref(nt)), "nl_get_types")
+        return int(nt.value)
+
+    def pair_histogram(self, q, r_max, nbins, typed=False, wait=True, out=None):
+        """Pair-distance histogram of the list of the last build (nl_pair_histogram): every stored pair once, half or
+        full list, in ``nbins`` bins uniform in r up to ``r_max`` (within the list's cut-offs; less the skin with
+        ``wait=False``, nl_pair_histogram_enqueue).  Returns a contiguous int64 device tensor ``(nbins,)``, or with
+        ``typed`` (nl_pair_histogram_typed) ``(ntypes (ntypes + 1) / 2, nbins)`` with the row ``rdf.slot(a, b, ntypes)`` per
+        pair of types of set_type_cutoffs.  New and zeroed when ``out`` is None; otherwise the counts are added to ``out``,
+        so frames accumulate.  Exact integer counts, the same for both list kinds; allocates nothing: it can be captured."""
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        nbins = int(nbins)
+        if typed:
+            nt = self._ntypes()
+            shape = (nt * (nt + 1) // 2, nbins)
+        else:
+            shape = (nbins,)
+        o = torch.zeros(shape, dtype=torch.int64, device=self.device) if out is None else out
+        if tuple(o.shape) != shape or o.dtype != torch.int64 or not o.is_contiguous() or o.device != q.device:
+            raise TypeError(f"out must be a contiguous int64 tensor of shape {shape} on the list's device")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        name = "nl_pair_histogram" + ("_typed" if typed else "") + ("" if wait else "_enqueue")
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], float(r_max), nbins, o.data_ptr(), stream), name)
+        return o
+
+    def rdf(self, hist, r_max, frames=1, types=None):
+        """``(r_mid, g)`` from a histogram of pair_histogram (md_neighbor_list_amd.rdf.rdf) with the volume of the box and
+        the particle counts of the last build filled in.  ``hist`` ``(nbins,)``: g(r) of all particles.  ``hist``
+        ``(nslots, nbins)`` and ``types=(a, b)``: g_ab(r), the counts of a and b taken from the type table.  Raises
+        ValueError unless all three axes are periodic (an open axis has no bulk density to normalise by)."""
+        import numpy as np
+
+        from . import rdf as _rdf
+
+        if self.periodic_mask() != 7:
+            raise ValueError("rdf() needs a box periodic on all three axes")
+        Lx, Ly, Lz = self.box[:3]
+        h = hist.detach().cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
+        if types is None:
+            if h.ndim != 1:
+                raise ValueError("a typed histogram needs types=(a, b)")
+            return _rdf.rdf(h, r_max, Lx * Ly * Lz, self._n, frames=frames)
+        a, b = (int(t) for t in types)
+        nt = self._ntypes()
+        if h.ndim != 2 or h.shape[0] != _rdf.nslots(nt):
+            raise ValueError(f"types=(a, b) picks a row of a typed histogram of {_rdf.nslots(nt)} rows")
+        counts = torch.bincount(self.types().to(torch.int64), minlength=nt).cpu()
+        return _rdf.rdf(h[_rdf.slot(a, b, nt)], r_max, Lx * Ly * Lz, int(counts[a]), None if a == b else int(counts[b]),
+                        frames=frames)
+
     # ------------------------------------------------------------------ periodic re-sorting (SORT_FREQ)
     def cell_order(self):
         """order[s] = input index of the particle at cell-ordered slot s of the last build (nl_get_cell_order; the
