@@ -217,6 +217,28 @@ int nl_make_list_slab_begin(nl_handle_t h, const void* q_dev, int32_t q_stride, 
                             int32_t n, int32_t n_ghost_lo, int32_t z_lo, int32_t z_hi, void* stream);
 int nl_make_list_slab_finish(nl_handle_t h, void* stream, int sync);
 
+/* Local-index slab lists, for the consumers below.  Off by default: nothing above changes.
+ * While on:
+ *   - nl_make_list_slab and nl_make_list_slab_begin take gid_dev == NULL only (a gid array or NL_GID_IN_W: NL_ERR_ARG).
+ *     The list is exactly what such a build has always produced: its ids are rows of q_dev, the n_rows owned particles
+ *     first and the ghosts behind them, the local-index list of LAMMPS and HOOMD.  Half: row r holds the rows j > r within
+ *     the cut-off, so a pair of an owned particle and a ghost is in the owned row on BOTH ranks that see it.  Full: every
+ *     owned row holds all its partners, ghosts included.
+ *   - nl_lj_forces, nl_lj_virial, nl_pair_histogram and their _enqueue variants accept the list of a slab build that was
+ *     made while the switch was on.  The rows are the n_rows owned particles, q_dev holds all n positions of the build, and
+ *     partner j is a ghost iff j >= n_rows.  Each family states below what a rank computes; summed over the ranks of a
+ *     decomposition the results are those of a whole build of the global box.
+ *   - nl_make_list_distributed is NL_ERR_STATE: its lists hold global ids and its ghost counts live on the device.
+ *   - Whole builds (nl_make_list, nl_update_list) and their consumers are unaffected.
+ * Everything else stays refused by the consumers (NL_ERR_STATE): a slab build made with the switch off, caller ids,
+ * distributed builds; a type table, an input-row exclusion table and nl_set_pair_images refuse slab builds as before, so
+ * the _typed variants are not reachable on a slab.  A global exclusion table (nl_set_exclusions_global) applies, its ids
+ * being the rows of q_dev.
+ * Synchronous, as the other setters: finishes a pending build; a changed value drops the list (the next nl_update_list
+ * builds); the same value again changes nothing; allocates nothing. */
+int nl_set_local_ids(nl_handle_t h, int on);
+int nl_get_local_ids(nl_handle_t h, int* on);
+
 /* ------------------------------------------------------------------------------- the decomposed build, whole */
 
 /* The domain-decomposed build with its halo exchange inside the library (no reference
@@ -518,7 +540,12 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream);
  * pairs further than 64 ulp (in r) from it.  After a NL_LIST_FULL build every row gathers its partners and
  * writes its force once; after a NL_LIST_HALF build every pair is evaluated once and the reaction is added to the
  * partner with floating-point atomics (f_dev is zeroed first).  Enqueued on `stream` (NULL = the null stream);
- * waits for the build first. */
+ * waits for the build first.
+ * On a local-index slab list (nl_set_local_ids): f_dev is n_rows x 4, q_dev holds the n positions of the build.  Per entry
+ * (row i owned, partner j; j is a ghost iff j >= n_rows): a full list is read as ever; in a half list an owned partner
+ * receives the reaction, a ghost partner receives nothing -- its owner evaluates the same pair in its own row, so there are
+ * no atomics to ghost rows and no reverse communication; pe_i takes half the pair energy either way.  Every owned
+ * particle's {fx, fy, fz, pe_i} is what a whole build of the global box gives that particle; the pe_i of all ranks sum to U. */
 int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
                  void* f_dev, void* stream);
 /* nl_lj_forces without the wait: stream-ordered behind the last nl_update_list, which must have been enqueued on the same
@@ -552,7 +579,8 @@ int nl_lj_forces_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_strid
  *     report W_ab = sum over pairs d_a F_b, U = sum over pairs u(r), n_in = the number of pairs within rc_force.
  *   - Sign: d = r_i - r_j and F the force on i, so repulsion gives positive diagonal terms (the LAMMPS convention).
  *   - Ordering, the state required, the rc_force <= rc test (<= rc - skin for the enqueue variants) and the typed
- *     variants' conditions are exactly those of the four force calls; slab and distributed builds: NL_ERR_STATE.
+ *     variants' conditions are exactly those of the four force calls; slab and distributed builds: NL_ERR_STATE (but for a
+ *     local-index slab list, below).
  *   - Where the enqueue variants find a non-zero status word all 8 values are NaN; the error itself surfaces at the next
  *     nl_synchronize.  n == 0 gives 8 zeros.
  *   - Reproducible: no floating-point atomics anywhere, every sum has a fixed order.  Two calls on the same list and
@@ -563,6 +591,11 @@ int nl_lj_forces_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_strid
  *     allocates that buffer: on a stream that is being captured it returns NL_ERR_STATE (call once before the capture).
  *     Calls on one handle share it, so they must be ordered against each other, as everything else on a handle.
  *   - The enqueue variants copy nothing from the host and can be captured, as nl_lj_forces_enqueue.
+ *   - On a local-index slab list (nl_set_local_ids) the rows are the n_rows owned particles and every entry (row i owned,
+ *     partner j; j is a ghost iff j >= n_rows) has a weight, applied in double: after a NL_LIST_FULL build 1/2 for every
+ *     entry, as above; after a NL_LIST_HALF build 1 for an owned partner and 1/2 for a ghost partner, whose owner stores
+ *     the pair too.  The weights are powers of two (exact), n_in may be a half-integer on a rank, and the 8 doubles summed
+ *     over the ranks of a decomposition are W, U and n_in of the global box.  Reproducible as above.
  * Tested contract (tests/test_lj_virial.py): every component within c_W u S of an O(N^2) float64 sum,
  * S that component's uncancelled sum; n_in exact where no pair lies within 2^-17 (relative, r^2) of a cut-off. */
 #define NL_VIRIAL_BLOCKS 2048
@@ -596,7 +629,7 @@ int nl_lj_virial_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_strid
  *     no entries and its slot stays as it was.  The enqueue variants: the same limits less the skin, as
  *     nl_lj_forces_enqueue.
  *   - Ordering and state: those of nl_lj_forces and nl_lj_forces_enqueue, checks in the same order; slab and distributed
- *     builds are NL_ERR_STATE; n == 0 adds nothing.  Where an enqueue variant finds a non-zero status word it adds
+ *     builds are NL_ERR_STATE (but for a local-index slab list, below); n == 0 adds nothing.  Where an enqueue variant finds a non-zero status word it adds
  *     nothing; the error itself surfaces at the next nl_synchronize.
  *   - Capture.  The enqueue variants copy nothing from the host and no call ever allocates (every block computes the
  *     edges itself, into LDS): they can be captured from the first call on.
@@ -605,6 +638,13 @@ int nl_lj_virial_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_strid
  *   - One wave per row over a grid of at most 2048 blocks of 4 waves.  Where nslots x nbins <= NL_HIST_LDS_COUNTERS a block
  *     counts in LDS and adds its non-zero counters to hist_dev at its end; a larger histogram is added to hist_dev entry
  *     by entry.  Both give the same counters.
+ *   - On a local-index slab list (nl_set_local_ids) the rows are the n_rows owned particles and the counters keep their
+ *     unit of whole pairs.  Per entry (row i owned, partner j; j is a ghost iff j >= n_rows): an owned partner counts as
+ *     above (half: every entry; full: j > i); a ghost partner counts iff dz < 0, or dz == 0 and z_i < z_j as raw
+ *     coordinates, d = r_i - r_j the image above.  That image is exactly antisymmetric under the swap of the two particles
+ *     and r2 is symmetric, so exactly one of the two ranks that store a crossing pair counts it, in the same bin: the
+ *     counters of the ranks add up, bit for bit, to those of the whole-box call, and a half and a full slab build give the
+ *     same counters.
  * Tested contract (tests/test_pair_histogram.py): equal, bin by bin, to an O(N^2) float64 count that
  * uses no list wherever no pair lies within 2^-17 (fp32; 2^-46 fp64; relative, r^2) of an edge; elsewhere the cumulative
  * counts are bracketed by the pairs surely below each edge and those within its band. */

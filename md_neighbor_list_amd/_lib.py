@@ -32,6 +32,8 @@ PROTOTYPES = {
     "nl_set_box": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "nl_get_box": (C.c_int, [_P, C.POINTER(C.c_double * 6)]),
     "nl_set_graph": (C.c_int, [_P, C.c_int]),
+    "nl_set_local_ids": (C.c_int, [_P, C.c_int]),
+    "nl_get_local_ids": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "nl_destroy": (C.c_int, [_P]),
     "nl_make_list": (C.c_int, [_P, _P, _I32, _I32, _P, C.c_int]),
     "nl_make_list_slab": (C.c_int, [_P, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, C.c_int]),

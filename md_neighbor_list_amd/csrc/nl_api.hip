@@ -135,6 +135,7 @@ struct nl_handle_s {
   bool capacity_user = false;
   int list_kind = NL_LIST_HALF;
   int pbc = 0;               // axes of the minimum image, bit d = axis d (nl_set_periodic_axes); 0 = the open box
+  bool local_ids = false;    // nl_set_local_ids: slab builds take no caller ids, and the consumers read their lists
 
   // device buffers (DevBuf: each owns its allocation and knows the bytes and items it holds; freed with the handle)
   DevBuf<int32_t> rank;
@@ -291,7 +292,9 @@ template <typename F> int dispatch_t_off(nl_handle_t h, F&& f) {
 // What every consumer of the list needs first (nl_lj_forces*, nl_pair_vectors*).  Synchronous: the list must be complete
 // (and its build must have succeeded).  enqueue: stream-ordered behind the build instead -- a build, or one the host has
 // not seen fail; a pending one must be an update's (a plain asynchronous build may still need finish() to complete its
-// list) and enqueued on this stream.  Either way the list's ids must index q.
+// list) and enqueued on this stream.  Either way the list's ids must index q: a whole build's, or those of a slab build
+// made under nl_set_local_ids (rows of the caller's buffer, ghosts behind the owned rows).  The switch drops the list when it
+// changes, so a list that exists was built under the value the handle holds.
 int consumer_ready(nl_handle_t h, hipStream_t s, bool enqueue) {
   if (enqueue) {
     if (!h->pending && !h->built) return fail(h, NL_ERR_STATE);
@@ -299,7 +302,7 @@ int consumer_ready(nl_handle_t h, hipStream_t s, bool enqueue) {
   } else if (int rc = nl_synchronize(h)) {
     return rc;
   }
-  if (h->args.slab || h->n_rows != h->n) return fail(h, NL_ERR_STATE);
+  if ((h->args.slab || h->n_rows != h->n) && (!h->local_ids || h->args.gid || h->args.dyn)) return fail(h, NL_ERR_STATE);
   return NL_OK;
 }
 
@@ -1529,6 +1532,25 @@ int nl_set_list_kind(nl_handle_t h, int kind) {
   return NL_OK;
 }
 
+int nl_set_local_ids(nl_handle_t h, int on) {
+  if (!h) return NL_ERR_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->pending) (void)finish(h, false);
+  h->upd_valid = false;
+  if ((on != 0) != h->local_ids) {
+    h->local_ids = on != 0;
+    h->built = false;
+    h->t_valid = false;
+  }
+  return NL_OK;
+}
+
+int nl_get_local_ids(nl_handle_t h, int* on) {
+  if (!h || !on) return fail(h, NL_ERR_ARG);
+  *on = h->local_ids ? 1 : 0;
+  return NL_OK;
+}
+
 int nl_set_graph(nl_handle_t h, int on) {
   if (!h) return NL_ERR_ARG;
   h->use_graph = on != 0;
@@ -1573,6 +1595,7 @@ int make_list_slab_part(nl_handle_t h, BuildArgs a, int32_t z_hi, void* stream, 
     return fail(h, NL_ERR_ARG);
   if (a.n_ghost_lo < 0 || a.n_ghost_lo > n - n_rows) return fail(h, NL_ERR_ARG);
   if (a.gid == NL_GID_IN_W && a.stride != 4) return fail(h, NL_ERR_ARG);
+  if (h->local_ids && a.gid) return fail(h, NL_ERR_ARG);  // nl_set_local_ids: the ids are the rows of q
   const int32_t mz = h->m[2];
   if (z_lo < 0 || z_hi > mz || z_lo >= z_hi) return fail(h, NL_ERR_ARG);
   const int32_t owned = z_hi - z_lo;

@@ -98,14 +98,23 @@ template <typename T, typename OFF> struct LjArgs {
   int32_t stride;
   const OFF* __restrict__ kp;
   const int32_t* __restrict__ list;
-  int32_t n;
+  int32_t n;  // rows of the list: the build's n_rows (a local-id slab build: ids from n on are ghosts, LjPartner)
   const uint32_t* __restrict__ status;
   T Lx, Ly, Lz, xy, xz, yz;
 };
 
-// The pairs of one row, a wave per row: on_pair(j, dx, dy, dz, fx, fy, fz, pe, in) for every entry of the row, with the
-// separation at the image the list found the pair at (minimum-image list, nl_set_periodic_axes: folded on the periodic axes,
-// L > 0) and the values of lj_pair.
+// What a row knows of an entry's partner besides its position (DESIGN.md section 8n).  ghost: j is no row of this list -- a
+// ghost of a local-id slab build (nl_set_local_ids: owned rows first, j >= n_rows), whose owner stores the same pair in its own
+// row; never set after a whole build, whose every id is a row.  first: of the two ranks that store an owned-ghost pair, this
+// is the one that counts it -- dz < 0, or dz == 0 and z_i < z_j as given.  lj_image is odd under the swap of the two particles
+// (two_diff, rint and fma are), so exactly one of the two rows says so.
+struct LjPartner {
+  bool ghost, first;
+};
+
+// The pairs of one row, a wave per row: on_pair(j, partner, dx, dy, dz, fx, fy, fz, pe, in) for every entry of the row, with
+// the separation at the image the list found the pair at (minimum-image list, nl_set_periodic_axes: folded on the periodic
+// axes, L > 0), the values of lj_pair and what LjPartner says of j.  a.n: the rows of the list (n_rows of the build).
 // By type: lane t < ntypes holds eps4, sig2 and rcf2 of (t_row, t), an entry picks them by its partner's type with ds_bpermute.
 template <typename T, typename OFF, bool TRI, typename PAR, typename F>
 __device__ __forceinline__ void lj_row_pairs(const LjArgs<T, OFF>& a, const PAR& p, int32_t row, int32_t lane, F&& on_pair) {
@@ -135,12 +144,13 @@ __device__ __forceinline__ void lj_row_pairs(const LjArgs<T, OFF>& a, const PAR&
     bool in;
     lj_image<T, TRI>(xi, yi, zi, xj, yj, zj, dx, dy, dz, a.Lx, a.Ly, a.Lz, a.xy, a.xz, a.yz);
     lj_pair<T>(dx, dy, dz, e4, s2, c2, fx, fy, fz, pe, in);
-    on_pair(j, dx, dy, dz, fx, fy, fz, pe, in);
+    const LjPartner w = {j >= a.n, dz < (T)0 || (dz == (T)0 && zi < zj)};
+    on_pair(j, w, dx, dy, dz, fx, fy, fz, pe, in);
   }
 }
 
-// one wave per row; f = {fx, fy, fz, pe_i} with pe_i = half of the pair energies of particle i.  A list whose build failed
-// (status) gives NaN forces.
+// one wave per row; f = {fx, fy, fz, pe_i} of the list's rows, pe_i = half of the pair energies of particle i.  A list whose
+// build failed (status) gives NaN forces.
 template <typename T, bool HALF, typename OFF, bool TRI, typename PAR>
 __device__ __forceinline__ void lj_row(const LjArgs<T, OFF>& a, const PAR& p, T* __restrict__ f) {
   const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
@@ -153,9 +163,9 @@ __device__ __forceinline__ void lj_row(const LjArgs<T, OFF>& a, const PAR& p, T*
     return;
   }
   T ax = 0, ay = 0, az = 0, ae = 0;
-  lj_row_pairs<T, OFF, TRI>(a, p, row, lane, [&](int32_t j, T, T, T, T fx, T fy, T fz, T pe, bool in) {
+  lj_row_pairs<T, OFF, TRI>(a, p, row, lane, [&](int32_t j, LjPartner w, T, T, T, T fx, T fy, T fz, T pe, bool in) {
     ax += fx, ay += fy, az += fz, ae += (T)0.5 * pe;
-    if (HALF && in) {  // Newton's third law: the partner's share
+    if (HALF && in && !w.ghost) {  // Newton's third law: the partner's share (a ghost gets its own from its owner's row)
       atomicAdd(&f[(size_t)j * 4 + 0], -fx);
       atomicAdd(&f[(size_t)j * 4 + 1], -fy);
       atomicAdd(&f[(size_t)j * 4 + 2], -fz);
@@ -184,6 +194,13 @@ __global__ void __launch_bounds__(256) k_lj_typed(LjArgs<T, OFF> a, LjByType<T> 
   lj_row<T, HALF, OFF, TRI>(a, p, f);
 }
 
+// Zeroes the forces in front of a half list's atomics.  A kernel, not hipMemsetAsync: captured into a graph behind other work
+// on the buffer (torch.cuda.graph; a fill of f in front of the replay), the memset node zeroed only some of every four words
+// from the second replay on -- with the parent's library as with this one, eagerly never -- and the forces kept what was there.
+template <typename T> __global__ void __launch_bounds__(256) k_lj_zero(T* __restrict__ f, size_t count) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) f[i] = (T)0;
+}
+
 // The arguments of a launch over the handle's list (lj_launch, virial_launch).  Box lengths for the minimum image on the
 // axes of the list's build; 0 = open axis (the reference's distances, neighlist_cpu.hpp:219-223).  The box and the mask
 // are the build's (BuildPlan::box, BuildPlan::pbc), not what nl_set_box or nl_set_periodic_axes may have set since; the
@@ -192,7 +209,7 @@ __global__ void __launch_bounds__(256) k_lj_typed(LjArgs<T, OFF> a, LjByType<T> 
 template <typename T, typename OFF> LjArgs<T, OFF> lj_args(nl_handle_t h, const void* q_dev, int32_t stride, const uint32_t* status) {
   const Box& b = h->plan.box;
   const int pbc = h->plan.pbc;
-  return {static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer), h->list, h->n, status,
+  return {static_cast<const T*>(q_dev), stride, static_cast<const OFF*>(h->key_pointer), h->list, h->n_rows, status,
           (pbc & 1) ? (T)b.L[0] : (T)0, (pbc & 2) ? (T)b.L[1] : (T)0, (pbc & 4) ? (T)b.L[2] : (T)0, (T)b.xy, (T)b.xz, (T)b.yz};
 }
 template <typename T> LjScalars<T> lj_scalars(const double* lj) { return {(T)(4.0 * lj[0]), (T)(lj[1] * lj[1]), (T)(lj[2] * lj[2])}; }
@@ -200,7 +217,7 @@ template <typename T> LjByType<T> lj_by_type(nl_handle_t h) { return {h->ty_type
 
 // lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables.
 int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, void* f_dev, hipStream_t s, const uint32_t* status) {
-  const int32_t n = h->n;
+  const int32_t n = h->n_rows;
   if (n == 0) return NL_OK;
   return dispatch_t_off(h, [&](auto t, auto off) -> int {
     using T = decltype(t);
@@ -213,7 +230,10 @@ int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj
       if (lj) hipLaunchKernelGGL((k_lj<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, a, lj_scalars<T>(lj), f);
       else hipLaunchKernelGGL((k_lj_typed<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, a, lj_by_type<T>(h), f);
     };
-    if (!h->plan.full) HIPCHK(h, hipMemsetAsync(f_dev, 0, sizeof(T) * 4 * (size_t)n, s));
+    if (!h->plan.full) {
+      const size_t count = 4 * (size_t)n;
+      hipLaunchKernelGGL((k_lj_zero<T>), dim3((unsigned)std::min<size_t>((count + 255) / 256, 8192)), dim3(256), 0, s, f, count);
+    }
     if (h->plan.tilt) h->plan.full ? launch(std::false_type(), std::true_type()) : launch(std::true_type(), std::true_type());
     else h->plan.full ? launch(std::false_type(), std::false_type()) : launch(std::true_type(), std::false_type());
     HIPCHK(h, hipGetLastError());

@@ -377,6 +377,7 @@ extern "C" {
 
 int nl_make_list_distributed(nl_handle_t h, nl_comm_t c, void* q_dev, int32_t q_capacity, int32_t n_owned, void* stream, int sync) {
   if (!h || !c) return NL_ERR_ARG;
+  if (h->local_ids) return fail(h, NL_ERR_STATE);  // (nl_set_local_ids: these lists hold global ids, their ghost counts live on the device)
   if (filter_rows_only(h)) return fail(h, NL_ERR_STATE);  // (nl_set_exclusions, nl_set_type_cutoffs: whole single-device builds only)
   if (box_changed(h)) return fail(h, NL_ERR_STATE);    // (nl_set_box: the layers are those of nl_create's box)
   if (h->pair_images) return fail(h, NL_ERR_STATE);    // (nl_set_pair_images: whole single-device builds only)

@@ -65,8 +65,10 @@ __device__ __forceinline__ void pair_hist_rows(const LjArgs<T, OFF>& a, const Hi
   for (int32_t row = (int32_t)blockIdx.x * 4 + wave; live && row < a.n; row += (int32_t)gridDim.x * 4) {
     int32_t ti = 0;
     if constexpr (TYPED) ti = min(g.types[row] & (NL_MAX_TYPES - 1), g.ntypes - 1);  // (k_type_check: types < ntypes; the min keeps the slot inside hist whatever the table holds)
-    lj_row_pairs<T, OFF, TRI>(a, none, row, lane, [&](int32_t j, T dx, T dy, T dz, T, T, T, T, bool) {
-      if (g.full && j <= row) return;  // a full list stores the pair twice: counted in the row of the smaller id
+    lj_row_pairs<T, OFF, TRI>(a, none, row, lane, [&](int32_t j, LjPartner w, T dx, T dy, T dz, T, T, T, T, bool) {
+      // a pair stored twice counts once: a full list's in the row of the smaller id, one that crosses a cut of a local-id
+      // slab build (both ranks store it, half or full) on the rank LjPartner::first names
+      if (w.ghost ? !w.first : (g.full && j <= row)) return;
       const T r2 = (dx * dx + dy * dy) + dz * dz;
       if (!(r2 < top)) return;  // beyond r_max, or NaN
       int32_t b = min((int32_t)(sqrtf((float)r2) * scale), nbins - 1);
@@ -102,7 +104,7 @@ __global__ void __launch_bounds__(STAGE_THREADS) k_pair_hist_typed(LjArgs<T, OFF
 
 int hist_launch(nl_handle_t h, const void* q_dev, int32_t stride, double r_max, int32_t nbins, bool typed, uint64_t* hist_dev,
                 hipStream_t s, const uint32_t* status) {
-  const int32_t n = h->n;
+  const int32_t n = h->n_rows;
   if (n == 0) return NL_OK;
   const int32_t nt = typed ? h->ty_ntypes : 1;
   const int64_t ncnt = (int64_t)(nt * (nt + 1) / 2) * nbins;

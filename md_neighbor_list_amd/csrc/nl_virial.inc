@@ -19,20 +19,25 @@ static_assert(VIR_BLOCKS <= 2048 && STAGE_THREADS == 4 * WAVE, "vir_part holds a
 // One wave per row (lj_row_pairs of nl_consumer.inc), the rows dealt to the waves of the grid in turn; every lane keeps its
 // 8 sums in double across all its rows.  A term is computed in T (one rounding each: the build has no contraction) and
 // converted, which is exact.
+// ghost_w: the weight of an entry whose partner is a ghost (LjPartner of nl_consumer.inc; a local-id slab build), against 1 for
+// every other entry: 1/2 after a half build, where the partner's owner stores the pair too, 1 after a full one, whose every
+// entry is halved by k_virial_reduce.  The weight goes into the sum's fma: w t is exact (a power of two), so fma(1, t, acc) is
+// acc + t, bit for bit what a whole build has always summed.
 // A failed list (status, the enqueue variants) is not read: the partials are zero and k_virial_reduce writes the NaN.
 template <typename T, typename OFF, bool TRI, typename PAR>
-__device__ __forceinline__ void lj_virial_rows(const LjArgs<T, OFF>& a, const PAR& p, double* __restrict__ part) {
+__device__ __forceinline__ void lj_virial_rows(const LjArgs<T, OFF>& a, const PAR& p, double ghost_w, double* __restrict__ part) {
   __shared__ double red[4][VIR_OUT];
   const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double acc[VIR_OUT] = {0, 0, 0, 0, 0, 0, 0, 0};
   const bool live = !(a.status && *a.status != 0u);  // (uniform over the launch)
   for (int32_t row = (int32_t)blockIdx.x * 4 + wave; live && row < a.n; row += (int32_t)gridDim.x * 4) {
-    lj_row_pairs<T, OFF, TRI>(a, p, row, lane, [&](int32_t, T dx, T dy, T dz, T fx, T fy, T fz, T pe, bool in) {
+    lj_row_pairs<T, OFF, TRI>(a, p, row, lane, [&](int32_t, LjPartner w, T dx, T dy, T dz, T fx, T fy, T fz, T pe, bool in) {
       const T wxx = fx * dx, wyy = fy * dy, wzz = fz * dz, wxy = fx * dy, wxz = fx * dz, wyz = fy * dz;
-      acc[0] += (double)wxx, acc[1] += (double)wyy, acc[2] += (double)wzz;
-      acc[3] += (double)wxy, acc[4] += (double)wxz, acc[5] += (double)wyz;
-      acc[6] += (double)pe;  // (+-0 outside rc_force, as the forces)
-      acc[7] += in ? 1.0 : 0.0;
+      const double c = w.ghost ? ghost_w : 1.0;
+      acc[0] = fma(c, (double)wxx, acc[0]), acc[1] = fma(c, (double)wyy, acc[1]), acc[2] = fma(c, (double)wzz, acc[2]);
+      acc[3] = fma(c, (double)wxy, acc[3]), acc[4] = fma(c, (double)wxz, acc[4]), acc[5] = fma(c, (double)wyz, acc[5]);
+      acc[6] = fma(c, (double)pe, acc[6]);  // (+-0 outside rc_force, as the forces)
+      acc[7] += in ? c : 0.0;
     });
   }
 #pragma unroll
@@ -49,12 +54,12 @@ __device__ __forceinline__ void lj_virial_rows(const LjArgs<T, OFF>& a, const PA
 }
 
 template <typename T, typename OFF, bool TRI>
-__global__ void __launch_bounds__(STAGE_THREADS) k_lj_virial(LjArgs<T, OFF> a, LjScalars<T> p, double* __restrict__ part) {
-  lj_virial_rows<T, OFF, TRI>(a, p, part);
+__global__ void __launch_bounds__(STAGE_THREADS) k_lj_virial(LjArgs<T, OFF> a, LjScalars<T> p, double ghost_w, double* __restrict__ part) {
+  lj_virial_rows<T, OFF, TRI>(a, p, ghost_w, part);
 }
 template <typename T, typename OFF, bool TRI>
-__global__ void __launch_bounds__(STAGE_THREADS) k_lj_virial_typed(LjArgs<T, OFF> a, LjByType<T> p, double* __restrict__ part) {
-  lj_virial_rows<T, OFF, TRI>(a, p, part);
+__global__ void __launch_bounds__(STAGE_THREADS) k_lj_virial_typed(LjArgs<T, OFF> a, LjByType<T> p, double ghost_w, double* __restrict__ part) {
+  lj_virial_rows<T, OFF, TRI>(a, p, ghost_w, part);
 }
 
 // One block: thread t adds the partials t, t + 256, ... in that order, then a tree over the threads.  scale: 1 after a
@@ -84,7 +89,7 @@ __global__ void __launch_bounds__(STAGE_THREADS) k_virial_reduce(const double* _
 // lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables (as lj_launch).
 int virial_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, double* out_dev, hipStream_t s,
                   const uint32_t* status) {
-  const int32_t n = h->n;
+  const int32_t n = h->n_rows;
   if (n == 0) {
     HIPCHK(h, hipMemsetAsync(out_dev, 0, sizeof(double) * VIR_OUT, s));
     return NL_OK;
@@ -97,14 +102,15 @@ int virial_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double
   }
   const int32_t nblk = (int32_t)std::min<int64_t>(((int64_t)n + 3) / 4, VIR_BLOCKS);
   double* part = h->vir_part;
+  const double ghost_w = h->plan.full ? 1.0 : 0.5;
   const int rc = dispatch_t_off(h, [&](auto t, auto off) -> int {
     using T = decltype(t);
     using OFF = decltype(off);
     const LjArgs<T, OFF> a = lj_args<T, OFF>(h, q_dev, stride, status);
     auto launch = [&](auto tri) {
       constexpr bool R = decltype(tri)::value;
-      if (lj) hipLaunchKernelGGL((k_lj_virial<T, OFF, R>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_scalars<T>(lj), part);
-      else hipLaunchKernelGGL((k_lj_virial_typed<T, OFF, R>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_by_type<T>(h), part);
+      if (lj) hipLaunchKernelGGL((k_lj_virial<T, OFF, R>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_scalars<T>(lj), ghost_w, part);
+      else hipLaunchKernelGGL((k_lj_virial_typed<T, OFF, R>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_by_type<T>(h), ghost_w, part);
     };
     h->plan.tilt ? launch(std::true_type()) : launch(std::false_type());
     HIPCHK(h, hipGetLastError());

@@ -106,6 +106,19 @@ class NeighListGPU:
         """Replay asynchronous builds from a captured hipGraph (nl_set_graph): saves launch overhead on small systems."""
         check(self._lib.nl_set_graph(self._h, 1 if on else 0), "nl_set_graph")
 
+    def set_local_ids(self, on: bool = True):
+        """Local-index slab lists (nl_set_local_ids): slab builds then take ``gid=None`` only, their ids are rows of the
+        caller's buffer (owned rows first, ghosts behind them), and lj_forces, lj_virial and pair_histogram read them, one
+        rank's share each.  Synchronous; a changed value drops the list.  Off by default."""
+        check(self._lib.nl_set_local_ids(self._h, 1 if on else 0), "nl_set_local_ids")
+
+    @property
+    def local_ids(self):
+        """Whether slab builds are local-index lists that the consumers accept (nl_get_local_ids)."""
+        on = C.c_int()
+        check(self._lib.nl_get_local_ids(self._h, C.byref(on)), "nl_get_local_ids")
+        return bool(on.value)
+
     def set_periodic(self, minimum_image=True, axes=None):
         """Minimum-image distances across the periodic faces (nl_set_periodic_axes).  The reference, and the default
         here, wrap the cell stencil but measure distances in an open box.  ``axes`` picks the periodic axes: a 3-tuple
@@ -489,7 +502,8 @@ class NeighListGPU:
         the last build (nl_lj_forces): gather per row after a full-list build, pair-once with atomics after a half
         build.  ``wait=False`` (nl_lj_forces_enqueue): no wait for the build, stream-ordered behind the last update();
         rc_force must then be <= cut-off - skin, and a list whose build failed gives NaN.  ``out``: an (n, 4) tensor
-        to write into (graph capture)."""
+        to write into (graph capture).  After a slab build under set_local_ids: ``(n_rows, 4)``, the owned particles' rows
+        of the global result (a ghost partner receives no reaction: its owner evaluates the pair in its own row)."""
         return self._lj("nl_lj_forces", q, (epsilon, sigma, rc_force), wait, out)
 
     def _lj(self, name, q, lj, wait, out):
@@ -504,9 +518,10 @@ class NeighListGPU:
             if o.shape != (8,) or o.dtype != torch.float64 or not o.is_contiguous() or o.device != q.device:
                 raise TypeError("out must be a contiguous float64 tensor of 8 on the list's device")
         else:
-            o = torch.empty((n, 4), dtype=self.dtype, device=self.device) if out is None else out
-            if o.shape != (n, 4) or o.dtype != self.dtype or not o.is_contiguous():
-                raise TypeError("out must be a contiguous (n, 4) tensor of the list's dtype")
+            rows = self._n_rows  # (a whole build: n)
+            o = torch.empty((rows, 4), dtype=self.dtype, device=self.device) if out is None else out
+            if o.shape != (rows, 4) or o.dtype != self.dtype or not o.is_contiguous():
+                raise TypeError("out must be a contiguous (n_rows, 4) tensor of the list's dtype")
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if lj and lj[2] is None:
             lj = (lj[0], lj[1], self.search_length if wait else self.search_length - self.skin)
@@ -522,7 +537,8 @@ class NeighListGPU:
         Pressure: ``P = N kT / V + (w[0] + w[1] + w[2]) / (3 V)``.
         ``wait``, ``rc_force`` and ``out`` (a float64 tensor of 8) as for lj_forces; with ``wait=False``
         (nl_lj_virial_enqueue) a list whose build failed gives 8 NaN.  The first call allocates scratch: make it before
-        a graph capture."""
+        a graph capture.  After a slab build under set_local_ids: this rank's share (a pair that crosses a cut counts 1/2
+        on either side, so n_in may be a half-integer); the ranks' 8 doubles add up to the global box's."""
         return self._lj("nl_lj_virial", q, (epsilon, sigma, rc_force), wait, out)
 
     def lj_virial_typed(self, q, wait=True, out=None):
@@ -542,7 +558,9 @@ class NeighListGPU:
         ``wait=False``, nl_pair_histogram_enqueue).  Returns a contiguous int64 device tensor ``(nbins,)``, or with
         ``typed`` (nl_pair_histogram_typed) ``(ntypes (ntypes + 1) / 2, nbins)`` with the row ``rdf.slot(a, b, ntypes)`` per
         pair of types of set_type_cutoffs.  New and zeroed when ``out`` is None; otherwise the counts are added to ``out``,
-        so frames accumulate.  Exact integer counts, the same for both list kinds; allocates nothing: it can be captured."""
+        so frames accumulate.  Exact integer counts, the same for both list kinds; allocates nothing: it can be captured.
+        After a slab build under set_local_ids: this rank's share in whole pairs (a pair that crosses a cut is counted by
+        exactly one of its two ranks); the ranks' counters add up to the global box's, bit for bit."""
         n = self._check_q(q, None)
         if n != self._n:
             raise ValueError("q must hold the particles the list was built from")
@@ -571,6 +589,8 @@ class NeighListGPU:
 
         if self.periodic_mask() != 7:
             raise ValueError("rdf() needs a box periodic on all three axes")
+        if self._n_rows != self._n:
+            raise ValueError("rdf() needs the global counts: sum the ranks' histograms of a slab build and call rdf.rdf")
         Lx, Ly, Lz = self.box[:3]
         h = hist.detach().cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
         if types is None:

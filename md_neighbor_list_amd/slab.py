@@ -204,6 +204,8 @@ def build(nl, st: SlabState, sync=True, overlap=None) -> None:
     if overlap is None:
         overlap = dist.get_backend() != "nccl" or os.environ.get("NL_SLAB_OVERLAP") == "1" if st.world > 1 else False
     gid = nl.GID_IN_W if st.q_all.shape[1] == 4 else st.gid_all
+    if nl.local_ids:  # local-index lists (nl_set_local_ids): the ids are the rows of q_all, for the consumers
+        gid = None
     if st.world == 1:
         nl.MakeNeighListSlab(st.q_all, gid, st.n_rows, 0, nl.mesh_size[2], sync=sync)
         return
