@@ -113,7 +113,8 @@ int nl_set_graph(nl_handle_t h, int on);
  * at its image next to that cell.  The pair is decided once, by the row that stores it (the smaller id); with
  * NL_LIST_FULL both rows decide on their own and may differ for a pair within one ulp of the cut-off across a face.
  * Slab builds: the two ghost layers of the box-end ranks are the periodic images (the caller sends the layers
- * unshifted, as for the open box).  Takes effect at the next build.
+ * unshifted, as for the open box), rounded as a whole build rounds them: a ghost whose own cell index was wrapped is
+ * taken at rn(rn(z -+ L) +- L), not at z.  Takes effect at the next build.
  * nl_set_periodic(h, m) is nl_set_periodic_axes(h, m ? 7 : 0). */
 int nl_set_periodic(nl_handle_t h, int minimum_image);
 
@@ -185,7 +186,10 @@ int nl_destroy(nl_handle_t h);
  * enqueues (the reference's timing loop, make_list.cu:124-127) and errors surface at the next nl_synchronize /
  * getter.  tblock_size and smem_hei of the reference select among its CUDA variants and have no counterpart.
  * Tested against the oracle at the mesh sizes where the build changes its binning, its row tables are full and its
- * scans take more than 64 blocks (needles, plates, dilute cubes): tests/test_mesh_limits.py. */
+ * scans take more than 64 blocks (needles, plates, dilute cubes): tests/test_mesh_limits.py.
+ * The cut-off decision itself is pinned down at the last bit -- pairs at rc (1 +- k ulp) in cell corners, on the fine rows'
+ * quarter-planes, across every face, a box length outside and in crowded cells -- on every search path, binning, mask,
+ * list kind and as slabs: tests/test_cutoff_paths.py. */
 int nl_make_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, void* stream, int sync);
 
 /* Slab (domain-decomposed) build, SURVEY.md section 8e -- no reference counterpart (the reference is single GPU).

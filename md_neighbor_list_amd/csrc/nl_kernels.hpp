@@ -130,8 +130,12 @@ __device__ __forceinline__ int32_t local_cell(const Grid<T>& g, T x, T y, T z, i
   if (lz >= g.mzl) return -2;
   if (g.slab) {  // the layer this local layer stands for may lie beyond the box end: the particle is its image there
     const int32_t acting = g.z_first + lz;
-    if (acting < 0) sh[2] -= g.L[2];
-    if (acting >= g.m[2]) sh[2] += g.L[2];
+    const T a = acting < 0 ? -g.L[2] : acting >= g.m[2] ? g.L[2] : (T)0;
+    // A particle that was wrapped into that layer is rounded twice by a whole build: the binning stores it at
+    // rn(z -+ L) and the search stages it through the face at rn(that +- L), which need not be z again (z = -0.5:
+    // rn(rn(z + L) - L) differs from z by the rounding error of the first sum).  The shift that takes z there is that
+    // error, exact in T, so the caller's one add_rn(z, sh[2]) lands on the whole build's image bit for bit.
+    if (a != (T)0) sh[2] = sh[2] != (T)0 ? sub_rn(add_rn(add_rn(z, sh[2]), a), z) : a;
   }
   if (shift_out) shift_out[0] = sh[0], shift_out[1] = sh[1], shift_out[2] = sh[2];
   if (wrap_out) wrap_out[0] = wrap[0], wrap_out[1] = wrap[1], wrap_out[2] = wrap[2];  // (the wraps n of nl_set_pair_images)
