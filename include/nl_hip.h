@@ -610,6 +610,59 @@ int nl_lj_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, dou
 int nl_lj_virial_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 int nl_lj_virial_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 
+/* Tabulated pair potentials: the forces and totals above for any pair potential the caller has sampled (Morse, Buckingham,
+ * Yukawa, a switched WCA, a coarse-grained or force-matched model), as LAMMPS pair_style table, HOOMD pair.Table and the
+ * GROMACS user tables do it: the caller samples once, the kernel interpolates.  The rule:
+ *   - Knots, uniform in r^2 so that no pair needs a square root.  In double D = (r_max^2 - r_min^2) / (nknots - 1) and
+ *     x_k = r_min^2 + k D.  The caller passes F[slot][k] = -U'(r) / r and U[slot][k] = U(r) at r = sqrt(x_k): F is the force
+ *     over r, so the force on i is F d with d = r_i - r_j.  Both arrays are nslots x nknots doubles, row-major, finite.  The
+ *     energy shift is the caller's business: U(r_max) need not be 0.
+ *   - Slots.  ntypes = 1: one table for every pair, with or without a type table set.  ntypes > 1 needs a type table
+ *     (nl_set_type_cutoffs) of exactly that ntypes, checked at the calls: nslots = ntypes (ntypes + 1) / 2 and a pair reads
+ *     slot(a, b) of nl_pair_histogram_typed.  One grid (r_min, r_max, nknots) serves all slots; a pair of types with a
+ *     shorter range pads its table with zeros.
+ *   - Device form, in the position type T: each knot holds {F_k, dF_k, U_k, dU_k} with dF_k = (T)(F[k + 1] - F[k]), the
+ *     difference taken in double and rounded once, dU_k the same, and 0 for the last knot.  x0 = (T)(r_min^2),
+ *     xc = (T)(r_max^2), iD = (T)(1 / D).
+ *   - Per entry: d from the image rule of nl_lj_forces; r2 = dx dx + dy dy + dz dz as the Lennard-Jones pair function writes
+ *     it, without contraction; in = r2 < xc && r2 > 0; outside `in` everything is 0.  For a pair that is in, all in T with one
+ *     rounding per operation: s = (r2 - x0) iD, k = min((int)s, nknots - 2), t = s - (T)k, fr = F_k + t dF_k,
+ *     pe = U_k + t dU_k, (fx, fy, fz) = fr d.
+ *   - Below the table.  A pair that is in with r2 < x0 has no value: its fr and pe are NaN, and the NaN reaches both
+ *     particles' forces (half list: the row's and the partner's; full list: each one's own row) and all 8 totals, n_in
+ *     included.  Deliberately so: a clamp would be silently wrong physics, and an error word would need a host sync.
+ *   - nl_set_pair_table: 2 <= nknots <= NL_TABLE_MAX_KNOTS, 0 < r_min < r_max, finite values, 1 <= ntypes <= NL_MAX_TYPES,
+ *     else NL_ERR_ARG and the old table is kept.  nknots == 0, or F_host and U_host both NULL, clears the table (one of them
+ *     alone NULL is NL_ERR_ARG).  Synchronous, as nl_set_lj_type_params: it waits for the device and copies.  The device
+ *     buffer is kept where the new table fits, so a captured graph keeps reading it (and reads the new table).  The list
+ *     is not touched: nl_update_list is not forced to build.  nl_get_pair_table: NL_ERR_STATE while no table is set.
+ *   - Reach, at the calls: r_max <= rc for the synchronous calls and rc - skin for the enqueue calls; with a type table
+ *     r_max <= rc_ab (less the skin) for every pair of types with rc_ab > 0 -- a pair with rc_ab = 0 has no entries.  Else
+ *     NL_ERR_ARG.  NL_ERR_STATE while no table is set, or while a table of ntypes > 1 has no type table.
+ *   - Everything else is nl_lj_forces / nl_lj_virial and their _enqueue variants: ordering and required state, NaN on a
+ *     non-zero status word, the layouts of f_dev (n_rows x 4 of T: fx, fy, fz, pe_i) and out_dev (8 doubles), the half
+ *     list's reaction with atomics after zeroing f_dev, full-list rows written once, the factor 1/2 of a full list, the
+ *     ghost rules of a local-index slab list (there only ntypes = 1 is reachable: type tables refuse slab builds), the
+ *     shared scratch of the totals with its first-call allocation rule, and totals that are reproducible bit for bit.
+ *     The enqueue variants copy nothing from the host and can be captured.
+ *   - Kernels.  One wave per row over a persistent grid of min(ceil(n_rows / 4), NL_TABLE_BLOCKS) blocks of 4 waves, whose
+ *     waves take the rows 4 block + wave, + 4 blocks, ...  A table of at most NL_TABLE_LDS_BYTES (nslots x nknots x 4 x
+ *     sizeof(T)) is staged into LDS once per block; a larger one is read from global memory.  Both paths compute the same
+ *     bits; NL_TABLE_LDS=0 in the environment of nl_set_pair_table forces the global path for that table (tests, A/B).
+ * Tested contract (tests/test_pair_table.py): every component of every particle within TABLE_C u S,
+ * and the totals within c_W u S, of an O(N^2) float64 sum of the same interpolation rule on the caller's double tables,
+ * S the uncancelled sums including the conditioning of s on the rounding of r2. */
+#define NL_TABLE_MAX_KNOTS 4096
+#define NL_TABLE_BLOCKS 512       /* most blocks of the table kernels */
+#define NL_TABLE_LDS_BYTES 65280  /* largest table staged in LDS: 64 KiB less the 256 bytes of the totals' block partials */
+int nl_set_pair_table(nl_handle_t h, int32_t ntypes, int32_t nknots, double r_min, double r_max, const double* F_host,
+                      const double* U_host);
+int nl_get_pair_table(nl_handle_t h, int32_t* ntypes, int32_t* nknots, double* r_min, double* r_max);
+int nl_table_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_table_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_table_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+int nl_table_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+
 /* The pair-distance histogram of the list, the counts behind a radial distribution function g(r): for everybody
  * (nl_pair_histogram) or per unordered pair of types (nl_pair_histogram_typed).  The rule:
  *   - Entries.  The sum runs over the entries (row i, partner j) of the list of the last build: the filtered list where an

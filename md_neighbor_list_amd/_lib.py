@@ -72,6 +72,12 @@ PROTOTYPES = {
     "nl_lj_virial_enqueue": (C.c_int, [_P, _P, _I32, _D, _D, _D, _P, _P]),
     "nl_lj_virial_typed": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_lj_virial_typed_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_set_pair_table": (C.c_int, [_P, _I32, _I32, _D, _D, C.POINTER(_D), C.POINTER(_D)]),
+    "nl_get_pair_table": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D)]),
+    "nl_table_forces": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_table_forces_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_table_virial": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_table_virial_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_pair_histogram": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_enqueue": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_typed": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),

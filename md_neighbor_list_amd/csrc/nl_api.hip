@@ -11,6 +11,8 @@
 #include <cstring>
 #include <new>
 #include <tuple>
+#include <type_traits>
+#include <vector>
 
 #include "nl_devbuf.hpp"
 #include "nl_kernels.hpp"
@@ -248,6 +250,13 @@ struct nl_handle_s {
   int32_t lj_ntypes = 0;
   double lj_rcf[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // rc_force_ab, [lj_ntypes][lj_ntypes]
   DevBuf<double> vir_part;         // nl_lj_virial (nl_virial.inc): [NL_VIRIAL_BLOCKS][8] block partials, allocated by the first call
+
+  // nl_set_pair_table (nl_table.inc): a tabulated pair potential, linear in r^2 between uniform knots
+  DevBuf<void> tb_tab;             // [nslots][tb_nknots] knots {F, dF, U, dU} in T; items = its bytes (kept across sets that fit)
+  int32_t tb_ntypes = 0, tb_nknots = 0;  // tb_nknots == 0: no table
+  double tb_rmin = 0, tb_rmax = 0;
+  double tb_x0 = 0, tb_xc = 0, tb_iD = 0;  // r_min^2, r_max^2 and 1 / D in double (rounded to T at the launches)
+  int tb_lds_env = 1;              // NL_TABLE_LDS=0 when the table was set: the kernels read it from global memory (tests, same-box A/B)
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -1975,4 +1984,5 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_types.inc"
 #include "nl_images.inc"
 #include "nl_virial.inc"
+#include "nl_table.inc"
 #include "nl_histogram.inc"

@@ -80,15 +80,42 @@ __device__ __forceinline__ void lj_image(T xi, T yi, T zi, T xj, T yj, T zj, T& 
   dx += lx, dy += ly, dz += lz;
 }
 
-// Where a pair's parameters come from: the launch's scalars, or a table over the types of the pair (nl_set_lj_type_params).
-template <typename T> struct LjScalars {
-  static constexpr bool typed = false;
+// Where a pair's values come from -- the pair function is a property of PAR (DESIGN.md section 8o):
+//   row(row, lane)    what a lane keeps for the whole row,
+//   entry(r, j)       what the entry with partner j takes of it (lanes_meet: called by every lane of the wave, in step),
+//   pair(e, d, ...)   the pair's values fx, fy, fz, pe, in from the separation.
+// Lennard-Jones from the launch's scalars, or from a table over the types of the pair (nl_set_lj_type_params): lane
+// t < ntypes holds eps4, sig2 and rcf2 of (t_row, t), an entry picks them by its partner's type with ds_bpermute.
+// A tabulated potential: TableByPair of nl_table.inc.  table: the pair function may give NaN inside its range (a pair below
+// the table), which the totals of nl_virial.inc carry into the pair count as well.
+template <typename T> struct LjRow {
   T eps4, sig2, rcf2;
 };
+template <typename T> struct LjScalars {
+  static constexpr bool lanes_meet = false, table = false;
+  T eps4, sig2, rcf2;
+  __device__ __forceinline__ LjRow<T> row(int32_t, int32_t) const { return {eps4, sig2, rcf2}; }
+  __device__ __forceinline__ LjRow<T> entry(const LjRow<T>& r, int32_t) const { return r; }
+  __device__ __forceinline__ void pair(const LjRow<T>& e, T dx, T dy, T dz, T& fx, T& fy, T& fz, T& pe, bool& in) const {
+    lj_pair<T>(dx, dy, dz, e.eps4, e.sig2, e.rcf2, fx, fy, fz, pe, in);
+  }
+};
 template <typename T> struct LjByType {
-  static constexpr bool typed = true;
+  static constexpr bool lanes_meet = true, table = false;
   const int32_t* __restrict__ types;
   const T* __restrict__ par;  // [3][NL_MAX_TYPES][NL_MAX_TYPES] 4 eps, sigma^2, rc_force^2
+  __device__ __forceinline__ LjRow<T> row(int32_t row, int32_t lane) const {  // this lane's entries of the row's type
+    constexpr int NT2 = NL_MAX_TYPES * NL_MAX_TYPES;
+    const int32_t at = (types[row] & (NL_MAX_TYPES - 1)) * NL_MAX_TYPES + (lane & (NL_MAX_TYPES - 1));
+    return {par[at], par[NT2 + at], par[2 * NT2 + at]};
+  }
+  __device__ __forceinline__ LjRow<T> entry(const LjRow<T>& r, int32_t j) const {
+    const int32_t tj = types[j] & (NL_MAX_TYPES - 1);
+    return {shfl_t(r.eps4, tj), shfl_t(r.sig2, tj), shfl_t(r.rcf2, tj)};
+  }
+  __device__ __forceinline__ void pair(const LjRow<T>& e, T dx, T dy, T dz, T& fx, T& fy, T& fz, T& pe, bool& in) const {
+    lj_pair<T>(dx, dy, dz, e.eps4, e.sig2, e.rcf2, fx, fy, fz, pe, in);
+  }
 };
 
 // What every kernel over the pairs of the list receives (k_lj*, k_lj_virial*).  status (the enqueue variants, which do not
@@ -114,28 +141,18 @@ struct LjPartner {
 
 // The pairs of one row, a wave per row: on_pair(j, partner, dx, dy, dz, fx, fy, fz, pe, in) for every entry of the row, with
 // the separation at the image the list found the pair at (minimum-image list, nl_set_periodic_axes: folded on the periodic
-// axes, L > 0), the values of lj_pair and what LjPartner says of j.  a.n: the rows of the list (n_rows of the build).
-// By type: lane t < ntypes holds eps4, sig2 and rcf2 of (t_row, t), an entry picks them by its partner's type with ds_bpermute.
+// axes, L > 0), the values of PAR's pair function and what LjPartner says of j.  a.n: the rows of the list (n_rows of the build).
 template <typename T, typename OFF, bool TRI, typename PAR, typename F>
 __device__ __forceinline__ void lj_row_pairs(const LjArgs<T, OFF>& a, const PAR& p, int32_t row, int32_t lane, F&& on_pair) {
-  T eps4, sig2, rcf2;  // scalars: the pair's; by type: this lane's entries of the row's type
-  if constexpr (PAR::typed) {
-    constexpr int NT2 = NL_MAX_TYPES * NL_MAX_TYPES;
-    const int32_t at = (p.types[row] & (NL_MAX_TYPES - 1)) * NL_MAX_TYPES + (lane & (NL_MAX_TYPES - 1));
-    eps4 = p.par[at], sig2 = p.par[NT2 + at], rcf2 = p.par[2 * NT2 + at];
-  } else {
-    eps4 = p.eps4, sig2 = p.sig2, rcf2 = p.rcf2;
-  }
+  const auto rp = p.row(row, lane);
   T xi, yi, zi;
   load_xyz(a.q, a.stride, row, xi, yi, zi);
   const OFF b = a.kp[row], e = a.kp[row + 1];
-  for (OFF k = b + lane; (PAR::typed ? k - lane : k) < e; k += 64) {  // (by type: every lane stays for the bpermute)
-    const bool valid = !PAR::typed || k < e;
+  for (OFF k = b + lane; (PAR::lanes_meet ? k - lane : k) < e; k += 64) {  // (lanes_meet: every lane stays for the bpermute)
+    const bool valid = !PAR::lanes_meet || k < e;
     const int32_t j = valid ? a.list[k] : row;
-    T e4 = eps4, s2 = sig2, c2 = rcf2;
-    if constexpr (PAR::typed) {
-      const int32_t tj = p.types[j] & (NL_MAX_TYPES - 1);
-      e4 = shfl_t(eps4, tj), s2 = shfl_t(sig2, tj), c2 = shfl_t(rcf2, tj);
+    const auto ep = p.entry(rp, j);
+    if constexpr (PAR::lanes_meet) {
       if (!valid) continue;
     }
     T xj, yj, zj;
@@ -143,7 +160,7 @@ __device__ __forceinline__ void lj_row_pairs(const LjArgs<T, OFF>& a, const PAR&
     T dx, dy, dz, fx, fy, fz, pe;
     bool in;
     lj_image<T, TRI>(xi, yi, zi, xj, yj, zj, dx, dy, dz, a.Lx, a.Ly, a.Lz, a.xy, a.xz, a.yz);
-    lj_pair<T>(dx, dy, dz, e4, s2, c2, fx, fy, fz, pe, in);
+    p.pair(ep, dx, dy, dz, fx, fy, fz, pe, in);
     const LjPartner w = {j >= a.n, dz < (T)0 || (dz == (T)0 && zi < zj)};
     on_pair(j, w, dx, dy, dz, fx, fy, fz, pe, in);
   }
@@ -152,9 +169,7 @@ __device__ __forceinline__ void lj_row_pairs(const LjArgs<T, OFF>& a, const PAR&
 // one wave per row; f = {fx, fy, fz, pe_i} of the list's rows, pe_i = half of the pair energies of particle i.  A list whose
 // build failed (status) gives NaN forces.
 template <typename T, bool HALF, typename OFF, bool TRI, typename PAR>
-__device__ __forceinline__ void lj_row(const LjArgs<T, OFF>& a, const PAR& p, T* __restrict__ f) {
-  const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (row >= a.n) return;
+__device__ __forceinline__ void lj_row_at(const LjArgs<T, OFF>& a, const PAR& p, T* __restrict__ f, int32_t row, int32_t lane) {
   if (a.status && *a.status != 0u) {  // (uniform: every row of the launch takes this branch)
     if (lane == 0) {
       const T nan = (T)NAN;
@@ -183,6 +198,14 @@ __device__ __forceinline__ void lj_row(const LjArgs<T, OFF>& a, const PAR& p, T*
       f[(size_t)row * 4 + 0] = ax, f[(size_t)row * 4 + 1] = ay, f[(size_t)row * 4 + 2] = az, f[(size_t)row * 4 + 3] = ae;
     }
   }
+}
+
+// one block per 4 rows (k_lj*); the persistent grid of the tabulated forces walks lj_row_at itself (nl_table.inc)
+template <typename T, bool HALF, typename OFF, bool TRI, typename PAR>
+__device__ __forceinline__ void lj_row(const LjArgs<T, OFF>& a, const PAR& p, T* __restrict__ f) {
+  const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (row >= a.n) return;
+  lj_row_at<T, HALF, OFF, TRI>(a, p, f, row, lane);
 }
 
 template <typename T, bool HALF, typename OFF, bool TRI>
@@ -261,10 +284,12 @@ int lj_typed_check(nl_handle_t h, double skin) {
 //   (what a list reused within the skin guarantees) first, then consumer_ready; the kernel takes the build's status word.
 template <typename OUT>
 int lj_call(nl_handle_t h, const void* q_dev, int32_t q_stride, const double* lj, OUT* out_dev, void* stream, bool enqueue,
-            int (*launch)(nl_handle_t, const void*, int32_t, const double*, OUT*, hipStream_t, const uint32_t*)) {
+            int (*launch)(nl_handle_t, const void*, int32_t, const double*, OUT*, hipStream_t, const uint32_t*),
+            int (*own_reach)(nl_handle_t, double) = nullptr) {
   if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4) || (lj && (!(lj[2] > 0) || !(lj[1] > 0)))) return fail(h, NL_ERR_ARG);
   const hipStream_t s = (hipStream_t)stream;
   const auto reach = [&](double skin) -> int {
+    if (own_reach) return own_reach(h, skin);  // (another pair function's: table_reach of nl_table.inc)
     if (!lj) return lj_typed_check(h, skin);
     return lj[2] <= h->rc - skin ? NL_OK : fail(h, NL_ERR_ARG);  // the list does not reach that far (rc - 0.0 is rc, exactly)
   };

@@ -38,6 +38,7 @@ __device__ __forceinline__ void lj_virial_rows(const LjArgs<T, OFF>& a, const PA
       acc[3] = fma(c, (double)wxy, acc[3]), acc[4] = fma(c, (double)wxz, acc[4]), acc[5] = fma(c, (double)wyz, acc[5]);
       acc[6] = fma(c, (double)pe, acc[6]);  // (+-0 outside rc_force, as the forces)
       acc[7] += in ? c : 0.0;
+      if constexpr (PAR::table) acc[7] += (in && pe != pe) ? (double)NAN : 0.0;  // (a pair below the table: all 8 are NaN)
     });
   }
 #pragma unroll
@@ -86,6 +87,16 @@ __global__ void __launch_bounds__(STAGE_THREADS) k_virial_reduce(const double* _
   if (t < VIR_OUT) out[t] = (status && *status != 0u) ? (double)NAN : scale * sm[t][0];
 }
 
+// vir_part, allocated by the first call of any of the totals (nl_lj_virial*, nl_table_virial*): a stream that is being
+// captured cannot allocate.
+int virial_scratch(nl_handle_t h, hipStream_t s) {
+  if (h->vir_part) return NL_OK;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHK(h, hipStreamIsCapturing(s, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(h, NL_ERR_STATE);
+  return side_alloc(h, h->vir_part, sizeof(double) * VIR_OUT * VIR_BLOCKS);
+}
+
 // lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables (as lj_launch).
 int virial_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, double* out_dev, hipStream_t s,
                   const uint32_t* status) {
@@ -94,12 +105,7 @@ int virial_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double
     HIPCHK(h, hipMemsetAsync(out_dev, 0, sizeof(double) * VIR_OUT, s));
     return NL_OK;
   }
-  if (!h->vir_part) {  // the first call: a stream that is being captured cannot allocate
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIPCHK(h, hipStreamIsCapturing(s, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(h, NL_ERR_STATE);
-    if (int rc = side_alloc(h, h->vir_part, sizeof(double) * VIR_OUT * VIR_BLOCKS)) return rc;
-  }
+  if (int rc = virial_scratch(h, s)) return rc;
   const int32_t nblk = (int32_t)std::min<int64_t>(((int64_t)n + 3) / 4, VIR_BLOCKS);
   double* part = h->vir_part;
   const double ghost_w = h->plan.full ? 1.0 : 0.5;

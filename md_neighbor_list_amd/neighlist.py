@@ -546,6 +546,47 @@ class NeighListGPU:
         nl_lj_virial_typed_enqueue."""
         return self._lj("nl_lj_virial_typed", q, (), wait, out)
 
+    # ------------------------------------------------------------------ tabulated pair potentials
+    def set_pair_table(self, F, U, r_min, r_max):
+        """A tabulated pair potential for table_forces and table_virial (nl_set_pair_table): ``F = -U'(r) / r`` and
+        ``U`` at the knots ``pair_table.knots(r_min, r_max, nknots)``, uniform in r^2 (``pair_table.sample`` makes them from
+        callables).  ``(nknots,)``: one table for every pair; ``(nslots, nknots)``: row ``rdf.slot(a, b, ntypes)`` per pair of
+        types of set_type_cutoffs, ntypes taken from nslots.  Synchronous; keeps its device buffer where the table fits."""
+        import numpy as np
+
+        F, U = (np.ascontiguousarray(np.asarray(m, dtype=np.float64)) for m in (F, U))
+        if F.shape != U.shape or F.ndim not in (1, 2):
+            raise TypeError("F and U must both be (nknots,) or (nslots, nknots)")
+        nslots = 1 if F.ndim == 1 else F.shape[0]
+        nt = int(round(((8 * nslots + 1) ** 0.5 - 1) / 2))
+        if nt * (nt + 1) // 2 != nslots:
+            raise TypeError(f"{nslots} rows are not ntypes (ntypes + 1) / 2 for any ntypes")
+        ptrs = [m.ctypes.data_as(C.POINTER(C.c_double)) for m in (F, U)]
+        check(self._lib.nl_set_pair_table(self._h, nt, int(F.shape[-1]), float(r_min), float(r_max), *ptrs), "nl_set_pair_table")
+
+    def clear_pair_table(self):
+        check(self._lib.nl_set_pair_table(self._h, 0, 0, 0.0, 0.0, None, None), "nl_set_pair_table")
+
+    def pair_table(self):
+        """``{"ntypes", "nknots", "r_min", "r_max"}`` of the table set (nl_get_pair_table), or None without one."""
+        nt, nk, lo, hi = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        code = self._lib.nl_get_pair_table(self._h, C.byref(nt), C.byref(nk), C.byref(lo), C.byref(hi))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_pair_table")
+        return {"ntypes": nt.value, "nknots": nk.value, "r_min": lo.value, "r_max": hi.value}
+
+    def table_forces(self, q, wait=True, out=None):
+        """lj_forces with the pair function of set_pair_table (nl_table_forces): ``(n, 4) = {fx, fy, fz, pe_i}``, linear
+        interpolation in r^2 between the knots, nothing beyond r_max (within the list's cut-off; less the skin with
+        ``wait=False``, nl_table_forces_enqueue).  A pair closer than r_min gives NaN to both its particles."""
+        return self._lj("nl_table_forces", q, (), wait, out)
+
+    def table_virial(self, q, wait=True, out=None):
+        """lj_virial with the pair function of set_pair_table (nl_table_virial; ``wait=False``: nl_table_virial_enqueue):
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, n_in the pairs within r_max; 8 NaN where a pair lies below r_min."""
+        return self._lj("nl_table_virial", q, (), wait, out)
+
     def _ntypes(self):
         """ntypes of the handle's type table (nl_get_types; NL_ERR_STATE without one)."""
         ptr, n, nt = C.c_void_p(), C.c_int32(), C.c_int32()
