@@ -1922,8 +1922,8 @@ __device__ __forceinline__ void cls_stage(const E* __restrict__ from, const ClsC
   }
 }
 
-// longest row k_fill_masks assembles in LDS (longer ones are written entry by entry); half list: 5 + 5 KiB of LDS =
-// 16 workgroups per CU
+// slots of a row k_fill_masks assembles in LDS: rows shorter than this (one slot stays free for the lanes without an
+// entry; rows of this length and more are written entry by entry); half list: 5 + 5 KiB of LDS = 16 workgroups per CU
 template <bool FULL> constexpr int EXPAND_RMAX_OF = FULL ? 192 : 160;
 constexpr int EXPAND_WAVES = 2;  // waves per workgroup of k_fill_masks: 16 workgroups (cells) in flight per CU
 
@@ -2087,43 +2087,69 @@ k_fill_masks(SweepArgs<T> a) {
 #if NL_STAMP_FILL
       fstamp(3);  // words arrived, popcounts, scans
 #endif
-      if (nmax <= EXPAND_RMAX) {
+      // Where the four rows go: a buffer descriptor per row (base: the row's first entry, size: its nrow entries),
+      // built once per group.  The range check drops a store whose offset is not below the size, so a lane without
+      // an entry needs no exec region and no branch; a dead row has size 0.
+      __amdgpu_buffer_rsrc_t dst[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) dst[q] = __builtin_amdgcn_make_buffer_rsrc(a.list + (ptrdiff_t)base(u0 + q), 0, nrow[q] * 4, 0x00020000);
+      // The walk over the set bits (both paths below): no exec region and no branch but the back edge, or hipcc sinks
+      // the reads under the branches and waits for each in turn.  A lane whose word is exhausted
+      // reads slot 0 of its row's tiles and writes where it does no harm; `word &= word - 1` leaves zero zero; the
+      // loop ends on a wave-uniform test.  LDS addresses are formed as byte addresses (no shift-select-shift).
+      typedef __attribute__((address_space(3))) int32_t lds_i32;
+      uint32_t src[4];  // byte address of gq[q]
+#pragma unroll
+      for (int q = 0; q < 4; q++) src[q] = (uint32_t)(uintptr_t)(lds_i32*)gq[q];
+      auto read_next = [&](int32_t (&val)[4], bool (&on)[4]) {
+        uint32_t rd[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) rd[q] = src[q] + ((uint32_t)__builtin_ctz(word[q]) << 8);  // tile t: t * WAVE * 4 bytes on (word 0: not used)
+        asm volatile("" : "+v"(rd[0]), "+v"(rd[1]), "+v"(rd[2]), "+v"(rd[3]));  // (select after the add: one v_lshl_add, not shift, select, add)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          on[q] = word[q] != 0;
+          val[q] = *(const lds_i32*)(uintptr_t)(on[q] ? rd[q] : src[q]);
+        }
+        asm volatile("" : "+v"(val[0]), "+v"(val[1]), "+v"(val[2]), "+v"(val[3]));  // the four reads, then one wait
+      };
+      if (nmax < EXPAND_RMAX) {
         // The set bits of a lane are consecutive entries of the row, but one trip through the bit loop writes one
         // entry per lane: ~13 lanes spread over the whole 290-byte row, 5-6 trips per row (8 for a full list).  So
         // the row is put together in LDS first (same loop, ds_write instead of a global store) and leaves as
         // 64-entry runs: 2-3 store instructions per row, each to consecutive addresses.
-        int32_t* const cw = lds + CAP + wave * 4 * EXPAND_RMAX;
+        // Row q has slots [q EXPAND_RMAX, (q + 1) EXPAND_RMAX) of the wave's buffer.  nmax < EXPAND_RMAX: slot nrow[0]
+        // of row 0 is free -- the exhausted lanes of all four rows write there (one address: no bank conflict).
+        const uint32_t cw = (uint32_t)(uintptr_t)(lds_i32*)(lds + CAP + wave * 4 * EXPAND_RMAX);
+        uint32_t dump = cw + 4 * (uint32_t)nrow[0];
+        asm volatile("" : "+v"(dump));  // kept in a vector register (a select takes one scalar operand: its mask)
+        uint32_t at[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) ptr[q] += q * EXPAND_RMAX;
-        while (word[0] | word[1] | word[2] | word[3]) {
+        for (int q = 0; q < 4; q++) at[q] = cw + 4 * (q * EXPAND_RMAX + ptr[q]);
+        do {  // (a group without a bit takes one trip, all four rows to the dump)
           int32_t val[4];
           bool on[4];
+          read_next(val, on);
 #pragma unroll
           for (int q = 0; q < 4; q++) {
-            on[q] = word[q] != 0;
-            const int32_t t = on[q] ? __ffs(word[q]) - 1 : 0;
-            val[q] = gq[q][t * WAVE];  // unconditional read of a valid slot: the four reads go out back to back
+            *(lds_i32*)(uintptr_t)(on[q] ? at[q] : dump) = val[q];
+            at[q] += 4;  // (an exhausted lane's place no longer matters)
+            word[q] &= word[q] - 1;
           }
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            if (on[q]) {
-              cw[ptr[q]] = val[q];
-              ptr[q]++;
-              word[q] &= word[q] - 1;
-            }
-          }
-        }
+        } while (__builtin_amdgcn_ballot_w64((word[0] | word[1] | word[2] | word[3]) != 0) != 0);
 #if NL_STAMP_FILL
         fstamp(4);  // bit loop
 #endif
         __builtin_amdgcn_wave_barrier();  // the buffer is private to the wave: LDS executes its accesses in order
-        for (int32_t e = lane; e - lane < nmax; e += WAVE) {
+        for (int32_t e0 = 0; e0 < nmax; e0 += WAVE) {
+          const int32_t e = e0 + lane;
+          const uint32_t rd = cw + 4 * (uint32_t)min(e, EXPAND_RMAX - 1);
           int32_t val[4];
 #pragma unroll
-          for (int q = 0; q < 4; q++) val[q] = cw[q * EXPAND_RMAX + min(e, EXPAND_RMAX - 1)];
+          for (int q = 0; q < 4; q++) val[q] = *(const lds_i32*)(uintptr_t)(rd + 4 * q * EXPAND_RMAX);
+          asm volatile("" ::"v"(val[0]), "v"(val[1]), "v"(val[2]), "v"(val[3]) : "memory");  // the four reads, then one wait
 #pragma unroll
-          for (int q = 0; q < 4; q++)
-            if (e < nrow[q]) a.list[(size_t)base(u0 + q) + e] = val[q];
+          for (int q = 0; q < 4; q++) __builtin_amdgcn_raw_buffer_store_b32((uint32_t)val[q], dst[q], e * 4, 0, 0);  // e >= nrow[q]: dropped
         }
         __builtin_amdgcn_wave_barrier();
 #if NL_STAMP_FILL
@@ -2131,24 +2157,21 @@ k_fill_masks(SweepArgs<T> a) {
 #endif
         continue;
       }
-      while (word[0] | word[1] | word[2] | word[3]) {  // a very long row: straight to memory
+      // a very long row: straight to memory, an exhausted lane's store at an offset past every row
+      uint32_t at[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) at[q] = 4 * ptr[q];
+      do {
         int32_t val[4];
         bool on[4];
+        read_next(val, on);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-          on[q] = word[q] != 0;
-          const int32_t t = on[q] ? __ffs(word[q]) - 1 : 0;
-          val[q] = gq[q][t * WAVE];
+          __builtin_amdgcn_raw_buffer_store_b32((uint32_t)val[q], dst[q], (int32_t)(on[q] ? at[q] : 0xFFFFFFFCu), 0, 0);
+          at[q] += 4;
+          word[q] &= word[q] - 1;
         }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          if (on[q]) {
-            a.list[(size_t)base(u0 + q) + ptr[q]] = val[q];
-            ptr[q]++;
-            word[q] &= word[q] - 1;
-          }
-        }
-      }
+      } while (__builtin_amdgcn_ballot_w64((word[0] | word[1] | word[2] | word[3]) != 0) != 0);
     }
   }
 #if NL_STAMP_FILL
