@@ -663,6 +663,77 @@ int nl_table_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, 
 int nl_table_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 int nl_table_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 
+/* Embedded-atom potentials (LAMMPS pair_style eam, eam/alloy; HOOMD metal.EAM): forces, per-particle energies and the 8
+ * totals of E = sum_i F_{t_i}(rho_i) + sum_pairs phi(r), rho_i = sum_j f_{t_j}(r_ij), j the partners of i in the list.  The rule:
+ *   - Pair part.  phi is the handle's pair table (nl_set_pair_table), evaluated by exactly the rule stated there, slots and
+ *     all: fr_phi, pe_phi, in_phi.  It must be set (NL_ERR_STATE otherwise); a model without a pair part passes zeros.
+ *   - Density tables.  The grid rule of nl_set_pair_table on a grid of their own: D = (r_max_d^2 - r_min_d^2) / (nknots_d - 1),
+ *     x_k = r_min_d^2 + k D.  One slot per type b of the SOURCE particle: ntypes slots.  The caller passes f[b][k] = f_b(r) and
+ *     G[b][k] = -f_b'(r) / r at r = sqrt(x_k), ntypes x nknots_d doubles each, row-major, finite.  Device form: the knot
+ *     {G_k, dG_k, f_k, df_k} in the position type T, differences taken in double and rounded once, 0 at the last knot;
+ *     x0_d = (T)(r_min_d^2), xc_d = (T)(r_max_d^2), iD = (T)(1 / D).  With r2 of the entry: in_d = r2 < xc_d && r2 > 0;
+ *     s = (r2 - x0_d) iD, k = min((int)s, nknots_d - 2), t = s - (T)k, one rounding per operation; f = f_k + t df_k and
+ *     G = G_k + t dG_k.  Outside in_d a partner contributes nothing.  A pair that is in_d with r2 < x0_d has no value: NaN, by
+ *     the same deliberate rule as a pair below the pair table.
+ *   - Embedding tables.  One slot per type a, uniform in rho on [0, rho_max]: rho_k = k Drho, Drho = rho_max / (nknots_e - 1)
+ *     in double.  The caller passes E[a][k] = F_a(rho_k) and P[a][k] = F_a'(rho_k).  Device form {E_k, dE_k, P_k, dP_k} in T,
+ *     rounded as above; iDrho = (T)(1 / Drho), rmax = (T)rho_max.  Per particle, in T with one rounding per operation:
+ *     s = rho iDrho, k = min((int)s, nknots_e - 2), t = s - (T)k, Fe = E_k + t dE_k, fp = P_k + t dP_k.  rho outside
+ *     0 <= rho <= rmax, or NaN, gives Fe = fp = NaN: a clamp would be silently wrong physics.
+ *   - Densities.  rho_i is the sum in T of f_{t_j}(r2) over the entries of i.  After NL_LIST_FULL row i gathers its partners
+ *     and is written once.  After NL_LIST_HALF rho is zeroed, every entry (row i, partner j) adds f_{t_j} to the row's sum and
+ *     f_{t_i} to rho_j with a floating-point atomic, and the row's sum reaches rho_i with one atomic.
+ *   - Forces.  For an entry (row i, partner j): d from the image rule of nl_lj_forces, r2 = dx dx + dy dy + dz dz without
+ *     contraction; G_i = the density slot t_i at r2, G_j = the slot t_j; emb = fp_i G_j + fp_j G_i where in_d, else 0 (taken
+ *     only where in_d, not as a product with 0: a NaN fp reaches the partners within r_max_d and nobody else);
+ *     fr = fr_phi + emb, one rounding per operation, no FMA; (fx, fy, fz) = fr d, the force on i, d = r_i - r_j;
+ *     in = in_phi || in_d.  f_dev is n x 4 of T: {fx, fy, fz, pe_i}, pe_i = (half the pair energies pe_phi, as
+ *     nl_table_forces) + Fe_i, Fe_i added last with one rounding, so sum pe_i = E.  The half list's reaction is
+ *     nl_table_forces': atomics after zeroing.
+ *   - Totals, the 8 doubles of nl_lj_virial: W_ab = sum_pairs d_a (fr d_b), U = sum_pairs pe_phi + sum_i Fe_i, n_in = the
+ *     pairs with `in`.  Terms in T, converted and summed in double in a fixed order as nl_lj_virial's; each Fe_i enters a
+ *     double sum of its own once, whatever the list kind (it is not halved after a full build).
+ *   - NaN.  A NaN fp_i (rho_i out of range) reaches i's own force and energy, the force of every partner within r_max_d and all
+ *     8 totals; a pair below r_min_d reaches both densities and from there the same places.
+ *   - Reproducibility.  After NL_LIST_FULL no pass uses an atomic: two calls on the same list and positions give the same
+ *     bits -- forces, rho and the 8 totals.  After NL_LIST_HALF rho is summed by atomics, so rho and EVERYTHING that follows,
+ *     the 8 totals included, is reproducible only within the tested bound: nl_eam_virial does not inherit nl_lj_virial's
+ *     bit-for-bit promise on a half list.
+ *   - Types.  ntypes == 1: one density and one embedding slot, with or without a type table.  ntypes > 1 needs a type table
+ *     of exactly that ntypes (NL_ERR_STATE without one, NL_ERR_ARG for another ntypes) and a pair table of 1 or ntypes types.
+ *   - Reach, at the calls: r_max of the pair table and r_max_d <= rc for the synchronous calls, <= rc - skin for the enqueue
+ *     calls; with a type table <= rc_ab (less the skin) for every rc_ab > 0.  Else NL_ERR_ARG.
+ *   - nl_set_eam: 2 <= nknots_d, nknots_e <= NL_TABLE_MAX_KNOTS, 0 < r_min_d < r_max_d, rho_max > 0, 1 <= ntypes <=
+ *     NL_MAX_TYPES, finite values everywhere, else NL_ERR_ARG and the old tables are kept.  nknots_d == 0, nknots_e == 0 or
+ *     four NULL arrays clear the tables (some of them NULL: NL_ERR_ARG).  Synchronous; the device buffer is kept where the new
+ *     tables fit, as nl_set_pair_table's; the list is not touched.  nl_get_eam: the scalars, and whether the density pass
+ *     (lds_density) and the forces and totals (lds_forces) read their tables from LDS; NL_ERR_STATE while no tables are set.
+ *   - Scratch.  rho, fp and Fe (3 T per particle, sized by n_max) belong to the handle.  The first of the four calls allocates
+ *     them: on a stream that is being captured it returns NL_ERR_STATE (call once before the capture), the rule of the
+ *     totals' scratch, which nl_eam_virial shares.  nl_initialize drops them.  nl_eam_get_density: rho_i and fp_i = F'(rho_i)
+ *     of the last call in T, in row order, valid until the next call or nl_initialize, stream-ordered behind that call
+ *     (no wait); NL_ERR_STATE before the first call.
+ *   - Slab and distributed builds: NL_ERR_STATE, local-index slab lists (nl_set_local_ids) included.  The force on an owned
+ *     particle needs fp of its ghost partners, a forward halo exchange of fp between the two passes that is the caller's.
+ *   - Kernels.  The persistent grid of the table kernels.  Density pass: its table in LDS where it fits NL_TABLE_LDS_BYTES;
+ *     embedding: one thread per particle, table from global memory; forces and totals: the pair table and the density table
+ *     both in LDS where together they fit NL_TABLE_LDS_BYTES, else both from global memory.  NL_TABLE_LDS=0 in the environment
+ *     of nl_set_eam forces the global path of all three.  Both paths compute the same bits.
+ *   - Everything else (ordering, state, NaN on a non-zero status word, n == 0, the enqueue variants copy nothing and can be
+ *     captured) is nl_table_forces' / nl_table_virial's.
+ * Tested contract (tests/test_eam.py): rho within EAM_C_RHO u S_rho, every component of every particle
+ * within EAM_C u S and the totals within EAM_CW u S of an O(N^2) float64 evaluation of the same rule, S the uncancelled sums
+ * including the conditioning of fp and Fe on rho. */
+int nl_set_eam(nl_handle_t h, int32_t ntypes, int32_t nknots_d, double r_min_d, double r_max_d, const double* f_host,
+               const double* G_host, int32_t nknots_e, double rho_max, const double* E_host, const double* P_host);
+int nl_get_eam(nl_handle_t h, int32_t* ntypes, int32_t* nknots_d, double* r_min_d, double* r_max_d, int32_t* nknots_e,
+               double* rho_max, int32_t* lds_density, int32_t* lds_forces);
+int nl_eam_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_eam_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_eam_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+int nl_eam_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+int nl_eam_get_density(nl_handle_t h, const void** rho_dev, const void** fp_dev, int32_t* n);
+
 /* The pair-distance histogram of the list, the counts behind a radial distribution function g(r): for everybody
  * (nl_pair_histogram) or per unordered pair of types (nl_pair_histogram_typed).  The rule:
  *   - Entries.  The sum runs over the entries (row i, partner j) of the list of the last build: the filtered list where an

@@ -258,6 +258,14 @@ struct nl_handle_s {
   double tb_x0 = 0, tb_xc = 0, tb_iD = 0;  // r_min^2, r_max^2 and 1 / D in double (rounded to T at the launches)
   int tb_lds_env = 1;              // NL_TABLE_LDS=0 when the table was set: the kernels read it from global memory (tests, same-box A/B)
 
+  // nl_set_eam (nl_eam.inc): the density and embedding tables of an embedded-atom potential; the pair part is tb_* above
+  DevBuf<void> ea_tab;             // [ea_ntypes][ea_nkd] density knots {G, dG, f, df}, then [ea_ntypes][ea_nke] embedding knots {E, dE, P, dP}, in T
+  int32_t ea_ntypes = 0, ea_nkd = 0, ea_nke = 0;  // ea_nkd == 0: no tables
+  double ea_rmin = 0, ea_rmax = 0, ea_rhomax = 0;
+  double ea_x0 = 0, ea_xc = 0, ea_iD = 0, ea_iDrho = 0;  // r_min_d^2, r_max_d^2, 1 / D and 1 / Drho in double (rounded to T at the launches)
+  int ea_lds_env = 1;              // NL_TABLE_LDS=0 when the tables were set (as tb_lds_env)
+  DevBuf<void> ea_part;            // [3][n_max] rho, fp = F'(rho), Fe = F(rho) of the last EAM call in T, allocated by the first call
+
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
   DevBuf<uint32_t> images;         // [capacity] int8 {s_a, s_b, s_c, 0} per entry, at the entry's index in `list`
@@ -1392,6 +1400,7 @@ int nl_initialize(nl_handle_t h, int32_t n_max) {
   h->kp_alt.release();
   h->kp_alt_valid = false;
   h->resort_buf.release();
+  h->ea_part.release();
   // the transposed list and its per-particle counts and cursors (nl_get_full_transposed: sized by n_max on first use)
   h->t_list.release(), h->t_count.release(), h->t_cursor.release();
   h->t_rows_cap = 0;
@@ -1985,4 +1994,5 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_images.inc"
 #include "nl_virial.inc"
 #include "nl_table.inc"
+#include "nl_eam.inc"
 #include "nl_histogram.inc"

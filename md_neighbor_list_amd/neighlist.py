@@ -587,6 +587,58 @@ class NeighListGPU:
         ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, n_in the pairs within r_max; 8 NaN where a pair lies below r_min."""
         return self._lj("nl_table_virial", q, (), wait, out)
 
+    # ------------------------------------------------------------------ embedded-atom potentials
+    def set_eam(self, f, G, r_min, r_max, E, P, rho_max):
+        """The density and embedding tables of an embedded-atom potential (nl_set_eam); the pair part is the table of
+        set_pair_table, which must be set as well (zeros for a model without one).  ``f = f_b(r)`` and ``G = -f_b'(r) / r`` at
+        the knots ``pair_table.knots(r_min, r_max, nknots_d)``, ``E = F_a(rho)`` and ``P = F_a'(rho)`` at
+        ``rho_k = k rho_max / (nknots_e - 1)`` (``eam.sample`` makes all four from callables).  ``(nknots,)``: one type;
+        ``(ntypes, nknots)``: one row per type of set_type_cutoffs.  Synchronous; keeps its device buffer where the tables fit."""
+        import numpy as np
+
+        f, G, E, P = (np.ascontiguousarray(np.atleast_2d(np.asarray(m, dtype=np.float64))) for m in (f, G, E, P))
+        if f.shape != G.shape or E.shape != P.shape or f.ndim != 2 or E.ndim != 2 or f.shape[0] != E.shape[0]:
+            raise TypeError("f, G must both be (ntypes, nknots_d) and E, P both (ntypes, nknots_e)")
+        ptr = lambda m: m.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        check(self._lib.nl_set_eam(self._h, int(f.shape[0]), int(f.shape[1]), float(r_min), float(r_max), ptr(f), ptr(G), int(E.shape[1]),
+                                   float(rho_max), ptr(E), ptr(P)), "nl_set_eam")
+
+    def clear_eam(self):
+        check(self._lib.nl_set_eam(self._h, 0, 0, 0.0, 0.0, None, None, 0, 0.0, None, None), "nl_set_eam")
+
+    def eam(self):
+        """``{"ntypes", "nknots_d", "r_min", "r_max", "nknots_e", "rho_max", "lds_density", "lds_forces"}`` of the tables set
+        (nl_get_eam), or None without them.  lds_*: the density pass, and the forces and totals, read their tables from LDS."""
+        nt, nd, ne, l1, l2 = (C.c_int32() for _ in range(5))
+        lo, hi, rm = C.c_double(), C.c_double(), C.c_double()
+        code = self._lib.nl_get_eam(self._h, C.byref(nt), C.byref(nd), C.byref(lo), C.byref(hi), C.byref(ne), C.byref(rm), C.byref(l1), C.byref(l2))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_eam")
+        return {"ntypes": nt.value, "nknots_d": nd.value, "r_min": lo.value, "r_max": hi.value, "nknots_e": ne.value, "rho_max": rm.value,
+                "lds_density": bool(l1.value), "lds_forces": bool(l2.value)}
+
+    def eam_forces(self, q, wait=True, out=None):
+        """Embedded-atom forces and per-particle energies (nl_eam_forces; ``wait=False``: nl_eam_forces_enqueue):
+        ``(n, 4) = {fx, fy, fz, pe_i}``, pe_i = half the pair energies of i + F(rho_i), so that ``pe.sum()`` is the energy.
+        Three passes over the list of the last build: densities, embedding, forces.  A density outside [0, rho_max] or a
+        pair below r_min gives NaN.  The first call allocates scratch: make it before a graph capture.  Whole builds only."""
+        return self._lj("nl_eam_forces", q, (), wait, out)
+
+    def eam_virial(self, q, wait=True, out=None):
+        """The totals that belong to eam_forces (nl_eam_virial; ``wait=False``: nl_eam_virial_enqueue):
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, U the pair energies plus every F(rho_i).  Bit for bit reproducible
+        after a full-list build; after a half-list build the densities are summed by atomics and the totals follow them."""
+        return self._lj("nl_eam_virial", q, (), wait, out)
+
+    def eam_density(self):
+        """``(rho, fp)``: rho_i and F'(rho_i) of the last eam_forces / eam_virial call (nl_eam_get_density), copies of
+        ``(n,)`` in the list's dtype, taken on the current stream."""
+        rho, fp, n = C.c_void_p(), C.c_void_p(), C.c_int32()
+        check(self._lib.nl_eam_get_density(self._h, C.byref(rho), C.byref(fp), C.byref(n)), "nl_eam_get_density")
+        ts = "<f4" if self.dtype == torch.float32 else "<f8"
+        return tuple(_as_tensor(p.value, (n.value,), ts, self, self.device).clone() for p in (rho, fp))
+
     def _ntypes(self):
         """ntypes of the handle's type table (nl_get_types; NL_ERR_STATE without one)."""
         ptr, n, nt = C.c_void_p(), C.c_int32(), C.c_int32()
