@@ -251,19 +251,22 @@ struct nl_handle_s {
   double lj_rcf[NL_MAX_TYPES * NL_MAX_TYPES] = {};  // rc_force_ab, [lj_ntypes][lj_ntypes]
   DevBuf<double> vir_part;         // nl_lj_virial (nl_virial.inc): [NL_VIRIAL_BLOCKS][8] block partials, allocated by the first call
 
-  // nl_set_pair_table (nl_table.inc): a tabulated pair potential, linear in r^2 between uniform knots
-  DevBuf<void> tb_tab;             // [nslots][tb_nknots] knots {F, dF, U, dU} in T; items = its bytes (kept across sets that fit)
-  int32_t tb_ntypes = 0, tb_nknots = 0;  // tb_nknots == 0: no table
-  double tb_rmin = 0, tb_rmax = 0;
-  double tb_x0 = 0, tb_xc = 0, tb_iD = 0;  // r_min^2, r_max^2 and 1 / D in double (rounded to T at the launches)
-  int tb_lds_env = 1;              // NL_TABLE_LDS=0 when the table was set: the kernels read it from global memory (tests, same-box A/B)
-
-  // nl_set_eam (nl_eam.inc): the density and embedding tables of an embedded-atom potential; the pair part is tb_* above
-  DevBuf<void> ea_tab;             // [ea_ntypes][ea_nkd] density knots {G, dG, f, df}, then [ea_ntypes][ea_nke] embedding knots {E, dE, P, dP}, in T
-  int32_t ea_ntypes = 0, ea_nkd = 0, ea_nke = 0;  // ea_nkd == 0: no tables
-  double ea_rmin = 0, ea_rmax = 0, ea_rhomax = 0;
-  double ea_x0 = 0, ea_xc = 0, ea_iD = 0, ea_iDrho = 0;  // r_min_d^2, r_max_d^2, 1 / D and 1 / Drho in double (rounded to T at the launches)
-  int ea_lds_env = 1;              // NL_TABLE_LDS=0 when the tables were set (as tb_lds_env)
+  // A table on a grid uniform in r^2 (nl_table.inc): its knots on the device and its scalars in double (rounded to T at the
+  // launches, table_view).
+  struct TableSet {
+    DevBuf<void> tab;                // [nslots][nknots] knots {V, dV, W, dW} in T; items = its bytes (kept across sets that fit)
+    int32_t ntypes = 0, nslots = 0, nknots = 0;  // nknots == 0: not set
+    double r_min = 0, r_max = 0;
+    double x0 = 0, xc = 0, iD = 0;   // r_min^2, r_max^2 and 1 / D
+    int lds_env = 1;                 // NL_TABLE_LDS=0 when it was set: the kernels read it from global memory (tests, same-box A/B)
+  };
+  // nl_set_pair_table: a tabulated pair potential, {F, dF, U, dU}, a slot per unordered pair of types
+  TableSet tb;
+  // nl_set_eam (nl_eam.inc): the density table of an embedded-atom potential, {G, dG, f, df}, a slot per type, and behind it
+  // in ea.tab [ea.ntypes][ea_nke] embedding knots {E, dE, P, dP} on their own grid, uniform in rho; the pair part is tb
+  TableSet ea;
+  int32_t ea_nke = 0;
+  double ea_rhomax = 0, ea_iDrho = 0;  // rho_max and 1 / Drho
   DevBuf<void> ea_part;            // [3][n_max] rho, fp = F'(rho), Fe = F(rho) of the last EAM call in T, allocated by the first call
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
@@ -305,6 +308,8 @@ template <typename F> int dispatch_t_off(nl_handle_t h, F&& f) {
   if (h->plan.wide) return f32 ? f(float(), int64_t()) : f(double(), int64_t());
   return f32 ? f(float(), int32_t()) : f(double(), int32_t());
 }
+// f(std::true_type or std::false_type) by v
+template <typename F> void with_flag(bool v, F&& f) { v ? f(std::true_type()) : f(std::false_type()); }
 
 // What every consumer of the list needs first (nl_lj_forces*, nl_pair_vectors*).  Synchronous: the list must be complete
 // (and its build must have succeeded).  enqueue: stream-ordered behind the build instead -- a build, or one the host has

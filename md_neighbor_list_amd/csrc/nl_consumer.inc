@@ -5,9 +5,11 @@
 //   half list: every pair once, the reaction goes to f[j] with floating-point atomics.
 // nl_lj_forces takes one epsilon, sigma and rc_force; nl_lj_forces_typed takes them per pair of types (nl_types.inc sets the
 // tables).  One kernel body (lj_row) and one launch serve both.
-// What the totals of nl_virial.inc share with the forces is written once, here (DESIGN.md section 8l): the arguments of a
-// launch (LjArgs, lj_args), the walk of a row up to the pair's values (lj_row_pairs over lj_image and lj_pair), and what
-// an entry point checks before its launch (lj_call).  Included at the end of nl_api.hip.
+// What the consumers of the list share is written once, here (DESIGN.md sections 8l, 8q): the arguments of a launch (LjArgs,
+// lj_args), the walk of a row up to the pair's values (lj_row_pairs over lj_image and lj_pair), the rows of a persistent grid
+// (grid_rows), a particle's type and a pair's slot (type_of, pair_slot), the launch of a kernel family over the rows
+// (rows_launch; totals_launch in nl_virial.inc), first-call scratch, what the list guarantees (list_reach) and what an entry
+// point does before its launch (consumer_call; lj_call and pair_call over it).  Included at the end of nl_api.hip.
 
 namespace {
 
@@ -200,12 +202,30 @@ __device__ __forceinline__ void lj_row_at(const LjArgs<T, OFF>& a, const PAR& p,
   }
 }
 
-// one block per 4 rows (k_lj*); the persistent grid of the tabulated forces walks lj_row_at itself (nl_table.inc)
+// one block per 4 rows (k_lj*); the persistent grids walk lj_row_at themselves (grid_rows)
 template <typename T, bool HALF, typename OFF, bool TRI, typename PAR>
 __device__ __forceinline__ void lj_row(const LjArgs<T, OFF>& a, const PAR& p, T* __restrict__ f) {
   const int32_t row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (row >= a.n) return;
   lj_row_at<T, HALF, OFF, TRI>(a, p, f, row, lane);
+}
+
+// The rows of a persistent grid of 4-wave blocks (the totals, the histogram, the tabulated and the EAM kernels): wave w of
+// block b takes the rows 4 b + w, + 4 gridDim, ... below n; on_row(row, lane).
+template <typename F> __device__ __forceinline__ void grid_rows(int32_t n, F&& on_row) {
+  const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int32_t row = (int32_t)blockIdx.x * 4 + wave; row < n; row += (int32_t)gridDim.x * 4) on_row(row, lane);
+}
+
+// A particle's type as an index below ntypes (types == nullptr: everybody is type 0), and the triangular slot of an
+// unordered pair of types (slot(a, b) of nl_pair_histogram_typed).  k_type_check: types < ntypes; the min keeps the slot
+// inside its table whatever the type table holds.
+__device__ __forceinline__ int32_t type_of(const int32_t* types, int32_t i, int32_t ntypes) {
+  return types ? min(types[i] & (NL_MAX_TYPES - 1), ntypes - 1) : 0;
+}
+__device__ __forceinline__ int32_t pair_slot(int32_t ti, int32_t tj, int32_t ntypes) {
+  const int32_t lo = min(ti, tj), hi = max(ti, tj);
+  return lo * (2 * ntypes - lo + 1) / 2 + (hi - lo);
 }
 
 template <typename T, bool HALF, typename OFF, bool TRI>
@@ -217,17 +237,20 @@ __global__ void __launch_bounds__(256) k_lj_typed(LjArgs<T, OFF> a, LjByType<T> 
   lj_row<T, HALF, OFF, TRI>(a, p, f);
 }
 
-// Zeroes the forces in front of a half list's atomics.  A kernel, not hipMemsetAsync: captured into a graph behind other work
+// Zeroes what a half list's atomics add to.  A kernel, not hipMemsetAsync: captured into a graph behind other work
 // on the buffer (torch.cuda.graph; a fill of f in front of the replay), the memset node zeroed only some of every four words
 // from the second replay on -- with the parent's library as with this one, eagerly never -- and the forces kept what was there.
 template <typename T> __global__ void __launch_bounds__(256) k_lj_zero(T* __restrict__ f, size_t count) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) f[i] = (T)0;
 }
+template <typename T> void zero_async(T* ptr, size_t count, hipStream_t s) {
+  hipLaunchKernelGGL((k_lj_zero<T>), dim3((unsigned)std::min<size_t>((count + 255) / 256, 8192)), dim3(256), 0, s, ptr, count);
+}
 
-// The arguments of a launch over the handle's list (lj_launch, virial_launch).  Box lengths for the minimum image on the
-// axes of the list's build; 0 = open axis (the reference's distances, neighlist_cpu.hpp:219-223).  The box and the mask
-// are the build's (BuildPlan::box, BuildPlan::pbc), not what nl_set_box or nl_set_periodic_axes may have set since; the
-// launches take the triclinic instances where that box has a tilt (BuildPlan::tilt).
+// The arguments of a launch over the handle's list (rows_launch, totals_launch, hist_launch).  Box lengths for the minimum
+// image on the axes of the list's build; 0 = open axis (the reference's distances, neighlist_cpu.hpp:219-223).  The box and
+// the mask are the build's (BuildPlan::box, BuildPlan::pbc), not what nl_set_box or nl_set_periodic_axes may have set since;
+// the launches take the triclinic instances where that box has a tilt (BuildPlan::tilt).
 // lj_scalars, lj_by_type: the parameters of a launch, the scalars rounded to T once.
 template <typename T, typename OFF> LjArgs<T, OFF> lj_args(nl_handle_t h, const void* q_dev, int32_t stride, const uint32_t* status) {
   const Box& b = h->plan.box;
@@ -238,34 +261,72 @@ template <typename T, typename OFF> LjArgs<T, OFF> lj_args(nl_handle_t h, const 
 template <typename T> LjScalars<T> lj_scalars(const double* lj) { return {(T)(4.0 * lj[0]), (T)(lj[1] * lj[1]), (T)(lj[2] * lj[2])}; }
 template <typename T> LjByType<T> lj_by_type(nl_handle_t h) { return {h->ty_types, static_cast<const T*>(h->lj_par)}; }
 
-// lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables.
-int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, void* f_dev, hipStream_t s, const uint32_t* status) {
+// The instance of a launch: the position and offset types of the build, half list, triclinic box.
+template <typename T_, typename OFF_, bool HALF, bool TRI> struct Inst {
+  using T = T_;
+  using OFF = OFF_;
+  static constexpr bool half = HALF, tri = TRI;
+};
+
+// A launch that leaves per_row values of T per row of the list in out_dev (forces: 4; the EAM densities: 1): nothing for an
+// empty list; the arguments; zeroes in front of a half list's atomics; body(Inst, LjArgs, out) launches the family's kernels;
+// the launch check.
+template <typename BODY>
+int rows_launch(nl_handle_t h, const void* q_dev, int32_t stride, void* out_dev, int32_t per_row, hipStream_t s, const uint32_t* status,
+                BODY&& body) {
   const int32_t n = h->n_rows;
   if (n == 0) return NL_OK;
   return dispatch_t_off(h, [&](auto t, auto off) -> int {
     using T = decltype(t);
     using OFF = decltype(off);
-    const int32_t nbw = (int32_t)(((int64_t)n * 64 + 255) / 256);
     const LjArgs<T, OFF> a = lj_args<T, OFF>(h, q_dev, stride, status);
-    T* f = static_cast<T*>(f_dev);
-    auto launch = [&](auto half, auto tri) {
-      constexpr bool H = decltype(half)::value, R = decltype(tri)::value;
-      if (lj) hipLaunchKernelGGL((k_lj<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, a, lj_scalars<T>(lj), f);
-      else hipLaunchKernelGGL((k_lj_typed<T, H, OFF, R>), dim3(nbw), dim3(256), 0, s, a, lj_by_type<T>(h), f);
-    };
-    if (!h->plan.full) {
-      const size_t count = 4 * (size_t)n;
-      hipLaunchKernelGGL((k_lj_zero<T>), dim3((unsigned)std::min<size_t>((count + 255) / 256, 8192)), dim3(256), 0, s, f, count);
-    }
-    if (h->plan.tilt) h->plan.full ? launch(std::false_type(), std::true_type()) : launch(std::true_type(), std::true_type());
-    else h->plan.full ? launch(std::false_type(), std::false_type()) : launch(std::true_type(), std::false_type());
+    T* out = static_cast<T*>(out_dev);
+    if (!h->plan.full) zero_async(out, (size_t)per_row * (size_t)n, s);
+    with_flag(!h->plan.full, [&](auto half) {
+      with_flag(h->plan.tilt, [&](auto tri) { body(Inst<T, OFF, decltype(half)::value, decltype(tri)::value>(), a, out); });
+    });
     HIPCHK(h, hipGetLastError());
     return NL_OK;
   });
 }
 
+// lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables.
+int lj_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, void* f_dev, hipStream_t s, const uint32_t* status) {
+  const int32_t nbw = (int32_t)(((int64_t)h->n_rows * 64 + 255) / 256);
+  return rows_launch(h, q_dev, stride, f_dev, 4, s, status, [&](auto i, const auto& a, auto* f) {
+    using I = decltype(i);
+    using T = typename I::T;
+    if (lj) hipLaunchKernelGGL((k_lj<T, I::half, typename I::OFF, I::tri>), dim3(nbw), dim3(256), 0, s, a, lj_scalars<T>(lj), f);
+    else hipLaunchKernelGGL((k_lj_typed<T, I::half, typename I::OFF, I::tri>), dim3(nbw), dim3(256), 0, s, a, lj_by_type<T>(h), f);
+  });
+}
+
+// First-call scratch of a consumer (vir_part, ea_part): allocated by the first call that needs it, which a stream that is
+// being captured cannot do.
+template <typename B> int first_call_scratch(nl_handle_t h, DevBuf<B>& b, size_t bytes, hipStream_t s) {
+  if (b) return NL_OK;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHK(h, hipStreamIsCapturing(s, &cap));
+  if (cap != hipStreamCaptureStatusNone) return fail(h, NL_ERR_STATE);
+  return side_alloc(h, b, bytes);
+}
+
+// What the list guarantees: every pair within the smallest cut-off it was built with -- rc, and with a type table the rc_ab.
+// skip_zero: a pair of types with rc_ab = 0 has no entries and asks for nothing (tables, typed histogram); otherwise it counts,
+// and nothing is within it (untyped histogram).  A list that may be reused holds this less the skin.
+double list_reach(nl_handle_t h, bool skip_zero) {
+  double lim = h->rc;
+  if (h->ty_types) {
+    const int32_t nt = h->ty_ntypes;
+    for (int32_t k = 0; k < nt * nt; k++)
+      if (!skip_zero || h->ty_rc[k] > 0.0) lim = std::min(lim, h->ty_rc[k]);
+  }
+  return lim;
+}
+
 // The typed forces' preconditions beyond the untyped ones: a type table and parameters of its ntypes, and rc_force_ab
-// within rc_ab (less the skin for the enqueue variant, whose list may be reused).
+// within rc_ab (less the skin for the enqueue variant, whose list may be reused) -- pair of types by pair of types, which
+// list_reach's one figure cannot say.
 int lj_typed_check(nl_handle_t h, double skin) {
   if (!h->ty_types || !h->lj_par) return fail(h, NL_ERR_STATE);
   if (h->lj_ntypes != h->ty_ntypes) return fail(h, NL_ERR_ARG);
@@ -277,22 +338,18 @@ int lj_typed_check(nl_handle_t h, double skin) {
   return NL_OK;
 }
 
-// The eight entry points (nl_lj_forces, nl_lj_virial, each _typed and _enqueue): the checks, then launch(...).
-//   the arguments (NL_ERR_ARG, a null handle included);
-//   synchronous: consumer_ready, then the reach -- rc_force within the list's rc, or lj_typed_check;
-//   enqueue (no wait: stream-ordered behind the update, or completed build, whose list it reads): the reach less the skin
-//   (what a list reused within the skin guarantees) first, then consumer_ready; the kernel takes the build's status word.
-template <typename OUT>
-int lj_call(nl_handle_t h, const void* q_dev, int32_t q_stride, const double* lj, OUT* out_dev, void* stream, bool enqueue,
-            int (*launch)(nl_handle_t, const void*, int32_t, const double*, OUT*, hipStream_t, const uint32_t*),
-            int (*own_reach)(nl_handle_t, double) = nullptr) {
-  if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4) || (lj && (!(lj[2] > 0) || !(lj[1] > 0)))) return fail(h, NL_ERR_ARG);
+// What every entry point of a consumer does before its launch, and the launch (the Lennard-Jones, table, EAM and histogram
+// calls; nl_pair_vectors has an order of its own, pair_vectors_call):
+//   the arguments (NL_ERR_ARG, a null handle included); args_ok: the call's own;
+//   synchronous: consumer_ready, then reach(0.0), the call's own preconditions and what it needs of the list;
+//   enqueue (no wait: stream-ordered behind the update, or completed build, whose list it reads): reach(skin) first (what a
+//   list reused within the skin guarantees), then consumer_ready; the kernels take the build's status word;
+//   launch(stream, status).
+template <typename REACH, typename LAUNCH>
+int consumer_call(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* out_dev, bool args_ok, void* stream, bool enqueue,
+                  REACH&& reach, LAUNCH&& launch) {
+  if (!h || !q_dev || !out_dev || (q_stride != 3 && q_stride != 4) || !args_ok) return fail(h, NL_ERR_ARG);
   const hipStream_t s = (hipStream_t)stream;
-  const auto reach = [&](double skin) -> int {
-    if (own_reach) return own_reach(h, skin);  // (another pair function's: table_reach of nl_table.inc)
-    if (!lj) return lj_typed_check(h, skin);
-    return lj[2] <= h->rc - skin ? NL_OK : fail(h, NL_ERR_ARG);  // the list does not reach that far (rc - 0.0 is rc, exactly)
-  };
   if (enqueue) {
     if (int rc = reach(h->skin)) return rc;
     if (int rc = consumer_ready(h, s, true)) return rc;
@@ -301,7 +358,28 @@ int lj_call(nl_handle_t h, const void* q_dev, int32_t q_stride, const double* lj
     if (int rc = reach(0.0)) return rc;
   }
   HIPCHK(h, hipSetDevice(h->device));
-  return launch(h, q_dev, q_stride, lj, out_dev, s, enqueue ? h->status : nullptr);
+  return launch(s, enqueue ? h->status : nullptr);
+}
+
+// The eight Lennard-Jones entry points (nl_lj_forces, nl_lj_virial, each _typed and _enqueue).  The reach: rc_force within
+// the list's rc, or lj_typed_check.
+template <typename OUT>
+int lj_call(nl_handle_t h, const void* q_dev, int32_t q_stride, const double* lj, OUT* out_dev, void* stream, bool enqueue,
+            int (*launch)(nl_handle_t, const void*, int32_t, const double*, OUT*, hipStream_t, const uint32_t*)) {
+  return consumer_call(
+      h, q_dev, q_stride, out_dev, !lj || (lj[2] > 0 && lj[1] > 0), stream, enqueue,
+      [&](double skin) -> int {
+        if (!lj) return lj_typed_check(h, skin);
+        return lj[2] <= h->rc - skin ? NL_OK : fail(h, NL_ERR_ARG);  // the list does not reach that far (rc - 0.0 is rc, exactly)
+      },
+      [&](hipStream_t s, const uint32_t* status) { return launch(h, q_dev, q_stride, lj, out_dev, s, status); });
+}
+// ... and those of another pair function (nl_table_*, nl_eam_*), with its own reach.
+template <typename OUT>
+int pair_call(nl_handle_t h, const void* q_dev, int32_t q_stride, OUT* out_dev, void* stream, bool enqueue,
+              int (*launch)(nl_handle_t, const void*, int32_t, OUT*, hipStream_t, const uint32_t*), int (*reach)(nl_handle_t, double)) {
+  return consumer_call(h, q_dev, q_stride, out_dev, true, stream, enqueue, [&](double skin) { return reach(h, skin); },
+                       [&](hipStream_t s, const uint32_t* status) { return launch(h, q_dev, q_stride, out_dev, s, status); });
 }
 
 }  // namespace

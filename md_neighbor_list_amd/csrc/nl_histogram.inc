@@ -2,8 +2,8 @@
 // one histogram for everybody (nl_pair_histogram) or one per unordered pair of types (nl_pair_histogram_typed), added to
 // uint64 counters of the caller on the device.  The rule is stated at nl_pair_histogram in include/nl_hip.h.
 // A third consumer on the shared walk of section 8l: the rows and the separations are lj_row_pairs' (lj_image; the values
-// of lj_pair are ignored and the compiler drops them), the entry checks are consumer_ready's in lj_call's two orders
-// (hist_call: lj_call itself asks for Lennard-Jones parameters, which a histogram has none of).
+// of lj_pair are ignored and the compiler drops them), a particle's type and a pair's slot are type_of and pair_slot, the entry
+// path is consumer_call's with the histogram's own arguments and reach over list_reach (hist_call; DESIGN.md section 8q).
 // Integer counters only: the answer is exact, the same for a half and a full build bit for bit, and the same every call.
 // Included at the end of nl_api.hip, behind nl_virial.inc.
 
@@ -62,9 +62,9 @@ __device__ __forceinline__ void pair_hist_rows(const LjArgs<T, OFF>& a, const Hi
   const float scale = (float)((double)nbins / g.r_max);
   const bool live = !(a.status && *a.status != 0u);  // (uniform over the launch)
   const LjScalars<T> none = {(T)0, (T)0, (T)0};
+  if constexpr (TYPED) __builtin_assume(g.types != nullptr);  // (type_of asks; a typed launch has the table)
   for (int32_t row = (int32_t)blockIdx.x * 4 + wave; live && row < a.n; row += (int32_t)gridDim.x * 4) {
-    int32_t ti = 0;
-    if constexpr (TYPED) ti = min(g.types[row] & (NL_MAX_TYPES - 1), g.ntypes - 1);  // (k_type_check: types < ntypes; the min keeps the slot inside hist whatever the table holds)
+    const int32_t ti = TYPED ? type_of(g.types, row, g.ntypes) : 0;
     lj_row_pairs<T, OFF, TRI>(a, none, row, lane, [&](int32_t j, LjPartner w, T dx, T dy, T dz, T, T, T, T, bool) {
       // a pair stored twice counts once: a full list's in the row of the smaller id, one that crosses a cut of a local-id
       // slab build (both ranks store it, half or full) on the rank LjPartner::first names
@@ -74,12 +74,7 @@ __device__ __forceinline__ void pair_hist_rows(const LjArgs<T, OFF>& a, const Hi
       int32_t b = min((int32_t)(sqrtf((float)r2) * scale), nbins - 1);
       while (b > 0 && r2 < edge[b - 1]) b--;
       while (r2 >= edge[b]) b++;
-      int32_t slot = 0;
-      if constexpr (TYPED) {
-        const int32_t tj = min(g.types[j] & (NL_MAX_TYPES - 1), g.ntypes - 1);
-        const int32_t lo = min(ti, tj), hi = max(ti, tj);
-        slot = lo * (2 * g.ntypes - lo + 1) / 2 + (hi - lo);
-      }
+      const int32_t slot = TYPED ? pair_slot(ti, type_of(g.types, j, g.ntypes), g.ntypes) : 0;
       const int32_t at = slot * nbins + b;
       if constexpr (LDS) atomicAdd(&cnt[at], 1ull);
       else atomicAdd(&g.hist[at], 1ull);
@@ -123,7 +118,7 @@ int hist_launch(nl_handle_t h, const void* q_dev, int32_t stride, double r_max, 
       else if (typed) hipLaunchKernelGGL((k_pair_hist_typed<T, OFF, R, false>), dim3(nblk), dim3(STAGE_THREADS), bytes, s, a, g);
       else hipLaunchKernelGGL((k_pair_hist<T, OFF, R>), dim3(nblk), dim3(STAGE_THREADS), bytes, s, a, g);
     };
-    h->plan.tilt ? launch(std::true_type()) : launch(std::false_type());
+    with_flag(h->plan.tilt, launch);
     HIPCHK(h, hipGetLastError());
     return NL_OK;
   });
@@ -134,31 +129,16 @@ int hist_launch(nl_handle_t h, const void* q_dev, int32_t stride, double r_max, 
 // list at all: refused).  Typed: every rc_ab > 0; a pair with rc_ab = 0 has no entries and its slot stays as it was.
 int hist_reach(nl_handle_t h, double r_max, bool typed, double skin) {
   if (typed && !h->ty_types) return fail(h, NL_ERR_STATE);
-  double lim = h->rc;
-  if (h->ty_types) {
-    const int32_t nt = h->ty_ntypes;
-    for (int32_t k = 0; k < nt * nt; k++)
-      if (!typed || h->ty_rc[k] > 0.0) lim = std::min(lim, h->ty_rc[k]);
-  }
-  return r_max <= lim - skin ? NL_OK : fail(h, NL_ERR_ARG);
+  return r_max <= list_reach(h, typed) - skin ? NL_OK : fail(h, NL_ERR_ARG);
 }
 
-// The four entry points: lj_call's checks in lj_call's two orders, with the histogram's arguments and reach.
+// The four entry points: consumer_call with the histogram's arguments and reach.
 int hist_call(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, int32_t nbins, uint64_t* hist_dev, void* stream,
               bool enqueue, bool typed) {
-  if (!h || !q_dev || !hist_dev || (q_stride != 3 && q_stride != 4) || !(r_max > 0) || !std::isfinite(r_max) || nbins < 1 ||
-      nbins > NL_HIST_MAX_BINS)
-    return fail(h, NL_ERR_ARG);
-  const hipStream_t s = (hipStream_t)stream;
-  if (enqueue) {
-    if (int rc = hist_reach(h, r_max, typed, h->skin)) return rc;
-    if (int rc = consumer_ready(h, s, true)) return rc;
-  } else {
-    if (int rc = consumer_ready(h, s, false)) return rc;
-    if (int rc = hist_reach(h, r_max, typed, 0.0)) return rc;
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  return hist_launch(h, q_dev, q_stride, r_max, nbins, typed, hist_dev, s, enqueue ? h->status : nullptr);
+  return consumer_call(
+      h, q_dev, q_stride, hist_dev, r_max > 0 && std::isfinite(r_max) && nbins >= 1 && nbins <= NL_HIST_MAX_BINS, stream, enqueue,
+      [&](double skin) { return hist_reach(h, r_max, typed, skin); },
+      [&](hipStream_t s, const uint32_t* status) { return hist_launch(h, q_dev, q_stride, r_max, nbins, typed, hist_dev, s, status); });
 }
 
 }  // namespace

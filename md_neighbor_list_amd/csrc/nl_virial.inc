@@ -2,11 +2,12 @@
 // the potential energy U and the number of pairs within rc_force, over the entries of the last build's list.  The pair's
 // values come from the walk that gives nl_lj_forces its pairs (lj_row_pairs of nl_consumer.inc: lj_image + lj_pair), so
 // the totals belong to those forces; the rule is stated at nl_lj_virial in include/nl_hip.h.  The launch arguments
-// (lj_args) and the entry points' checks (lj_call) are the forces' too.  No entry scatters anything (a stored pair
+// (lj_args) and the entry points' checks (lj_call over consumer_call) are the forces' too; the launch of the totals
+// (totals_launch) and the tree over a block (block_tree) are written here for every pair function (DESIGN.md section 8q).  No entry scatters anything (a stored pair
 // contributes once, in the row that stores it), so the half list needs no atomics, and nothing here is a floating-point
 // atomic: every sum has one fixed order,
 //   lane: its entries, row after row      wave: the butterfly of wave_sum      block: waves 0, 1, 2, 3
-//   k_virial_reduce: thread t the partials t, t + 256, ...; then a tree over the 256 threads
+//   k_virial_reduce: thread t the partials t, t + 256, ...; then block_tree over the 256 threads
 // and two calls on the same list and positions give the same 64 bytes.
 // Included at the end of nl_api.hip, behind nl_consumer.inc.
 
@@ -63,62 +64,59 @@ __global__ void __launch_bounds__(STAGE_THREADS) k_lj_virial_typed(LjArgs<T, OFF
   lj_virial_rows<T, OFF, TRI>(a, p, ghost_w, part);
 }
 
-// One block: thread t adds the partials t, t + 256, ... in that order, then a tree over the threads.  scale: 1 after a
-// half build, 1/2 after a full one, whose list holds every pair twice (exact).  A failed list gives 8 NaN.
+// The sum of a block in one fixed order (k_virial_reduce, k_eam_fe_part): every thread brings the C sums of
+// its own strided walk, then a tree over the threads; the block's sums are sm[c][0] of what it returns.
+template <int C> __device__ __forceinline__ auto& block_tree(const double (&s)[C]) {
+  __shared__ double sm[C][STAGE_THREADS];
+  const int32_t t = threadIdx.x;
+#pragma unroll
+  for (int c = 0; c < C; c++) sm[c][t] = s[c];
+  __syncthreads();
+  for (int32_t d = STAGE_THREADS / 2; d > 0; d >>= 1) {
+    if (t < d) {
+#pragma unroll
+      for (int c = 0; c < C; c++) sm[c][t] += sm[c][t + d];
+    }
+    __syncthreads();
+  }
+  return sm;
+}
+
+// One block: thread t adds the partials t, t + 256, ... in that order, then block_tree.  scale: 1 after a half build, 1/2
+// after a full one, whose list holds every pair twice (exact).  A failed list gives 8 NaN.
 __global__ void __launch_bounds__(STAGE_THREADS) k_virial_reduce(const double* __restrict__ part, int32_t nblk, double scale,
                                                                  double* __restrict__ out, const uint32_t* __restrict__ status) {
-  __shared__ double sm[VIR_OUT][STAGE_THREADS];
   const int32_t t = threadIdx.x;
   double s[VIR_OUT] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int32_t b = t; b < nblk; b += STAGE_THREADS) {
 #pragma unroll
     for (int c = 0; c < VIR_OUT; c++) s[c] += part[(size_t)b * VIR_OUT + c];
   }
-#pragma unroll
-  for (int c = 0; c < VIR_OUT; c++) sm[c][t] = s[c];
-  __syncthreads();
-  for (int32_t d = STAGE_THREADS / 2; d > 0; d >>= 1) {
-    if (t < d) {
-#pragma unroll
-      for (int c = 0; c < VIR_OUT; c++) sm[c][t] += sm[c][t + d];
-    }
-    __syncthreads();
-  }
+  const auto& sm = block_tree(s);
   if (t < VIR_OUT) out[t] = (status && *status != 0u) ? (double)NAN : scale * sm[t][0];
 }
 
-// vir_part, allocated by the first call of any of the totals (nl_lj_virial*, nl_table_virial*): a stream that is being
-// captured cannot allocate.
-int virial_scratch(nl_handle_t h, hipStream_t s) {
-  if (h->vir_part) return NL_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIPCHK(h, hipStreamIsCapturing(s, &cap));
-  if (cap != hipStreamCaptureStatusNone) return fail(h, NL_ERR_STATE);
-  return side_alloc(h, h->vir_part, sizeof(double) * VIR_OUT * VIR_BLOCKS);
-}
-
-// lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables (as lj_launch).
-int virial_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, double* out_dev, hipStream_t s,
-                  const uint32_t* status) {
+// A launch of the 8 totals into out_dev (the Lennard-Jones, table and EAM totals): zeroes for an empty list; vir_part; the
+// arguments; body(Inst, LjArgs, nblk, part) launches the family's kernel on nblk <= max_blocks blocks, which leave their
+// partials in part, and returns a status; k_virial_reduce.
+template <typename BODY>
+int totals_launch(nl_handle_t h, const void* q_dev, int32_t stride, double* out_dev, hipStream_t s, const uint32_t* status, int32_t max_blocks,
+                  BODY&& body) {
   const int32_t n = h->n_rows;
   if (n == 0) {
     HIPCHK(h, hipMemsetAsync(out_dev, 0, sizeof(double) * VIR_OUT, s));
     return NL_OK;
   }
-  if (int rc = virial_scratch(h, s)) return rc;
-  const int32_t nblk = (int32_t)std::min<int64_t>(((int64_t)n + 3) / 4, VIR_BLOCKS);
+  if (int rc = first_call_scratch(h, h->vir_part, sizeof(double) * VIR_OUT * VIR_BLOCKS, s)) return rc;
+  const int32_t nblk = (int32_t)std::min<int64_t>(((int64_t)n + 3) / 4, max_blocks);
   double* part = h->vir_part;
-  const double ghost_w = h->plan.full ? 1.0 : 0.5;
   const int rc = dispatch_t_off(h, [&](auto t, auto off) -> int {
     using T = decltype(t);
     using OFF = decltype(off);
     const LjArgs<T, OFF> a = lj_args<T, OFF>(h, q_dev, stride, status);
-    auto launch = [&](auto tri) {
-      constexpr bool R = decltype(tri)::value;
-      if (lj) hipLaunchKernelGGL((k_lj_virial<T, OFF, R>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_scalars<T>(lj), ghost_w, part);
-      else hipLaunchKernelGGL((k_lj_virial_typed<T, OFF, R>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_by_type<T>(h), ghost_w, part);
-    };
-    h->plan.tilt ? launch(std::true_type()) : launch(std::false_type());
+    int rb = NL_OK;
+    with_flag(h->plan.tilt, [&](auto tri) { rb = body(Inst<T, OFF, false, decltype(tri)::value>(), a, nblk, part); });
+    if (rb) return rb;
     HIPCHK(h, hipGetLastError());
     return NL_OK;
   });
@@ -126,6 +124,19 @@ int virial_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double
   hipLaunchKernelGGL(k_virial_reduce, dim3(1), dim3(STAGE_THREADS), 0, s, part, nblk, h->plan.full ? 0.5 : 1.0, out_dev, status);
   HIPCHK(h, hipGetLastError());
   return NL_OK;
+}
+
+// lj: {epsilon, sigma, rc_force} of the launch; nullptr: by type, from the handle's tables (as lj_launch).
+int virial_launch(nl_handle_t h, const void* q_dev, int32_t stride, const double* lj, double* out_dev, hipStream_t s,
+                  const uint32_t* status) {
+  const double ghost_w = h->plan.full ? 1.0 : 0.5;
+  return totals_launch(h, q_dev, stride, out_dev, s, status, VIR_BLOCKS, [&](auto i, const auto& a, int32_t nblk, double* part) {
+    using I = decltype(i);
+    using T = typename I::T;
+    if (lj) hipLaunchKernelGGL((k_lj_virial<T, typename I::OFF, I::tri>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_scalars<T>(lj), ghost_w, part);
+    else hipLaunchKernelGGL((k_lj_virial_typed<T, typename I::OFF, I::tri>), dim3(nblk), dim3(STAGE_THREADS), 0, s, a, lj_by_type<T>(h), ghost_w, part);
+    return NL_OK;
+  });
 }
 
 }  // namespace

@@ -516,6 +516,25 @@ def test_a_zero_embedding_is_the_pair_table(kind, dtype):
 
 @gpu
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("box", ["xyz", "tilt"])
+def test_the_density_is_a_table_energy(box, dtype):
+    """Every table is read through one knot and one read.  One type, and the pair table's U := the density
+    table's f on the same r_min, r_max and knots: on one full list rho_i is 2 pe_i of table_forces bit for bit -- the same walk,
+    lane order and wave sum, and every term of pe_i is a term of rho_i halved, which is exact: f >= f(R_MAX) = 0.06 on the
+    whole table, so no term comes near the underflow of either dtype and no table scale is needed."""
+    tab = _tabs("one")[0]
+    assert tab.f.min() > 0.05 and (tab.r_min_d, tab.r_max_d, tab.f.shape[1]) == (tab.r_min, tab.r_max, tab.U.shape[1])
+    nl, qd = _built(_input(box, box == "tilt"), box, dtype, True, 3.4, "one")
+    nl.set_pair_table(tab.F[0], tab.f[0], tab.r_min, tab.r_max)
+    nl.eam_forces(qd)
+    rho = nl.eam_density()[0].cpu().numpy()
+    pe = nl.table_forces(qd)[:, 3].cpu().numpy()
+    assert rho.dtype == np.dtype(dtype) and rho.shape == (N,) and np.all(rho > 1.0)
+    assert rho.tobytes() == (2 * pe).tobytes()
+
+
+@gpu
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("full", [False, True])
 def test_a_zero_pair_table(full, dtype):
     box, drift, kind = "tilt", False, "three"

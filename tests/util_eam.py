@@ -7,7 +7,7 @@ import numpy as np
 
 from md_neighbor_list_amd import eam, pair_table
 from tests.util import emulate_pairs, lj_pairs
-from tests.util_table import _slots, table_device_form, table_virial_emulate
+from tests.util_table import _block_sum, _knot, _lin, _slots, _sum_rows, table_device_form, table_virial_emulate
 from tests.virial_util import _AB
 
 # 4 x the largest ratios of test_eam.test_emulation_gives_c, every one the larger of the fp32 and the fp64 emulation: forces and
@@ -158,51 +158,10 @@ def eam_energy(q, box6, mask, fns, r_max, types=None):
 
 
 # -------------------------------------------------------------------------------------------------------- emulation
-def _knot(r2, x0, xc, iD, nk, T):
-    """eam_knot of csrc/nl_eam.inc in T: (in, below, k, t)."""
-    inn = (r2 < xc) & (r2 > 0)
-    below = r2 < x0
-    s = (r2 - x0) * iD
-    ok = inn & ~below
-    k = np.where(ok, np.minimum(np.where(ok, s, T(0)).astype(np.int32), nk - 2), 0)
-    return inn, below, k, s - k.astype(T)
-
-
-def _lin(V, dV, sl, k, t, inn, below, T):
-    return np.where(inn, np.where(below, T(np.nan), V[sl, k] + t * dV[sl, k]), T(0))
-
-
-def _sum_rows(n, I, term, rng):
-    """Per particle the sum in term's type of its rows of term[m, c], in a random order (util_table.table_emulate's sum)."""
-    order = np.lexsort((rng.random(len(I)), I))
-    Is, term = I[order], term[order]
-    rank = np.arange(len(Is)) - np.searchsorted(Is, np.arange(n))[Is]
-    out = np.zeros((n, term.shape[1]), dtype=term.dtype)
-    for k in range(int(rank.max()) + 1 if len(rank) else 0):
-        sel = rank == k
-        out[Is[sel]] += term[sel]
-    return out
-
-
 def fe_sum_emulate(fe, nblk_max=512):
-    """k_eam_fe_part and k_eam_add_u: thread g of the grid adds Fe_g, Fe_{g + threads}, ... in double, a tree over the 256
-    threads of a block, thread t the partials t, t + 256, ..., a tree."""
-    n = len(fe)
-    nblk = min((n + 255) // 256, nblk_max)
-    acc = np.zeros(nblk * 256)
-    for i0 in range(0, n, nblk * 256):
-        chunk = fe[i0:i0 + nblk * 256].astype(np.float64)
-        acc[:len(chunk)] += chunk
-    acc = acc.reshape(nblk, 256)
-    while acc.shape[1] > 1:
-        acc = acc[:, :acc.shape[1] // 2] + acc[:, acc.shape[1] // 2:]
-    thr = np.zeros(256)
-    for b0 in range(0, nblk, 256):
-        part = acc[b0:b0 + 256, 0]
-        thr[:len(part)] += part
-    while len(thr) > 1:
-        thr = thr[:len(thr) // 2] + thr[len(thr) // 2:]
-    return thr[0]
+    """k_eam_fe_part and k_eam_add_u: the Fe_i in double over the grid of k_eam_fe_part, then the partials of its blocks, both by
+    util_table._block_sum."""
+    return _block_sum(_block_sum(fe.astype(np.float64), min((len(fe) + 255) // 256, nblk_max)))[0]
 
 
 DEFECTS = ("a pair dropped from the density", "f of the row's type", "fp_i for both ends", "Fe left out", "no reaction in rho")

@@ -131,6 +131,47 @@ def table_device_form(F, U, r_min, r_max, T):
     return tuple(v.astype(T) for v in (F, dF, U, dU)) + (T(float(r_min) ** 2), T(float(r_max) ** 2), T(1.0 / D))
 
 
+def _knot(r2, x0, xc, iD, nk, T):
+    """table_knot of csrc/nl_table.inc in T: (in, below, k, t)."""
+    inn = (r2 < xc) & (r2 > 0)
+    below = r2 < x0
+    s = (r2 - x0) * iD
+    ok = inn & ~below
+    k = np.where(ok, np.minimum(np.where(ok, s, T(0)).astype(np.int32), nk - 2), 0)
+    return inn, below, k, s - k.astype(T)
+
+
+def _lin(V, dV, sl, k, t, inn, below, T):
+    """table_read of csrc/nl_table.inc in T, on the knots k of the slots sl."""
+    return np.where(inn, np.where(below, T(np.nan), V[sl, k] + t * dV[sl, k]), T(0))
+
+
+def _sum_rows(n, I, term, rng):
+    """Per particle the sum in term's type of its rows of term[m, c], every particle's terms in a random order (tests.util
+    lj_emulate's sum)."""
+    order = np.lexsort((rng.random(len(I)), I))
+    Is, term = I[order], term[order]
+    rank = np.arange(len(Is)) - np.searchsorted(Is, np.arange(n))[Is]
+    out = np.zeros((n, term.shape[1]), dtype=term.dtype)
+    for k in range(int(rank.max()) + 1 if len(rank) else 0):
+        sel = rank == k
+        out[Is[sel]] += term[sel]
+    return out
+
+
+def _block_sum(v, nblk=1):
+    """block_sum of csrc/nl_virial.inc on a grid of nblk blocks of 256 threads, in double: thread g of the grid adds v[g],
+    v[g + 256 nblk], ... in that order, then a tree over the threads of each block.  Returns the nblk sums."""
+    acc = np.zeros(nblk * 256)
+    for i0 in range(0, len(v), nblk * 256):
+        chunk = v[i0:i0 + nblk * 256]
+        acc[:len(chunk)] += chunk
+    acc = acc.reshape(nblk, 256)
+    while acc.shape[1] > 1:
+        acc = acc[:, :acc.shape[1] // 2] + acc[:, acc.shape[1] // 2:]
+    return acc[:, 0]
+
+
 def table_emulate_pairs(q, box6, mask, F, U, r_min, r_max, T, pairs, types=None, knot_shift=0, use_t=True):
     """lj_image (tests.util emulate_pairs) and TableByPair::pair (csrc/nl_table.inc) in the position type T over the ordered
     pairs (I, J): one rounding per operation, no FMA.  Returns (dx, dy, dz, fx, fy, fz, pe, in) in T.  knot_shift, use_t: the
@@ -142,49 +183,32 @@ def table_emulate_pairs(q, box6, mask, F, U, r_min, r_max, T, pairs, types=None,
     nslots, nk = Ft.shape
     nt = int(round(((8 * nslots + 1) ** 0.5 - 1) / 2))
     sl = _slots(None if types is None else np.asarray(types, dtype=np.int64), nt, I, J)
-    r2 = dx * dx + dy * dy + dz * dz
-    inn = (r2 < xc) & (r2 > 0)
-    below = r2 < x0
-    s = (r2 - x0) * iD
-    ok = inn & ~below
-    k = np.where(ok, np.minimum(np.where(ok, s, T(0)).astype(np.int32), nk - 2), 0)
-    t = s - k.astype(T)
+    inn, below, k, t = _knot(dx * dx + dy * dy + dz * dz, x0, xc, iD, nk, T)
     k = np.clip(k + knot_shift, 0, nk - 2)
     if not use_t:
         t = np.zeros_like(t)
-    nan = T(np.nan)
-    fr = np.where(inn, np.where(below, nan, Ft[sl, k] + t * dFt[sl, k]), T(0))
-    pe = np.where(inn, np.where(below, nan, Ut[sl, k] + t * dUt[sl, k]), T(0))
+    fr, pe = _lin(Ft, dFt, sl, k, t, inn, below, T), _lin(Ut, dUt, sl, k, t, inn, below, T)
     out = (dx, dy, dz, fr * dx, fr * dy, fr * dz, pe, inn)
     assert all(v.dtype == np.dtype(T) for v in out[:7])
     return out
 
 
 def table_emulate(q, box6, mask, F, U, r_min, r_max, T, rng, pairs, types=None, **defect):
-    """The row body of k_table_forces over table_emulate_pairs' values, f = {fx, fy, fz, pe / 2} summed per particle in T,
-    every particle's terms in a random order (tests.util lj_emulate's sum).  Returns f[n, 4] in T."""
+    """The row body of k_table_forces over table_emulate_pairs' values, f = {fx, fy, fz, pe / 2} summed per particle in T
+    (_sum_rows).  Returns f[n, 4] in T."""
     T = np.dtype(T).type
-    n, I = len(q), pairs[0]
     _, _, _, fx, fy, fz, pe, _ = table_emulate_pairs(q, box6, mask, F, U, r_min, r_max, T, pairs, types=types, **defect)
     term = np.stack([fx, fy, fz, T(0.5) * pe], axis=1)
     assert term.dtype == np.dtype(T)
-    order = np.lexsort((rng.random(len(I)), I))
-    Is, term = I[order], term[order]
-    start = np.searchsorted(Is, np.arange(n))
-    rank = np.arange(len(Is)) - start[Is]
-    f = np.zeros((n, 4), dtype=T)
-    for k in range(int(rank.max()) + 1 if len(rank) else 0):
-        sel = rank == k
-        f[Is[sel]] += term[sel]
-    return f
+    return _sum_rows(len(q), pairs[0], term, rng)
 
 
 def table_virial_emulate(n, I, vals, rng, nblk=512):
     """k_table_virial and k_virial_reduce over table_emulate_pairs' values of the ordered pairs of a FULL list, with the
     kernels' own summation tree: the six products and the energy in T, converted to double; row i goes to wave i mod 4 nblk,
     its entries (in a random order) to the lanes in turn, every lane adds its terms one after the other; then the butterfly
-    of the wave, waves ((0 + 1) + 2) + 3, thread t the partials t, t + 256, a tree over the threads, and the factor 1/2 of a
-    full list.  Returns the 7 sums and n_in."""
+    of the wave, waves ((0 + 1) + 2) + 3, the partials of the blocks by _block_sum, and the factor 1/2 of a full list.
+    Returns the 7 sums and n_in."""
     dx, dy, dz, fx, fy, fz, pe, inn = vals
     terms = [fx * dx, fy * dy, fz * dz, fx * dy, fx * dz, fy * dz, pe]
     assert all(t.dtype == dx.dtype for t in terms)
@@ -201,10 +225,5 @@ def table_virial_emulate(n, I, vals, rng, nblk=512):
         while acc.shape[2] > 1:  # wave_sum
             acc = acc[:, :, :acc.shape[2] // 2] + acc[:, :, acc.shape[2] // 2:]
         part = ((acc[:, 0, 0] + acc[:, 1, 0]) + acc[:, 2, 0]) + acc[:, 3, 0]
-        thr = np.zeros(256)
-        for b0 in range(0, nblk, 256):  # thread t: the partials t, t + 256, ...
-            thr[:len(part[b0:b0 + 256])] += part[b0:b0 + 256]
-        while len(thr) > 1:
-            thr = thr[:len(thr) // 2] + thr[len(thr) // 2:]
-        out[c] = 0.5 * thr[0]
+        out[c] = 0.5 * _block_sum(part)[0]
     return np.concatenate([out, [0.5 * inn.sum()]])
