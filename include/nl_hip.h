@@ -734,6 +734,85 @@ int nl_eam_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* ou
 int nl_eam_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 int nl_eam_get_density(nl_handle_t h, const void** rho_dev, const void** fp_dev, int32_t* n);
 
+/* Stillinger-Weber three-body potentials (LAMMPS pair_style sw, HOOMD md.many_body.SW: silicon, germanium, mW water, CdTe, GaN,
+ * SiC): forces, per-particle energies and the 8 totals of
+ *   E = sum_pairs phi(r) + sum_i sum_{j<k} Lambda[t_i][t_j][t_k] (cos theta_jik - c0[t_i][t_j][t_k])^2 g_{t_i t_j}(r_ij) g_{t_i t_k}(r_ik),
+ * j, k the partners of the centre i in the list.  The rule, for both position types T, with one rounding per operation, no
+ * contraction, and sqrt and / the correctly rounded IEEE operations (the compiler's default for HIP in fp32 as in fp64):
+ *   - Pair part.  phi is the handle's pair table (nl_set_pair_table), evaluated by exactly the rule stated there, slots and
+ *     all: fr_phi, pe_phi, in_phi.  It must be set (NL_ERR_STATE otherwise); a model without a pair part passes zeros.
+ *   - Radial tables g.  The grid rule of nl_set_pair_table on a grid of their own: D = (r_max_3^2 - r_min_3^2) / (nknots - 1),
+ *     x_k = r_min_3^2 + k D.  ntypes x ntypes slots, slot a ntypes + b for centre type a and end type b (it need not be
+ *     symmetric).  The caller passes g[slot][k] = g(r) and G[slot][k] = -g'(r) / r at r = sqrt(x_k), finite.  Device form: the
+ *     knot {G_k, dG_k, g_k, dg_k} in T, differences taken in double and rounded once, 0 at the last knot; x0_3 = (T)(r_min_3^2),
+ *     xc_3 = (T)(r_max_3^2), iD = (T)(1 / D).  in_3 = r2 < xc_3 && r2 > 0; s = (r2 - x0_3) iD, k = min((int)s, nknots - 2),
+ *     t = s - (T)k, g = g_k + t dg_k, G = G_k + t dG_k.  A partner that is in_3 with r2 < x0_3 has no value: g = G = NaN, the
+ *     deliberate rule of a pair below the pair table.
+ *   - Angular parameters.  lambda_host and cos0_host: ntypes^3 doubles each, [a][b][c] with a the centre; finite, exactly
+ *     symmetric in (b, c), cos0 in [-1, 1]; rounded to T once.  ntypes <= NL_SW_MAX_TYPES.
+ *   - Partners.  j and k range over the entries of row i of the list of the last build (the filtered list where an exclusion or
+ *     type table is set) that are in_3: an excluded partner, or one of a pair of types with rc_ab = 0, forms no triple.
+ *   - Per partner j of centre i, once: a = r_i - r_j from the image rule of nl_lj_forces, r2_a = ax ax + ay ay + az az as the
+ *     pair function writes it; r = sqrt(r2_a), ir_a = 1 / r, ir2_a = ir_a ir_a, g_a and G_a from the slot (t_i, t_j).
+ *   - Per ordered pair of partners (j, k), k != j, with b, ir_b, g_b of k, Lambda and c0 of (t_i, t_j, t_k), every product and
+ *     sum below one operation in the order the brackets give:
+ *       cs = (((ax bx + ay by) + az bz) ir_a) ir_b       dc = cs - c0       ld = Lambda dc       ldd = ld dc
+ *       q = g_a g_b       h = ldd q       a2 = (ld + ld) q       cb = a2 (ir_a ir_b)       ca = ldd (G_a g_b) + a2 (cs ir2_a)
+ *     The force on the end j from the triple is cb b - ca a, which is
+ *       F_j = -Lambda dc^2 G_a g_b a + 2 Lambda dc g_a g_b (b ir_a ir_b - cs a ir_a^2).
+ *     It is summed over k in parts: sa = sum_k ca, sb = sum_k (cb b) (per component), e_j = sum_k h, each a sum in T in no
+ *     promised order; then F_j = sb - sa a, one product and one difference per component.  F_k is the same from k's side, and
+ *     the centre receives F_i = -(sum_j F_j), the sum over its partners in T, negated.
+ *   - f_dev is n x 4 of T: {fx, fy, fz, pe_i}.  It is zeroed by a kernel, then every centre i adds its own value
+ *     {pair force of its row + F_i, half its pair energies + (sum_j e_j) (T)(1/6)} -- each of the two a sum in T as
+ *     nl_table_forces forms it, then one addition -- and to each partner j {F_j, e_j (T)(1/3)}, by floating-point atomics.  So
+ *     pe_i holds half the pair energies and a third of h for each particle of a triple (the LAMMPS per-atom convention):
+ *     sum pe_i = E.
+ *   - Totals, the 8 doubles of nl_lj_virial.  The pair part is nl_table_virial's, with in = in_phi || in_3 for n_in.  The
+ *     three-body part adds, per centre i and partner j, W_cd -= a_c F_j,d for (c, d) = xx, yy, zz, xy, xz, yz -- the product
+ *     in T from the F_j above, negated, converted -- and U += e_j / 2: every triple once (the kernel doubles the W term in
+ *     double in front of the factor 1/2 of a full list, which is exact).  Summed in double in one fixed order.
+ *   - Full lists only.  A row must hold all partners of its centre: after a NL_LIST_HALF build the four calls return
+ *     NL_ERR_STATE.  Slab builds (local-index ones included) and distributed builds: NL_ERR_STATE -- the force on an owned end
+ *     needs the triples centred on ghosts.
+ *   - At most NL_SW_MAX_NEAR partners in_3 per centre.  A centre with more has no value: NaN in all four columns of the centre
+ *     and of every partner of it that is in_3, and in all 8 totals.  A clamp would be silently wrong physics, and an error
+ *     word would need a host sync.  Rows may be any length: only the in-range partners count.
+ *   - NaN otherwise: where the arithmetic above gives it.  A partner below r_min_3 of a centre with at least two partners in_3
+ *     makes the centre and all its in_3 partners NaN (all four columns) and all 8 totals; a centre with that one partner
+ *     alone has no triple and no NaN.
+ *   - Reproducibility.  The totals use no atomic and one fixed order: two nl_sw_virial calls on the same list and positions
+ *     give the same 8 doubles, bit for bit.  The forces reach the ends, and the centres, by floating-point atomics: f_dev is
+ *     reproducible only within the tested bound.
+ *   - Types.  ntypes == 1: one slot, with or without a type table.  ntypes > 1 needs a type table of exactly that ntypes
+ *     (NL_ERR_STATE without one, NL_ERR_ARG for another ntypes) and a pair table of 1 or ntypes types: nl_set_eam's rules.
+ *   - Reach, at the calls: r_max of the pair table and r_max_3 <= rc for the synchronous calls, <= rc - skin for the enqueue
+ *     calls; with a type table <= rc_ab (less the skin) for every rc_ab > 0.  Else NL_ERR_ARG.
+ *   - nl_set_sw: 2 <= nknots <= NL_TABLE_MAX_KNOTS, 0 < r_min_3 < r_max_3, 1 <= ntypes <= NL_SW_MAX_TYPES, finite tables, angular
+ *     parameters as above, else NL_ERR_ARG and the old tables are kept.  nknots == 0 or four NULL arrays clear the tables (some of
+ *     them NULL: NL_ERR_ARG).  Synchronous; the device buffer is kept where the new tables fit; the list is not touched.
+ *     nl_get_sw: the scalars, and lds: whether the forces and totals read their tables from LDS; NL_ERR_STATE while no tables
+ *     are set.
+ *   - Kernels.  The persistent grid of the table kernels, one wave per centre row: the row is walked once (pair part; the in_3
+ *     partners compacted into a per-wave LDS strip of 64 x {j, a}), then every lane holds one partner and loops over all of
+ *     them.  The pair table and the g tables are staged in LDS where together with the block's strips (4 x 64 x (3 sizeof(T)
+ *     + 4) bytes) they fit NL_TABLE_LDS_BYTES, else both are read from global memory; NL_TABLE_LDS=0 in the environment of
+ *     nl_set_sw forces the global path.  Both paths compute the same totals bit for bit.
+ *   - Everything else (ordering, state, NaN on a non-zero status word, n == 0, the totals' scratch with its first-call rule, the
+ *     enqueue variants copy nothing and can be captured) is nl_table_forces' / nl_table_virial's.
+ * Tested contract (tests/test_sw.py): every component of every particle within SW_C u S and the totals
+ * within SW_CW u S of an O(N m^2) float64 evaluation of the same rule (md_neighbor_list_amd.sw three_body), S the uncancelled
+ * sums over pairs and triples including the conditioning of each table read on the rounding of its r2. */
+#define NL_SW_MAX_TYPES 4
+#define NL_SW_MAX_NEAR 64
+int nl_set_sw(nl_handle_t h, int32_t ntypes, int32_t nknots, double r_min_3, double r_max_3, const double* g_host,
+              const double* G_host, const double* lambda_host, const double* cos0_host);
+int nl_get_sw(nl_handle_t h, int32_t* ntypes, int32_t* nknots, double* r_min_3, double* r_max_3, int32_t* lds);
+int nl_sw_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_sw_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_sw_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+int nl_sw_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+
 /* The pair-distance histogram of the list, the counts behind a radial distribution function g(r): for everybody
  * (nl_pair_histogram) or per unordered pair of types (nl_pair_histogram_typed).  The rule:
  *   - Entries.  The sum runs over the entries (row i, partner j) of the list of the last build: the filtered list where an

@@ -86,6 +86,12 @@ PROTOTYPES = {
     "nl_eam_virial": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_eam_virial_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_eam_get_density": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I32)]),
+    "nl_set_sw": (C.c_int, [_P, _I32, _I32, _D, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
+    "nl_get_sw": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I32)]),
+    "nl_sw_forces": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_sw_forces_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_sw_virial": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_sw_virial_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_pair_histogram": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_enqueue": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_typed": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),

@@ -268,6 +268,9 @@ struct nl_handle_s {
   int32_t ea_nke = 0;
   double ea_rhomax = 0, ea_iDrho = 0;  // rho_max and 1 / Drho
   DevBuf<void> ea_part;            // [3][n_max] rho, fp = F'(rho), Fe = F(rho) of the last EAM call in T, allocated by the first call
+  // nl_set_sw (nl_sw.inc): the radial tables of a three-body potential, {G, dG, g, dg}, slot t_i ntypes + t_j, and behind them
+  // in sw.tab [ntypes^3] knots {Lambda, -, cos0, -} of [t_i][t_j][t_k]; the pair part is tb
+  TableSet sw;
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -2000,4 +2003,5 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_virial.inc"
 #include "nl_table.inc"
 #include "nl_eam.inc"
+#include "nl_sw.inc"
 #include "nl_histogram.inc"

@@ -639,6 +639,51 @@ class NeighListGPU:
         ts = "<f4" if self.dtype == torch.float32 else "<f8"
         return tuple(_as_tensor(p.value, (n.value,), ts, self, self.device).clone() for p in (rho, fp))
 
+    # ------------------------------------------------------------------ Stillinger-Weber three-body potentials
+    def set_sw(self, g, G, r_min, r_max, lam, cos0):
+        """The radial tables and angular parameters of a three-body potential (nl_set_sw); the pair part is the table of
+        set_pair_table, which must be set as well (zeros for a model without one).  ``g = g_ab(r)`` and ``G = -g_ab'(r) / r`` at
+        the knots ``pair_table.knots(r_min, r_max, nknots)`` (``sw.sample`` makes them from callables): ``(nknots,)`` for one
+        type, ``(ntypes^2, nknots)`` with row ``a ntypes + b`` for centre type a and end type b.  ``lam`` and ``cos0``:
+        ``(ntypes, ntypes, ntypes)`` as ``sw.angular`` returns them (scalars for one type).  Synchronous; keeps its device
+        buffer where the tables fit."""
+        import numpy as np
+
+        g, G = (np.ascontiguousarray(np.atleast_2d(np.asarray(m, dtype=np.float64))) for m in (g, G))
+        lam, cos0 = (np.ascontiguousarray(np.asarray(m, dtype=np.float64)).reshape(-1) for m in (lam, cos0))
+        nt = int(round(g.shape[0] ** 0.5))
+        if g.shape != G.shape or g.ndim != 2 or nt * nt != g.shape[0] or lam.shape != (nt ** 3,) or cos0.shape != (nt ** 3,):
+            raise TypeError("g, G must both be (ntypes^2, nknots) and lam, cos0 both hold ntypes^3 values")
+        ptr = lambda m: m.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        check(self._lib.nl_set_sw(self._h, nt, int(g.shape[1]), float(r_min), float(r_max), ptr(g), ptr(G), ptr(lam), ptr(cos0)), "nl_set_sw")
+
+    def clear_sw(self):
+        check(self._lib.nl_set_sw(self._h, 0, 0, 0.0, 0.0, None, None, None, None), "nl_set_sw")
+
+    def sw(self):
+        """``{"ntypes", "nknots", "r_min", "r_max", "lds"}`` of the tables set (nl_get_sw), or None without them.  lds: the
+        forces and totals read the pair table and the radial tables from LDS."""
+        nt, nk, lds = (C.c_int32() for _ in range(3))
+        lo, hi = C.c_double(), C.c_double()
+        code = self._lib.nl_get_sw(self._h, C.byref(nt), C.byref(nk), C.byref(lo), C.byref(hi), C.byref(lds))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_sw")
+        return {"ntypes": nt.value, "nknots": nk.value, "r_min": lo.value, "r_max": hi.value, "lds": bool(lds.value)}
+
+    def sw_forces(self, q, wait=True, out=None):
+        """Stillinger-Weber forces and per-particle energies (nl_sw_forces; ``wait=False``: nl_sw_forces_enqueue):
+        ``(n, 4) = {fx, fy, fz, pe_i}``, pe_i = half the pair energies of i + a third of every triple i is part of, so that
+        ``pe.sum()`` is the energy.  Full lists of whole builds only.  A centre with more than 64 partners within r_max of the
+        radial tables, or one closer than their r_min, gives NaN to itself and to those partners."""
+        return self._lj("nl_sw_forces", q, (), wait, out)
+
+    def sw_virial(self, q, wait=True, out=None):
+        """The totals that belong to sw_forces (nl_sw_virial; ``wait=False``: nl_sw_virial_enqueue):
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, every pair and every triple once, n_in the pairs within the longer of
+        the two ranges.  No atomics: bit for bit reproducible.  The first call allocates scratch: make it before a graph capture."""
+        return self._lj("nl_sw_virial", q, (), wait, out)
+
     def _ntypes(self):
         """ntypes of the handle's type table (nl_get_types; NL_ERR_STATE without one)."""
         ptr, n, nt = C.c_void_p(), C.c_int32(), C.c_int32()
