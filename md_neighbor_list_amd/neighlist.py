@@ -206,18 +206,23 @@ class NeighListGPU:
         return int(st[0]), int(st[1])
 
     # ------------------------------------------------------------------ excluded pairs
-    def _exclusion_pairs(self, pairs):
-        if isinstance(pairs, torch.Tensor):
-            t = pairs
+    def _int32_input(self, a, name, shape, dims, word):
+        """A caller's int32/int64 tensor or array as a contiguous int32 device tensor.  dims: its shape, None for any extent;
+        name, shape and word fill the messages.  int64 values outside the int32 range are refused: a cast would wrap them."""
+        if isinstance(a, torch.Tensor):
+            t = a
         else:
             import numpy as np
 
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(pairs)))
-        if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != 2:
-            raise TypeError("pairs must be an (E, 2) int32 or int64 tensor or array")
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+        if t.dtype not in (torch.int32, torch.int64) or t.dim() != len(dims) or any(d is not None and e != d for e, d in zip(t.shape, dims)):
+            raise TypeError(f"{name} must be an {shape} int32 or int64 tensor or array")
         if t.dtype == torch.int64 and t.numel() and (int(t.min()) < -2**31 or int(t.max()) >= 2**31):
-            raise ValueError("pairs hold an index outside the int32 range")  # (a cast would wrap it onto a valid id)
+            raise ValueError(f"{name} hold {word} outside the int32 range")
         return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def _exclusion_pairs(self, pairs):
+        return self._int32_input(pairs, "pairs", "(E, 2)", (None, 2), "an index")
 
     def set_exclusions(self, pairs, particle_number):
         """Leaves the pairs of ``pairs`` out of every later build (nl_set_exclusions): an ``(E, 2)`` int32/int64 tensor or
@@ -259,12 +264,7 @@ class NeighListGPU:
         rc = np.ascontiguousarray(np.asarray(rc_matrix, dtype=np.float64))
         if rc.ndim != 2 or rc.shape[0] != rc.shape[1]:
             raise TypeError("rc_matrix must be a square (ntypes, ntypes) matrix")
-        t = types if isinstance(types, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(types)))
-        if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
-            raise TypeError("types must be an (n,) int32 or int64 tensor or array")
-        if t.dtype == torch.int64 and t.numel() and (int(t.min()) < -2**31 or int(t.max()) >= 2**31):
-            raise ValueError("types hold a value outside the int32 range")
-        t = t.to(device=self.device, dtype=torch.int32).contiguous()
+        t = self._int32_input(types, "types", "(n,)", (None,), "a value")
         n = int(t.shape[0])
         ptr = t.data_ptr() if n else None
         if n == 0:  # (an empty table still needs a non-NULL pointer: NULL clears)
@@ -280,9 +280,14 @@ class NeighListGPU:
     def types(self):
         """The handle's copy of the types (nl_get_types), relabelled by resort(); a view, valid until the table is set
         or cleared."""
+        ptr, n, _ = self._get_types()
+        return _as_tensor(ptr, (n,), "<i4", self, self.device)
+
+    def _get_types(self):
+        """(pointer, n, ntypes) of the handle's type table (nl_get_types; NL_ERR_STATE without one)."""
         ptr, n, nt = C.c_void_p(), C.c_int32(), C.c_int32()
         check(self._lib.nl_get_types(self._h, C.byref(ptr), C.byref(n), C.byref(nt)), "nl_get_types")
-        return _as_tensor(ptr.value, (n.value,), "<i4", self, self.device)
+        return ptr.value, int(n.value), int(nt.value)
 
     def set_lj_type_params(self, epsilon, sigma, rc_force):
         """Lennard-Jones parameters per pair of types for lj_forces_typed (nl_set_lj_type_params): three symmetric
@@ -299,7 +304,7 @@ class NeighListGPU:
     def lj_forces_typed(self, q, wait=True, out=None):
         """lj_forces with the parameters of set_lj_type_params, per pair of types (nl_lj_forces_typed); ``wait=False``:
         nl_lj_forces_typed_enqueue (rc_force within cut-off - skin).  Returns ``(n, 4) = {fx, fy, fz, pe_i}``."""
-        return self._lj("nl_lj_forces_typed", q, (), wait, out)
+        return self._consume("nl_lj_forces_typed", q, (), wait, out, totals=False)
 
     # ------------------------------------------------------------------ pair images
     def set_pair_images(self, on=True):
@@ -366,21 +371,24 @@ class NeighListGPU:
 
     GID_IN_W = "w"  # MakeNeighListSlab(gid=GID_IN_W): ids are stored in q[:, 3] as integer bit patterns (NL_GID_IN_W)
 
+    def _gid_ptr(self, q, gid, n):
+        """What a slab build takes as gid: the tensor's address, NULL for None (identity), 1 for GID_IN_W."""
+        if isinstance(gid, str):
+            if gid != self.GID_IN_W or q.shape[1] != 4:
+                raise TypeError("gid='w' needs 4-component positions")
+            return 1
+        if gid is None:
+            return None
+        if gid.device.type != "cuda" or gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
+            raise TypeError("gid must be a contiguous int32 device tensor with one id per particle")
+        return gid.data_ptr()
+
     def MakeNeighListSlab(self, q, gid, n_rows, z_lo, z_hi, sync=True):
         """Domain-decomposed build: rows for the first ``n_rows`` (owned) particles, the rest
         are ghosts of the two neighbouring cell layers; ``gid`` are global ids: an int32 device tensor, None
         (identity) or ``GID_IN_W`` (taken from the w component of the positions)."""
         n = self._check_q(q, None)
-        if isinstance(gid, str):
-            if gid != self.GID_IN_W or q.shape[1] != 4:
-                raise TypeError("gid='w' needs 4-component positions")
-            gid_ptr = 1
-        elif gid is not None:
-            if gid.device.type != "cuda" or gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
-                raise TypeError("gid must be a contiguous int32 device tensor with one id per particle")
-            gid_ptr = gid.data_ptr()
-        else:
-            gid_ptr = None
+        gid_ptr = self._gid_ptr(q, gid, n)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._q = (q, gid)
         self._n, self._n_rows = n, int(n_rows)
@@ -394,16 +402,7 @@ class NeighListGPU:
         """nl_make_list_slab_begin: the part of a slab build that needs only the owned particles q[:n_rows]; the ghost
         rows of q may still be in flight.  Follow with MakeNeighListSlabFinish once the current stream waits for them."""
         n = self._check_q(q, None)
-        if isinstance(gid, str):
-            if gid != self.GID_IN_W or q.shape[1] != 4:
-                raise TypeError("gid='w' needs 4-component positions")
-            gid_ptr = 1
-        elif gid is not None:
-            if gid.device.type != "cuda" or gid.dtype != torch.int32 or gid.numel() != n or not gid.is_contiguous():
-                raise TypeError("gid must be a contiguous int32 device tensor with one id per particle")
-            gid_ptr = gid.data_ptr()
-        else:
-            gid_ptr = None
+        gid_ptr = self._gid_ptr(q, gid, n)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._q = (q, gid)
         self._n, self._n_rows = n, int(n_rows)
@@ -425,17 +424,20 @@ class NeighListGPU:
         (nl_get_full_transposed); the number of columns is the n of the last build.  Entries ``k >= count[i]`` hold -1
         after a half build, and after a full build when the buffer was just allocated or grown (the first fetch, one
         after ``Initialize`` or ``set_full_list``) -- otherwise whatever an earlier build left there."""
+        lst, _, stride, mx = self._full_transposed()
+        return _as_tensor(lst, (max(mx, 1), stride), "<i4", self, self.device)
+
+    def _full_transposed(self):
+        """(list, counts, stride, longest row) of nl_get_full_transposed."""
         lst, cnt, stride, mx = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int32()
         check(self._lib.nl_get_full_transposed(self._h, C.byref(lst), C.byref(cnt), C.byref(stride), C.byref(mx)),
               "nl_get_full_transposed")
-        return _as_tensor(lst.value, (max(mx.value, 1), stride.value), "<i4", self, self.device)
+        return lst.value, cnt.value, int(stride.value), int(mx.value)
 
     def number_of_partners(self):
         """neighlist_gpu.hpp:476-482: full counts."""
-        lst, cnt, stride, mx = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int32()
-        check(self._lib.nl_get_full_transposed(self._h, C.byref(lst), C.byref(cnt), C.byref(stride), C.byref(mx)),
-              "nl_get_full_transposed")
-        return _as_tensor(cnt.value, (stride.value,), "<i4", self, self.device)
+        _, cnt, stride, _ = self._full_transposed()
+        return _as_tensor(cnt, (stride,), "<i4", self, self.device)
 
     def number_of_pairs(self):
         """neighlist_gpu.hpp:484-487: the sum of the FULL counts (= 2 x half pairs)."""
@@ -504,16 +506,16 @@ class NeighListGPU:
         rc_force must then be <= cut-off - skin, and a list whose build failed gives NaN.  ``out``: an (n, 4) tensor
         to write into (graph capture).  After a slab build under set_local_ids: ``(n_rows, 4)``, the owned particles' rows
         of the global result (a ghost partner receives no reaction: its owner evaluates the pair in its own row)."""
-        return self._lj("nl_lj_forces", q, (epsilon, sigma, rc_force), wait, out)
+        return self._consume("nl_lj_forces", q, (epsilon, sigma, rc_force), wait, out, totals=False)
 
-    def _lj(self, name, q, lj, wait, out):
-        """What lj_forces, lj_virial and their typed forms share: the output (``(n, 4)`` of the list's dtype, or 8 float64
-        for a virial), the stream, the pick of ``name`` or ``name``_enqueue and the call.  lj: (epsilon, sigma, rc_force),
-        or () for the typed forms."""
+    def _consume(self, name, q, lj, wait, out, totals):
+        """The consumers' call: the output (the ``(n_rows, 4)`` rows of the list's dtype, or the 8 float64 ``totals``), the
+        stream, the pick of ``name`` or ``name``_enqueue and the call.  lj: (epsilon, sigma, rc_force) for the scalar
+        Lennard-Jones forms, () for every other consumer."""
         n = self._check_q(q, None)
         if n != self._n:
             raise ValueError("q must hold the particles the list was built from")
-        if "virial" in name:
+        if totals:
             o = torch.empty(8, dtype=torch.float64, device=self.device) if out is None else out
             if o.shape != (8,) or o.dtype != torch.float64 or not o.is_contiguous() or o.device != q.device:
                 raise TypeError("out must be a contiguous float64 tensor of 8 on the list's device")
@@ -539,12 +541,12 @@ class NeighListGPU:
         (nl_lj_virial_enqueue) a list whose build failed gives 8 NaN.  The first call allocates scratch: make it before
         a graph capture.  After a slab build under set_local_ids: this rank's share (a pair that crosses a cut counts 1/2
         on either side, so n_in may be a half-integer); the ranks' 8 doubles add up to the global box's."""
-        return self._lj("nl_lj_virial", q, (epsilon, sigma, rc_force), wait, out)
+        return self._consume("nl_lj_virial", q, (epsilon, sigma, rc_force), wait, out, totals=True)
 
     def lj_virial_typed(self, q, wait=True, out=None):
         """lj_virial with the parameters of set_lj_type_params, per pair of types (nl_lj_virial_typed); ``wait=False``:
         nl_lj_virial_typed_enqueue."""
-        return self._lj("nl_lj_virial_typed", q, (), wait, out)
+        return self._consume("nl_lj_virial_typed", q, (), wait, out, totals=True)
 
     # ------------------------------------------------------------------ tabulated pair potentials
     def set_pair_table(self, F, U, r_min, r_max):
@@ -580,12 +582,12 @@ class NeighListGPU:
         """lj_forces with the pair function of set_pair_table (nl_table_forces): ``(n, 4) = {fx, fy, fz, pe_i}``, linear
         interpolation in r^2 between the knots, nothing beyond r_max (within the list's cut-off; less the skin with
         ``wait=False``, nl_table_forces_enqueue).  A pair closer than r_min gives NaN to both its particles."""
-        return self._lj("nl_table_forces", q, (), wait, out)
+        return self._consume("nl_table_forces", q, (), wait, out, totals=False)
 
     def table_virial(self, q, wait=True, out=None):
         """lj_virial with the pair function of set_pair_table (nl_table_virial; ``wait=False``: nl_table_virial_enqueue):
         ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, n_in the pairs within r_max; 8 NaN where a pair lies below r_min."""
-        return self._lj("nl_table_virial", q, (), wait, out)
+        return self._consume("nl_table_virial", q, (), wait, out, totals=True)
 
     # ------------------------------------------------------------------ embedded-atom potentials
     def set_eam(self, f, G, r_min, r_max, E, P, rho_max):
@@ -623,13 +625,13 @@ class NeighListGPU:
         ``(n, 4) = {fx, fy, fz, pe_i}``, pe_i = half the pair energies of i + F(rho_i), so that ``pe.sum()`` is the energy.
         Three passes over the list of the last build: densities, embedding, forces.  A density outside [0, rho_max] or a
         pair below r_min gives NaN.  The first call allocates scratch: make it before a graph capture.  Whole builds only."""
-        return self._lj("nl_eam_forces", q, (), wait, out)
+        return self._consume("nl_eam_forces", q, (), wait, out, totals=False)
 
     def eam_virial(self, q, wait=True, out=None):
         """The totals that belong to eam_forces (nl_eam_virial; ``wait=False``: nl_eam_virial_enqueue):
         ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, U the pair energies plus every F(rho_i).  Bit for bit reproducible
         after a full-list build; after a half-list build the densities are summed by atomics and the totals follow them."""
-        return self._lj("nl_eam_virial", q, (), wait, out)
+        return self._consume("nl_eam_virial", q, (), wait, out, totals=True)
 
     def eam_density(self):
         """``(rho, fp)``: rho_i and F'(rho_i) of the last eam_forces / eam_virial call (nl_eam_get_density), copies of
@@ -676,19 +678,13 @@ class NeighListGPU:
         ``(n, 4) = {fx, fy, fz, pe_i}``, pe_i = half the pair energies of i + a third of every triple i is part of, so that
         ``pe.sum()`` is the energy.  Full lists of whole builds only.  A centre with more than 64 partners within r_max of the
         radial tables, or one closer than their r_min, gives NaN to itself and to those partners."""
-        return self._lj("nl_sw_forces", q, (), wait, out)
+        return self._consume("nl_sw_forces", q, (), wait, out, totals=False)
 
     def sw_virial(self, q, wait=True, out=None):
         """The totals that belong to sw_forces (nl_sw_virial; ``wait=False``: nl_sw_virial_enqueue):
         ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, every pair and every triple once, n_in the pairs within the longer of
         the two ranges.  No atomics: bit for bit reproducible.  The first call allocates scratch: make it before a graph capture."""
-        return self._lj("nl_sw_virial", q, (), wait, out)
-
-    def _ntypes(self):
-        """ntypes of the handle's type table (nl_get_types; NL_ERR_STATE without one)."""
-        ptr, n, nt = C.c_void_p(), C.c_int32(), C.c_int32()
-        check(self._lib.nl_get_types(self._h, C.byref(ptr), C.byref(n), C.byref(nt)), "nl_get_types")
-        return int(nt.value)
+        return self._consume("nl_sw_virial", q, (), wait, out, totals=True)
 
     def pair_histogram(self, q, r_max, nbins, typed=False, wait=True, out=None):
         """Pair-distance histogram of the list of the last build (nl_pair_histogram): every stored pair once, half or
@@ -704,7 +700,7 @@ class NeighListGPU:
             raise ValueError("q must hold the particles the list was built from")
         nbins = int(nbins)
         if typed:
-            nt = self._ntypes()
+            nt = self._get_types()[2]
             shape = (nt * (nt + 1) // 2, nbins)
         else:
             shape = (nbins,)
@@ -736,7 +732,7 @@ class NeighListGPU:
                 raise ValueError("a typed histogram needs types=(a, b)")
             return _rdf.rdf(h, r_max, Lx * Ly * Lz, self._n, frames=frames)
         a, b = (int(t) for t in types)
-        nt = self._ntypes()
+        nt = self._get_types()[2]
         if h.ndim != 2 or h.shape[0] != _rdf.nslots(nt):
             raise ValueError(f"types=(a, b) picks a row of a typed histogram of {_rdf.nslots(nt)} rows")
         counts = torch.bincount(self.types().to(torch.int64), minlength=nt).cpu()

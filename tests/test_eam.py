@@ -33,9 +33,12 @@ import re
 import numpy as np
 import pytest
 
-from md_neighbor_list_amd import eam, pair_table, rdf
-from tests.test_lj_consumer import _handle, _torch
-from tests.test_pair_table import CASES, DTYPES, N, NK, R_MAX, R_MIN, _input, _moved, _pairs, _tab
+from md_neighbor_list_amd import eam, pair_table
+from tests import consumer_contract as contract
+from tests.consumer_util import CASES, DTYPES, N, NK, R_MAX, R_MIN, _handle, _pair_tab, _tab, _torch
+from tests.consumer_util import _table_input as _input
+from tests.consumer_util import _table_moved as _moved
+from tests.consumer_util import _table_pairs as _pairs
 from tests.util import LJ_BOXES, LJ_M, ROOT, check_lj, lj_pairs, lj_ratio, lj_unit
 from tests.util_eam import (DEFECTS, EAM_C, EAM_C_RHO, EAM_CW, EamTables, eam_emulate, eam_energy, eam_functions, eam_list_pairs,
                             eam_reference)
@@ -52,16 +55,6 @@ EMULATED_MAX, EMULATED_MAX_RHO, EMULATED_MAX_W = 1.82, 2.35, 0.391  # the larges
 
 
 # ------------------------------------------------------------------------------------------------ inputs, references
-def _pair_tab(nt, r_min, r_max, nk):
-    """The pair tables of test_pair_table's _tab ("morse", "typed3") on another grid."""
-    if nt == 1:
-        return pair_table.sample(*morse(), r_min, r_max, nk)
-    rows = [pair_table.sample(*morse(De=1.0 + 0.2 * (s % 5), a=1.5, r0=1.05 + 0.03 * (s % 6)), r_min, r_max, nk) for s in range(rdf.nslots(nt))]
-    F, U = np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
-    F[rdf.slot(0, nt - 1, nt)] = U[rdf.slot(0, nt - 1, nt)] = 0.0
-    return F, U
-
-
 @functools.lru_cache(maxsize=None)
 def _tabs(kind, nk=NK, nke=NK, embedding=True, pair=True, rho_max=None, r_min_pair=R_MIN, r_max_pair=R_MAX, r_max_d=R_MAX):
     """(EamTables, types, rc_ab(rc_list)) of a potential: one type with the Morse table, or the 3-type mixture of
@@ -362,10 +355,6 @@ def test_wrong_results_are_rejected():
 
 
 # ------------------------------------------------------------------------------------------------------ GPU helpers
-def _tdt(dtype):
-    return _torch().float32 if dtype == np.float32 else _torch().float64
-
-
 def _set(nl, kind, rc, **kw):
     """The type table (three types, at the list's cut-off), the pair table and the EAM tables onto an initialised handle."""
     tab, types, rc_ab = _tabs(kind, **kw)
@@ -374,17 +363,6 @@ def _set(nl, kind, rc, **kw):
     nl.set_pair_table(tab.F if tab.nt_pair > 1 else tab.F[0], tab.U if tab.nt_pair > 1 else tab.U[0], tab.r_min, tab.r_max)
     nl.set_eam(tab.f, tab.G, tab.r_min_d, tab.r_max_d, tab.E, tab.P, tab.rho_max)
     return tab
-
-
-def _built(q, box, dtype, full, rc, kind, off=0, stride=4, **kw):
-    """(handle, device positions) after one build, the tables set."""
-    torch = _torch()
-    nl = _handle(box, dtype, full, rc, off)
-    nl.Initialize(len(q))
-    _set(nl, kind, rc, **kw)
-    qd = torch.from_numpy(np.ascontiguousarray(q[:, :stride].astype(dtype))).cuda()
-    nl.MakeNeighList(qd, len(q))
-    return nl, qd
 
 
 def _check(f, rho, w, ref, dtype, rows=None):
@@ -401,15 +379,13 @@ def _check(f, rho, w, ref, dtype, rows=None):
     return f, rho, w
 
 
-def _run(nl, qd, ref, dtype, wait=True, rows=None):
-    f = nl.eam_forces(qd, wait=wait)
-    rho, fp = nl.eam_density()
-    w = nl.eam_virial(qd, wait=wait)
-    assert f.shape == (N, 4) and f.dtype == _tdt(dtype) and w.shape == (8,) and w.dtype == _torch().float64
-    assert rho.shape == (N,) and rho.dtype == _tdt(dtype) and fp.shape == (N,)
-    return _check(f, rho, w, ref, dtype, rows)
-
-
+EAM = contract.Consumer(
+    forces="eam_forces", virial="eam_virial", scratch="eam_virial", clear="clear_eam", info="eam",
+    entry=("nl_eam_forces", "nl_eam_forces_enqueue", "nl_eam_virial", "nl_eam_virial_enqueue"), set=_set, kinds=KINDS, ref=_ref,
+    moved_ref=_moved_ref, extra=lambda nl: nl.eam_density(),  # (rho, fp)
+    check=lambda f, w, x, ref, dtype, rows=None: _check(f, x[0], w, ref, dtype, rows), half_lists=True, local_slabs=False)
+_built = functools.partial(contract.built, EAM)
+_run = functools.partial(contract.run, EAM)
 gpu = pytest.mark.gpu
 
 
@@ -667,24 +643,7 @@ def test_a_pair_below_the_density_table(full, dtype):
 @pytest.mark.parametrize("box,kind", [("xyz", "one"), ("tilt", "three")])
 def test_reuse_within_the_skin(box, kind, full, dtype):
     """A list kept by nl_update_list, read at moved positions by the enqueue variants; no extra build."""
-    torch = _torch()
-    q1 = _moved(box)[0]
-    nl = _handle(box, dtype, full, 2.9)
-    nl.set_skin(0.4)
-    nl.Initialize(N)
-    _set(nl, kind, 2.9)
-    qd = torch.from_numpy(_input(box, False).astype(dtype)).cuda()
-    nl.update(qd, sync=True)
-    builds = nl.update_stats()[1]
-    nl.eam_virial(qd)  # (the scratch)
-    qd.copy_(torch.from_numpy(q1.astype(dtype)))
-    nl.update(qd)
-    f = nl.eam_forces(qd, wait=False)
-    rho = nl.eam_density()[0]
-    w = nl.eam_virial(qd, wait=False)
-    torch.cuda.synchronize()
-    assert nl.update_stats()[1] == builds
-    _check(f, rho, w, _moved_ref(box, kind), dtype)
+    contract.reuse_within_the_skin(EAM, box, kind, full, dtype)
 
 
 @gpu
@@ -695,88 +654,52 @@ def test_captured(full):
     from md_neighbor_list_amd._lib import NL_ERR_STATE, NLError
 
     torch = _torch()
-    dtype = np.float32
-    sets = [(_input("xyz", False), _ref("xyz", False, "one")), (_moved("xyz")[0], _moved_ref("xyz", "one"))]
-    nl = _handle("xyz", dtype, full, 2.9)
-    nl.set_skin(0.4)
-    nl.Initialize(N)
-    _set(nl, "one", 2.9)
-    src = torch.from_numpy(sets[0][0].astype(dtype)).cuda()
-    qd = src.clone()
-    fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
-    wd = torch.empty(8, dtype=torch.float64, device="cuda")
-    nl.update(qd, sync=True)
-    nl.update(qd)
-    nl.table_virial(qd, wait=False)  # (the totals' scratch exists: what is missing below is the EAM scratch)
-    nl.synchronize()
-    g0 = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g0):
-        for call, o in ((nl.eam_forces, fd), (nl.eam_virial, wd)):
-            with pytest.raises(NLError) as e:
-                call(qd, wait=False, out=o)
-            assert e.value.code == NL_ERR_STATE
-        nl.table_forces(qd, wait=False, out=fd)
-    nl.eam_forces(qd)  # synchronous, outside a capture: allocates
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        qd.copy_(src)
-        nl.update(qd)
-        nl.eam_forces(qd, wait=False, out=fd)
-        nl.eam_virial(qd, wait=False, out=wd)
-    for q, ref in sets:
-        src.copy_(torch.from_numpy(q.astype(dtype)))
-        fd.fill_(-1.0), wd.fill_(-1.0)
-        g.replay()
-        torch.cuda.synchronize()
-        _check(fd, nl.eam_density()[0], wd, ref, dtype)
-    # tables of the same size set afterwards keep the device buffer: the next replay computes with them
-    tab = _tabs("one", embedding=False)[0]
-    nl.set_eam(tab.f, tab.G, tab.r_min_d, tab.r_max_d, tab.E, tab.P, tab.rho_max)
-    fd.fill_(-1.0), wd.fill_(-1.0)
-    g.replay()
-    torch.cuda.synchronize()
-    q1, pairs1 = _moved("xyz")
-    _check(fd, nl.eam_density()[0], wd, _refs(q1, "xyz", "one", pairs1, embedding=False), dtype)
+
+    def before(nl, qd, fd, wd):
+        nl.table_virial(qd, wait=False)  # (the totals' scratch exists: what is missing below is the EAM scratch)
+        nl.synchronize()
+        g0 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g0):
+            for call, o in ((nl.eam_forces, fd), (nl.eam_virial, wd)):
+                with pytest.raises(NLError) as e:
+                    call(qd, wait=False, out=o)
+                assert e.value.code == NL_ERR_STATE
+            nl.table_forces(qd, wait=False, out=fd)
+        nl.eam_forces(qd)  # synchronous, outside a capture: allocates
+
+    def after(nl, replay):
+        # tables of the same size set afterwards keep the device buffer: the next replay computes with them
+        tab = _tabs("one", embedding=False)[0]
+        nl.set_eam(tab.f, tab.G, tab.r_min_d, tab.r_max_d, tab.E, tab.P, tab.rho_max)
+        fd, wd = replay()
+        q1, pairs1 = _moved("xyz")
+        _check(fd, nl.eam_density()[0], wd, _refs(q1, "xyz", "one", pairs1, embedding=False), np.float32)
+
+    contract.captured(EAM, full, before, after)
 
 
 @gpu
 def test_failed_list():
     """An enqueue behind an asynchronous build that overflowed its capacity: NaN forces, densities and totals, NL_ERR_CAPACITY
     at synchronize; after the synchronous repeat all are finite."""
-    from md_neighbor_list_amd import NeighListGPU, inputs
-    from md_neighbor_list_amd._lib import NL_ERR_CAPACITY, NLError
+    def set_tables(nl):
+        fs, dfs, Fs, dFs = eam_functions(1)
+        nl.set_pair_table(*pair_table.sample(*morse(), 1e-3, R_MAX, NK), 1e-3, R_MAX)  # (a uniform random box has close pairs)
+        f, G, E, P = eam.sample(fs[0], dfs[0], Fs[0], dFs[0], 1e-3, R_MAX, NK, 400.0, NK)
+        nl.set_eam(f, G, 1e-3, R_MAX, E, P, 400.0)
 
-    torch = _torch()
-    q, box = inputs.uniform_box(20000, dtype=np.float32, seed=28, box=(28.0, 28.0, 28.0))
-    nl = NeighListGPU(3.3, *box, dtype=torch.float32)
-    nl.set_skin(0.4)
-    nl.Initialize(len(q))
-    fs, dfs, Fs, dFs = eam_functions(1)
-    nl.set_pair_table(*pair_table.sample(*morse(), 1e-3, R_MAX, NK), 1e-3, R_MAX)  # (a uniform random box has close pairs)
-    f, G, E, P = eam.sample(fs[0], dfs[0], Fs[0], dFs[0], 1e-3, R_MAX, NK, 400.0, NK)
-    nl.set_eam(f, G, 1e-3, R_MAX, E, P, 400.0)
-    nl.update(torch.from_numpy(q).cuda(), sync=True)
-    qd = torch.from_numpy(q).cuda()
-    nl.eam_virial(qd)  # (the scratch of both kinds)
-    nl.set_capacity(1000)
-    nl.update(qd)
-    f, w = nl.eam_forces(qd, wait=False), nl.eam_virial(qd, wait=False)
-    with pytest.raises(NLError) as e:
-        nl.synchronize()
-    assert e.value.code == NL_ERR_CAPACITY
-    assert torch.isnan(f).all() and f.shape == (len(q), 4) and torch.isnan(w).all() and torch.isnan(nl.eam_density()[0]).all()
-    nl.update(qd, sync=True)  # grows the list
-    f, w = nl.eam_forces(qd, wait=False), nl.eam_virial(qd, wait=False)
-    assert torch.isfinite(f).all() and torch.isfinite(w).all() and w[7] > 0
+    def prepare(nl, qd):
+        nl.update(qd, sync=True)
+        nl.eam_virial(qd)  # (the scratch of both kinds)
+
+    contract.failed_list(EAM, set_tables, prepare)
 
 
 @gpu
 @pytest.mark.parametrize("off", [32, 64])
 @pytest.mark.parametrize("full", [False, True])
 def test_both_offset_widths(full, off):
-    nl, qd = _built(_input("hex", True), "hex", np.float32, full, 2.5, "three", off)
-    assert nl.build_info()["offset_bits"] == off
-    _run(nl, qd, _ref("hex", True, "three"), np.float32)
+    contract.both_offset_widths(EAM, full, off)
 
 
 @gpu
@@ -795,7 +718,7 @@ def test_state_and_arguments():
     qd = torch.from_numpy(q.astype(np.float32)).cuda()
     fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
     out = torch.empty(8, dtype=torch.float64, device="cuda")
-    calls = [(lib.nl_eam_forces, fd), (lib.nl_eam_forces_enqueue, fd), (lib.nl_eam_virial, out), (lib.nl_eam_virial_enqueue, out)]
+    calls = contract.entry_calls(EAM, lib, fd, out)
     set_one = lambda t=tab: nl.set_eam(t.f, t.G, t.r_min_d, t.r_max_d, t.E, t.P, t.rho_max)  # noqa: E731
     # nothing set; only the pair table; only the EAM tables
     assert nl.eam() is None and lib.nl_get_eam(nl._h, *([None] * 8)) == NL_ERR_STATE
@@ -840,32 +763,16 @@ def test_state_and_arguments():
         nl.set_eam(f, G[:-1], R_MIN, R_MAX, E, P, rm)
     with pytest.raises(TypeError):
         nl.set_eam(tab3.f, tab3.G, R_MIN, R_MAX, E, P, rm)  # 3 density slots, 1 embedding slot
-    # the calls' arguments
-    for fn, o in calls:
-        assert fn(nl._h, qd.data_ptr(), 4, None, None) == NL_ERR_ARG
-        assert fn(nl._h, None, 4, o.data_ptr(), None) == NL_ERR_ARG
-        assert fn(None, qd.data_ptr(), 4, o.data_ptr(), None) == NL_ERR_ARG
-        for stride in (0, 2, 5):
-            assert fn(nl._h, qd.data_ptr(), stride, o.data_ptr(), None) == NL_ERR_ARG
-    # the setter does not touch the list
-    nl.update(qd, sync=True)
-    builds = nl.update_stats()[1]
-    set_one()
-    nl.update(qd, sync=True)
-    assert nl.update_stats()[1] == builds
-    # reach of the density table: rc = 2.9, skin = 0.3 (the pair table stays at 2.5)
+    contract.call_arguments(calls, nl, qd)
+    contract.setter_keeps_the_list(nl, qd, set_one)
+    # reach of the density table (the pair table stays at 2.5)
     fs, dfs, Fs, dFs = eam_functions(1)
-    for r_max, sync_ok, enq_ok in ((2.6, True, True), (2.7, True, False), (2.9, True, False), (3.0, False, False)):
+
+    def set_r_max(r_max):
         t = eam.sample(fs[0], dfs[0], Fs[0], dFs[0], R_MIN, r_max, NK, 60.0, NK)
         nl.set_eam(t[0], t[1], R_MIN, r_max, t[2], t[3], 60.0)
-        for wait, ok in ((True, sync_ok), (False, enq_ok)):
-            for call in (nl.eam_forces, nl.eam_virial):
-                if ok:
-                    call(qd, wait=wait)
-                else:
-                    with pytest.raises(NLError) as e:
-                        call(qd, wait=wait)
-                    assert e.value.code == NL_ERR_ARG, (r_max, wait)
+
+    contract.reach(EAM, nl, qd, set_r_max)
     # ... and of the pair table
     set_one()
     nl.set_pair_table(*pair_table.sample(*morse(), R_MIN, 2.7, NK), R_MIN, 2.7)
@@ -874,35 +781,9 @@ def test_state_and_arguments():
         nl.eam_forces(qd, wait=False)
     assert e.value.code == NL_ERR_ARG
     nl.set_pair_table(F, U, R_MIN, R_MAX)
-    # clearing, both ways
-    nl.clear_eam()
-    assert nl.eam() is None
-    set_one()
-    assert lib.nl_set_eam(nl._h, *args(nd=0)) == 0 and nl.eam() is None
-    for wait in (True, False):
-        with pytest.raises(NLError) as e:
-            nl.eam_forces(qd, wait=wait)
-        assert e.value.code == NL_ERR_STATE
+    contract.clearing(EAM, nl, qd, set_one, lambda: lib.nl_set_eam(nl._h, *args(nd=0)))
     # several types: a type table of that ntypes, a pair table of 1 or ntypes types
-    set_one(tab3)
-    for call in (nl.eam_forces, nl.eam_virial):
-        with pytest.raises(NLError) as e:
-            call(qd)
-        assert e.value.code == NL_ERR_STATE
-    nl.set_type_cutoffs(types % 2, [[2.9, 2.9], [2.9, 2.9]])
-    nl.MakeNeighList(qd, N)
-    with pytest.raises(NLError) as e:
-        nl.eam_forces(qd)
-    assert e.value.code == NL_ERR_ARG  # ntypes 3 against the type table's 2
-    set_one()
-    assert torch.isfinite(nl.eam_forces(qd)).all()  # one type works with a type table set
-    nl.set_type_cutoffs(types, [[2.9, 2.9, 0.0], [2.9, 2.55, 2.9], [0.0, 2.9, 2.9]])
-    nl.MakeNeighList(qd, N)
-    set_one(tab3)
-    assert torch.isfinite(nl.eam_virial(qd)).all()  # a pair table of one type under three density slots; 2.5 <= 2.55
-    with pytest.raises(NLError) as e:
-        nl.eam_virial(qd, wait=False)  # 2.5 > 2.55 - 0.3
-    assert e.value.code == NL_ERR_ARG
+    contract.several_types(EAM, nl, qd, types, set_one, lambda: set_one(tab3))  # (a pair table of one type under three density slots)
     nl.set_pair_table(tab3.F, tab3.U, R_MIN, R_MAX)
     assert torch.isfinite(nl.eam_forces(qd)).all()
     # nl_initialize drops the scratch; the next call allocates it again, for more particles
@@ -913,17 +794,13 @@ def test_state_and_arguments():
     assert lib.nl_eam_get_density(nl._h, C.byref(p), C.byref(p), C.byref(C.c_int32())) == NL_ERR_STATE
     nl.MakeNeighList(qd, N)
     _run(nl, qd, _ref("open", False, "one"), np.float32)
+
     # n == 0
-    empty = _handle("open", np.float32, False, 2.9)
-    empty.Initialize(16)
-    empty.set_pair_table(F, U, R_MIN, R_MAX)
-    empty.set_eam(tab.f, tab.G, R_MIN, R_MAX, tab.E, tab.P, rm)
-    empty.MakeNeighList(torch.zeros((0, 4), dtype=torch.float32, device="cuda"))
-    out.fill_(7.0)
-    assert lib.nl_eam_virial(empty._h, qd.data_ptr(), 4, out.data_ptr(), None) == 0
-    assert lib.nl_eam_forces(empty._h, qd.data_ptr(), 4, fd.data_ptr(), None) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(out.cpu().numpy(), np.zeros(8))
+    def set_tables(empty):
+        empty.set_pair_table(F, U, R_MIN, R_MAX)
+        empty.set_eam(tab.f, tab.G, R_MIN, R_MAX, tab.E, tab.P, rm)
+
+    contract.no_particles(EAM, lib, False, set_tables, qd, fd, out)
 
 
 @gpu
@@ -931,28 +808,7 @@ def test_state_and_arguments():
 def test_slab_lists_are_refused(full):
     """A slab build, with and without nl_set_local_ids: NL_ERR_STATE from all four calls (fp of the ghosts is a halo exchange of
     the caller's)."""
-    from md_neighbor_list_amd._lib import NL_ERR_STATE, NLError
-    from tests.test_slab_paths import slab_parts
-
-    torch = _torch()
-    box, dtype, rc = "xyz", np.float32, 3.4
-    box6, mask = LJ_BOXES[box]
-    q = _input(box, False)
-    part = slab_parts(q[:, :3].astype(dtype), box6[:3], rc, ((0, 2), (2, 4)), mask)[0]
-    for local in (True, False):
-        nl = _handle(box, dtype, full, rc)
-        nl.set_local_ids(local)
-        nl.Initialize(N)
-        _set(nl, "one", rc)
-        qd = torch.from_numpy(np.ascontiguousarray(q[part["order"]].astype(dtype))).cuda()
-        nl.MakeNeighListSlab(qd, None, len(part["own"]), part["z_lo"], part["z_hi"])
-        if local:
-            assert torch.isfinite(nl.table_forces(qd)).all()  # (the pair table's calls take this list)
-        for call in (nl.eam_forces, nl.eam_virial):
-            for wait in (True, False):
-                with pytest.raises(NLError) as e:
-                    call(qd, wait=wait)
-                assert e.value.code == NL_ERR_STATE
+    contract.slab_lists_are_refused(EAM, full)
 
 
 @gpu
@@ -960,28 +816,4 @@ def test_slab_lists_are_refused(full):
 def test_distributed_lists_are_refused(full):
     """A distributed build of a world of one (nl_make_list_distributed: the whole box, the global ids in w): its list holds
     caller ids, and all four calls are NL_ERR_STATE, wait and enqueue."""
-    from md_neighbor_list_amd import _lib
-    from md_neighbor_list_amd._lib import NL_ERR_STATE
-
-    torch = _torch()
-    box, dtype, rc = "xyz", np.float32, 3.4
-    nl = _handle(box, dtype, full, rc)
-    nl.Initialize(N)
-    _set(nl, "one", rc)
-    lib = nl._lib
-    q = _input(box, False).astype(np.float32)
-    q[:, 3] = np.arange(N, dtype=np.int32).view(np.float32)  # NL_GID_IN_W
-    qd = torch.from_numpy(q).cuda()
-    fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
-    out = torch.empty(8, dtype=torch.float64, device="cuda")
-    cb = _lib.SENDRECV_FN(lambda *a: 1)  # (never called: a world of one exchanges nothing)
-    comm = C.c_void_p()
-    assert lib.nl_comm_create_callbacks(C.byref(comm), 0, 1, cb, None, torch.cuda.current_device()) == 0
-    try:
-        assert lib.nl_make_list_distributed(nl._h, comm, qd.data_ptr(), N, N, None, 1) == 0
-        npairs = C.c_int64()
-        assert lib.nl_number_of_pairs(nl._h, C.byref(npairs)) == 0 and npairs.value > 50 * N  # (the build succeeded: about 55 pairs a particle)
-        for fn, o in ((lib.nl_eam_forces, fd), (lib.nl_eam_forces_enqueue, fd), (lib.nl_eam_virial, out), (lib.nl_eam_virial_enqueue, out)):
-            assert fn(nl._h, qd.data_ptr(), 4, o.data_ptr(), None) == NL_ERR_STATE
-    finally:
-        lib.nl_comm_destroy(comm)
+    contract.distributed_lists_are_refused(EAM, full)

@@ -25,74 +25,20 @@ import functools
 import numpy as np
 import pytest
 
-from tests.util import (LJ_A, LJ_BOXES, LJ_C, LJ_L, LJ_M, check_lj, lj_band_particles, lj_drift, lj_emulate, lj_fold, lj_fractional,
-                        lj_lattice,
-                        lj_pairs, lj_ratio, lj_reference, lj_type_params, lj_unit, lj_wrap)
+from tests.consumer_util import CASES, EMULATED, N, PARS, RC_LISTS, RCF, _bonds, _dimers, _handle, _torch
+from tests.consumer_util import _lj_forces as _forces
+from tests.consumer_util import _lj_input as _input
+from tests.consumer_util import _lj_moved as _moved
+from tests.consumer_util import _lj_moved_pairs as _moved_pairs
+from tests.consumer_util import _lj_pairs as _pairs
+from tests.consumer_util import _lj_par as _par
+from tests.util import (LJ_A, LJ_BOXES, LJ_C, LJ_L, check_lj, lj_band_particles, lj_drift, lj_emulate, lj_fold, lj_fractional, lj_pairs,
+                        lj_ratio, lj_reference, lj_unit)
 
-RCF = 2.5
-RC_LISTS = (2.5, 3.4, 3.6)
-SEED = 11
-N = LJ_M ** 3
-PARS = ("scalar", "typed3", "typed32")
-CASES = [("open", False), ("xy", False), ("xy", True), ("xyz", False), ("xyz", True), ("tilt", False), ("tilt", True),
-         ("hex", False), ("hex", True)]
-# what the emulation that fixes c runs over: every box and mask in the box and drifted, scalars and both type tables
-EMULATED = [("xyz", False, "scalar"), ("xyz", True, "scalar"), ("tilt", False, "scalar"), ("tilt", True, "scalar"),
-            ("xy", True, "scalar"), ("hex", True, "scalar"), ("open", False, "scalar"), ("xyz", True, "typed3"),
-            ("tilt", True, "typed32")]
 EMULATED_MAX = 12.80  # the largest ratio of test_emulation_gives_c (force columns; energy 5.3)
 
 
-def _torch():
-    import torch
-
-    return torch
-
-
 # ------------------------------------------------------------------------------------------------ inputs, references
-@functools.lru_cache(maxsize=None)
-def _par(name, rc_list=3.4):
-    """(types, rc_ab, eps, sig, rcf) of a parameter set; scalars: (None, None, 1, 1, 2.5)."""
-    if name == "scalar":
-        return None, None, 1.0, 1.0, RCF
-    return lj_type_params(int(name[5:]), rc_list)
-
-
-@functools.lru_cache(maxsize=None)
-def _cuts():
-    """Every rc_force any case uses: the lattice keeps its pairs out of the band around each."""
-    c = {RCF}
-    for name in PARS[1:]:
-        c |= set(np.unique(_par(name)[4]).tolist()) - {0.0}
-    return tuple(sorted(c))
-
-
-@functools.lru_cache(maxsize=None)
-def _input(box, drift, shift=False):
-    """[n, 4] float64 holding float32 values.  shift: the lattice moved by a / 2 and wrapped, so that particles sit on
-    both sides of every periodic face (the skin tests)."""
-    box6, mask = LJ_BOXES[box]
-    if drift:
-        q = lj_drift(_input(box, False, shift), SEED + 1, box)
-        q[:, :3] = q[:, :3].astype(np.float32)
-        q.setflags(write=False)
-        return q
-    q = lj_lattice(SEED, box, cuts=_cuts()) if not shift else _input(box, False).copy()
-    if shift:
-        q[:, :3] = lj_wrap(q[:, :3] - 0.5 * LJ_A * np.array([mask & 1, mask >> 1 & 1, mask >> 2 & 1]), box6, mask)
-    q[:, :3] = q[:, :3].astype(np.float32)
-    q.setflags(write=False)
-    return q
-
-
-@functools.lru_cache(maxsize=None)
-def _pairs(box, drift, shift=False):
-    box6, mask = LJ_BOXES[box]
-    p = lj_pairs(_input(box, drift, shift), box6, mask, max(RC_LISTS))
-    assert not len(lj_band_particles(None, box6, mask, _cuts(), 2.0 ** -17, pairs=p)), "a pair in the band of a cut-off"
-    return p
-
-
 @functools.lru_cache(maxsize=None)
 def _ref(box, drift, par, shift=False):
     box6, mask = LJ_BOXES[box]
@@ -287,44 +233,6 @@ def test_inputs():
 
 
 # ------------------------------------------------------------------------------------------------------ GPU helpers
-def _handle(box, dtype, full, rc, off=0, images=False):
-    torch = _torch()
-    from md_neighbor_list_amd import NeighListGPU
-
-    box6, mask = LJ_BOXES[box]
-    axes = tuple(bool(mask >> a & 1) for a in range(3))
-    nl = NeighListGPU(rc, *box6[:3], dtype=torch.float32 if dtype == np.float32 else torch.float64, full_list=full,
-                      minimum_image=axes if mask else False, tilt=box6[3:])
-    if off:
-        nl.set_offset_width(off)
-    if images:
-        nl.set_pair_images(True)
-    return nl
-
-
-def _forces(q, box, dtype, full, rc, par, off=0, stride=4, exclusions=None):
-    """(handle, device positions, forces on the host) of one build and one blocking consumer call."""
-    torch = _torch()
-    n = len(q)
-    nl = _handle(box, dtype, full, rc, off)
-    nl.Initialize(n)
-    types, _, eps, sig, rcf = _par(par, rc)
-    if types is not None:
-        nl.set_type_cutoffs(types, _par(par, rc)[1])
-    if exclusions is not None:
-        nl.set_exclusions(exclusions, n)
-    qd = torch.from_numpy(np.ascontiguousarray(q[:, :stride].astype(dtype))).cuda()
-    nl.MakeNeighList(qd, n)
-    if off:
-        assert nl.build_info()["offset_bits"] == off
-    if types is not None:
-        nl.set_lj_type_params(eps, sig, rcf)
-        f = nl.lj_forces_typed(qd)
-    else:
-        f = nl.lj_forces(qd, 1.0, 1.0, rc_force=RCF)
-    return nl, qd, f.cpu().numpy()
-
-
 def _check_sums(got, want, S, dtype):
     """Total force within c u sum_i S_i of zero's float64 value, total energy within the same kind of bound."""
     u = lj_unit(dtype)
@@ -372,39 +280,6 @@ def test_offsets_strides_and_type_counts(full, dtype):
                 check_lj(got, *want[par], dtype)
 
 
-def _dimers(dtype, box6, mask, seed=5):
-    """Two-particle molecules on a 6^3 grid of spacing 10.5 (L = 63), on grid points i * 10.5: those with i = 0 straddle a
-    face, two or three of them an edge or the corner.  Coordinates are multiples of 2^-16 (fp32) / 2^-45 (fp64), so the
-    separations and their folds are exact in the position type and the comparison is of lj_pair alone.  Returns
-    (q[2 m, 4] with partners adjacent, group per dimer): 0 = r in [0.9, rc_force (1 - 2^-10)], 1 = below the band
-    rc_force (1 - k s), 2 = above it (4 <= k <= 64; s = 2^-20 for fp32, 2^-49 for fp64), 3 = coincident."""
-    rng = np.random.default_rng(seed)
-    grid, s = (2.0 ** -16, 2.0 ** -20) if dtype == np.float32 else (2.0 ** -45, 2.0 ** -49)
-    g = np.stack(np.meshgrid(*(np.arange(6),) * 3, indexing="ij"), axis=-1).reshape(-1, 3)
-    if not mask:
-        g = g + 0.5  # (an open box: every molecule inside)
-    mid = g * 10.5
-    m = len(mid)
-    group = rng.permutation(np.arange(m) % 8)
-    group = np.where(group < 4, 0, np.where(group < 6, 1, np.where(group == 6, 2, 3)))
-    u = rng.normal(size=(m, 3))
-    u = np.where(np.abs(u) < 0.2, 0.2, u)  # (every component takes part: a molecule on a face crosses it)
-    u /= np.linalg.norm(u, axis=1)[:, None]
-    k = rng.uniform(12.0, 56.0, size=m)
-    r = np.where(group == 0, rng.uniform(0.9, RCF * (1 - 2.0 ** -10), size=m),
-                 np.where(group == 1, RCF * (1 - k * s), np.where(group == 2, RCF * (1 + k * s), 0.0)))
-    p1 = np.round((mid - 0.5 * r[:, None] * u) / grid) * grid
-    p2 = np.round((p1 + r[:, None] * u) / grid) * grid
-    p2[group == 3] = p1[group == 3]
-    got = np.sqrt(((p2 - p1) ** 2).sum(axis=1)) / RCF - 1.0
-    assert np.all((got[group == 1] <= -4 * s) & (got[group == 1] >= -64 * s))
-    assert np.all((got[group == 2] >= 4 * s) & (got[group == 2] <= 64 * s))
-    q = np.zeros((2 * m, 4))
-    q[0::2, :3], q[1::2, :3] = p1, p2
-    q[:, :3] = lj_wrap(q[:, :3], box6, mask)
-    return q, group, np.flatnonzero((g >= 1).all(axis=1))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("full", [False, True])
@@ -442,31 +317,6 @@ def test_isolated_dimers(box, full, dtype):
         check_lj(got, want, S, dtype)
         assert np.all(got[np.repeat(group >= 2, 2)] == 0)
         assert np.array_equal(got[0::2, :3], -got[1::2, :3]) and np.array_equal(got[0::2, 3], got[1::2, 3])
-
-
-@functools.lru_cache(maxsize=None)
-def _moved(box, step=0.03, seed=21):
-    """The shifted lattice of `box` with every particle moved by up to `step` per axis (far below skin / 2 = 0.2): particles
-    leave through the faces, pairs cross rc_force both ways, none ends in the band of a cut-off."""
-    box6, mask = LJ_BOXES[box]
-    q0 = _input(box, False, True)
-    rng = np.random.default_rng(seed)
-    q = q0.copy()
-    todo = np.arange(N)
-    for _ in range(20):
-        q[todo, :3] = (q0[todo, :3] + rng.uniform(-step, step, size=(len(todo), 3))).astype(np.float32)
-        todo = lj_band_particles(q, box6, mask, _cuts(), 2.0 ** -15, rows=todo)
-        if not len(todo):
-            break
-    assert not len(todo)
-    q.setflags(write=False)
-    return q
-
-
-@functools.lru_cache(maxsize=None)
-def _moved_pairs(box):
-    box6, mask = LJ_BOXES[box]
-    return lj_pairs(_moved(box), box6, mask, RCF)
 
 
 def test_moved_input():
@@ -518,13 +368,6 @@ def test_reuse_within_the_skin(box, images, full, dtype):
         assert nl.update_stats()[1] == builds
         want, S = lj_reference(q1, box6, mask, eps, sig, rcf, types=types, pairs=_moved_pairs(box))
         check_lj(f.cpu().numpy(), want, S, dtype)
-
-
-@functools.lru_cache(maxsize=None)
-def _bonds():
-    """1-2 bonds along x of the lattice: every site with its +x neighbour, periodic."""
-    idx = np.arange(N).reshape(LJ_M, LJ_M, LJ_M)
-    return np.stack([idx.ravel(), np.roll(idx, -1, axis=0).ravel()], axis=1).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=None)

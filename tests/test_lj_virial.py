@@ -30,14 +30,18 @@ import re
 import numpy as np
 import pytest
 
-from tests.test_lj_consumer import (CASES, EMULATED, N, PARS, RC_LISTS, RCF, _bonds, _dimers, _forces, _handle, _input, _moved,
-                                    _moved_pairs, _pairs, _par, _torch)
+from tests.consumer_util import BIG_BOX, CASES, DTYPES, EMULATED, N, PARS, RC_LISTS, RCF, _big, _bonds, _dimers, _handle, _tdt, _torch
+from tests.consumer_util import NBLK_VIRIAL as NBLK
+from tests.consumer_util import _lj_forces as _forces
+from tests.consumer_util import _lj_input as _input
+from tests.consumer_util import _lj_moved as _moved
+from tests.consumer_util import _lj_moved_pairs as _moved_pairs
+from tests.consumer_util import _lj_pairs as _pairs
+from tests.consumer_util import _lj_par as _par
 from tests.util import LJ_BOXES, LJ_C, LJ_L, ROOT, lj_band_particles, lj_drift, lj_emulate, lj_pairs, lj_unit
 from tests.virial_util import VIR_C, check_virial, emulate_pairs, virial_emulate, virial_ratio, virial_reference
 
 EMULATED_MAX = 11.9  # the largest per-row ratio of test_emulation_gives_c
-NBLK = 2048  # NL_VIRIAL_BLOCKS of include/nl_hip.h: the most blocks of 4 waves k_lj_virial is launched with
-DTYPES = [np.float32, np.float64]
 
 
 # ------------------------------------------------------------------------------------------------ inputs, references
@@ -60,23 +64,6 @@ def _moved_vref(box, par, seed=21):
     types, _, eps, sig, rcf = _par(par)
     pairs = _moved_pairs(box) if seed == 21 else lj_pairs(_moved(box, 0.03, seed), box6, mask, RCF)
     return virial_reference(_moved(box, 0.03, seed), box6, mask, eps, sig, rcf, types=types, pairs=pairs)
-
-
-BIG_BOX = ((2 * LJ_L, 2 * LJ_L, LJ_L, 0.0, 0.0, 0.0), 7)
-
-
-@functools.lru_cache(maxsize=None)
-def _big():
-    """The "xyz" lattice tiled 2 x 2 x 1 and rounded to float32 again (coordinates in [16, 32) lose a bit): n = 10976 rows
-    for at most 4 NBLK = 8192 waves, so waves take a second row and the last turn is ragged.  (q, reference)"""
-    base = _input("xyz", False)
-    q = np.concatenate([base + np.array([ix * LJ_L, iy * LJ_L, 0.0, 0.0]) for ix in range(2) for iy in range(2)])
-    q[:, :3] = q[:, :3].astype(np.float32)
-    box6, mask = BIG_BOX
-    pairs = lj_pairs(q, box6, mask, RCF * (1 + 2.0 ** -16))
-    assert not len(lj_band_particles(None, box6, mask, (RCF,), 2.0 ** -17, pairs=pairs)), "a pair in the band of the cut-off"
-    q.setflags(write=False)
-    return q, virial_reference(q, box6, mask, 1.0, 1.0, RCF, pairs=pairs)
 
 
 def _weakest(par):
@@ -271,11 +258,6 @@ def test_wrong_results_are_rejected():
 
 
 # ------------------------------------------------------------------------------------------------------ GPU helpers
-def _tdt(dtype):
-    torch = _torch()
-    return torch.float32 if dtype == np.float32 else torch.float64
-
-
 def _virial(nl, qd, par, **kw):
     """The wrapper call of a parameter set (after _forces, which sets the tables), as a device tensor."""
     return nl.lj_virial_typed(qd, **kw) if par != "scalar" else nl.lj_virial(qd, 1.0, 1.0, rc_force=RCF, **kw)

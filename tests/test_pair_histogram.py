@@ -18,14 +18,13 @@ import pytest
 
 from md_neighbor_list_amd import rdf as R
 from tests.hist_util import CAP, band_fraction, check_hist, hist_bands, hist_count, hist_edges2, hist_merge, hist_r2, hist_rho
-from tests.test_lj_consumer import N, SEED, _bonds, _handle, _input, _moved, _torch
-from tests.test_lj_virial import BIG_BOX, NBLK, _big
+from tests.consumer_util import BIG_BOX, DTYPES, HIST_INPUTS, N, SEED, _big, _bonds, _handle, _torch
+from tests.consumer_util import NBLK_VIRIAL as NBLK
+from tests.consumer_util import _lj_input as _input
+from tests.consumer_util import _lj_moved as _moved
 from tests.util import LJ_BOXES, LJ_L, ROOT, lj_drift, lj_lattice, lj_pairs, lj_type_params
 
-DTYPES = [np.float32, np.float64]
 RC = 3.4  # the list cut-off of the designed inputs (rc_ab of lj_type_params(nt, 3.4) too)
-# box: (r_max, nbins); every edge, 2.5 and 3.4 are cuts of the lattice.  ("hex" is the "xyz" shape on the sheared film.)
-HIST_INPUTS = {"xyz": (2.5, 50), "tilt": (3.0, 64), "open": (2.5, 7), "xy": (3.4, 128), "hex": (2.5, 50)}
 MATRIX = [(box, drift) for box in HIST_INPUTS for drift in (False, True) if drift <= (LJ_BOXES[box][1] != 0)]
 MAX_BINS, LDS_COUNTERS = 4096, 4096  # include/nl_hip.h (test_header_constants)
 

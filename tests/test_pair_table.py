@@ -31,23 +31,19 @@ import numpy as np
 import pytest
 
 from md_neighbor_list_amd import pair_table, rdf
-from tests.test_lj_consumer import _handle, _torch
-from tests.util import (LJ_BOXES, LJ_C, LJ_M, ROOT, check_lj, lj_band_particles, lj_drift, lj_lattice, lj_pairs, lj_ratio,
-                        lj_reference, lj_type_params, lj_unit)
+from tests import consumer_contract as contract
+from tests.consumer_util import CASES, DTYPES, N, NK, R_MAX, R_MIN, _handle, _off_the_band, _tab, _tdt, _torch
+from tests.consumer_util import _table_input as _input
+from tests.consumer_util import _table_moved as _moved
+from tests.consumer_util import _table_pairs as _pairs
+from tests.util import LJ_BOXES, LJ_C, LJ_M, ROOT, check_lj, lj_pairs, lj_ratio, lj_reference, lj_type_params, lj_unit
 from tests.util_table import (TABLE_C, TABLE_CW, lj, lj_f_xx, lj_u_xx, morse, table_emulate, table_emulate_pairs, table_pairs,
                               table_reference, table_virial_emulate, table_virial_reference)
 from tests.virial_util import check_virial, virial_ratio
 
-R_MIN, R_MAX = 0.85, 2.5
-NK = 1024
-SEED = 11
-N = LJ_M ** 3
 NBLK = 512  # NL_TABLE_BLOCKS of include/nl_hip.h
 RC_LISTS = (2.5, 3.4)
-DTYPES = [np.float32, np.float64]
 TABS = ("morse", "lj", "typed3")
-CASES = [("open", False), ("xy", False), ("xy", True), ("xyz", False), ("xyz", True), ("tilt", False), ("tilt", True),
-         ("hex", False), ("hex", True)]
 # what the emulation that fixes TABLE_C and TABLE_CW runs over
 EMULATED = [("open", False, "morse"), ("open", False, "lj"), ("xyz", False, "morse"), ("xyz", True, "lj"), ("tilt", False, "lj"),
             ("tilt", True, "morse"), ("xyz", True, "typed3"), ("tilt", True, "typed3")]
@@ -55,65 +51,6 @@ EMULATED_MAX, EMULATED_MAX_W = 2.67, 0.487  # the largest ratios of test_emulati
 
 
 # ------------------------------------------------------------------------------------------------ inputs, references
-@functools.lru_cache(maxsize=None)
-def _tab(name, nk=NK):
-    """(F, U, types, rc_ab(rc_list)) of a table on the grid (R_MIN, R_MAX, nk).  typed3: a Morse potential per pair of 3
-    types, the slot of the pair (0, 2) -- which the type table leaves out of the list -- zero."""
-    if name in ("morse", "lj"):
-        F, U = pair_table.sample(*(morse() if name == "morse" else lj()), R_MIN, R_MAX, nk)
-        return F, U, None, None
-    nt = int(name[5:])
-    types = lj_type_params(nt, 3.4)[0]
-    rows = [pair_table.sample(*morse(De=1.0 + 0.2 * (s % 5), a=1.5, r0=1.05 + 0.03 * (s % 6)), R_MIN, R_MAX, nk) for s in range(rdf.nslots(nt))]
-    F, U = np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
-    F[rdf.slot(0, nt - 1, nt)] = U[rdf.slot(0, nt - 1, nt)] = 0.0
-
-    def rc_ab(rc_list):
-        rc = np.full((nt, nt), float(rc_list))
-        rc[0, nt - 1] = rc[nt - 1, 0] = 0.0
-        return rc
-
-    return F, U, types, rc_ab
-
-
-@functools.lru_cache(maxsize=None)
-def _input(box, drift):
-    """[n, 4] float64 holding float32 values."""
-    q = lj_drift(_input(box, False), SEED + 1, box) if drift else lj_lattice(SEED, box, cuts=(R_MIN, R_MAX))
-    q[:, :3] = q[:, :3].astype(np.float32)
-    q.setflags(write=False)
-    return q
-
-
-def _off_the_band(q, box6, mask, pairs):
-    return not len(lj_band_particles(None, box6, mask, (R_MIN, R_MAX), 2.0 ** -17, pairs=pairs))
-
-
-@functools.lru_cache(maxsize=None)
-def _pairs(box, drift):
-    box6, mask = LJ_BOXES[box]
-    p = lj_pairs(_input(box, drift), box6, mask, R_MAX * (1 + 2.0 ** -16))
-    assert _off_the_band(None, box6, mask, p), "a pair in the band of r_max or r_min"
-    return p
-
-
-@functools.lru_cache(maxsize=None)
-def _moved(box, seed=21, step=0.03):
-    """The lattice of `box` with every particle moved by up to `step` per axis (far below skin / 2), none into the band."""
-    box6, mask = LJ_BOXES[box]
-    q0 = _input(box, False)
-    rng = np.random.default_rng(seed)
-    q, todo = q0.copy(), np.arange(N)
-    for _ in range(20):
-        q[todo, :3] = (q0[todo, :3] + rng.uniform(-step, step, size=(len(todo), 3))).astype(np.float32)
-        todo = lj_band_particles(q, box6, mask, (R_MIN, R_MAX), 2.0 ** -15, rows=todo)
-        if not len(todo):
-            break
-    assert not len(todo)
-    q.setflags(write=False)
-    return q, lj_pairs(q, box6, mask, R_MAX * (1 + 2.0 ** -16))
-
-
 def _refs(q, box, tab, pairs, nk=NK):
     box6, mask = LJ_BOXES[box]
     F, U, types, rc_ab = _tab(tab, nk)
@@ -321,27 +258,12 @@ def test_wrong_results_are_rejected():
 
 
 # ------------------------------------------------------------------------------------------------------ GPU helpers
-def _tdt(dtype):
-    return _torch().float32 if dtype == np.float32 else _torch().float64
-
-
 def _set(nl, tab, rc, nk=NK):
     """The table (and, for a typed one, the type table at the list's cut-off) onto a handle that has been initialised."""
     F, U, types, rc_ab = _tab(tab, nk)
     if types is not None:
         nl.set_type_cutoffs(types, rc_ab(rc))
     nl.set_pair_table(F, U, R_MIN, R_MAX)
-
-
-def _built(q, box, dtype, full, rc, tab, off=0, stride=4, nk=NK):
-    """(handle, device positions) after one build, the table set."""
-    torch = _torch()
-    nl = _handle(box, dtype, full, rc, off)
-    nl.Initialize(len(q))
-    _set(nl, tab, rc, nk)
-    qd = torch.from_numpy(np.ascontiguousarray(q[:, :stride].astype(dtype))).cuda()
-    nl.MakeNeighList(qd, len(q))
-    return nl, qd
 
 
 def _check(f, w, refs, dtype, rows=None):
@@ -355,6 +277,12 @@ def _check(f, w, refs, dtype, rows=None):
     return f, w
 
 
+TABLE = contract.Consumer(
+    forces="table_forces", virial="table_virial", scratch="table_virial", clear="clear_pair_table", info="pair_table",
+    entry=("nl_table_forces", "nl_table_forces_enqueue", "nl_table_virial", "nl_table_virial_enqueue"), set=_set, kinds=TABS, ref=_ref,
+    moved_ref=_moved_ref, extra=lambda nl: (), check=lambda f, w, x, refs, dtype, rows=None: _check(f, w, refs, dtype, rows),
+    half_lists=True, local_slabs=True)
+_built = functools.partial(contract.built, TABLE)
 gpu = pytest.mark.gpu
 
 
@@ -503,23 +431,7 @@ def test_a_pair_below_the_table(full, dtype):
 @pytest.mark.parametrize("full", [False, True])
 @pytest.mark.parametrize("box,tab", [("xyz", "morse"), ("tilt", "typed3")])
 def test_reuse_within_the_skin(box, tab, full, dtype):
-    """A list kept by nl_update_list, read at moved positions by the enqueue variants; no extra build."""
-    torch = _torch()
-    q1 = _moved(box)[0]
-    nl = _handle(box, dtype, full, 2.9)
-    nl.set_skin(0.4)
-    nl.Initialize(N)
-    _set(nl, tab, 2.9)
-    qd = torch.from_numpy(_input(box, False).astype(dtype)).cuda()
-    nl.update(qd, sync=True)
-    builds = nl.update_stats()[1]
-    nl.table_virial(qd)  # (the scratch of the totals)
-    qd.copy_(torch.from_numpy(q1.astype(dtype)))
-    nl.update(qd)
-    f, w = nl.table_forces(qd, wait=False), nl.table_virial(qd, wait=False)
-    torch.cuda.synchronize()
-    assert nl.update_stats()[1] == builds
-    _check(f, w, _moved_ref(box, tab), dtype)
+    contract.reuse_within_the_skin(TABLE, box, tab, full, dtype)
 
 
 @gpu
@@ -527,65 +439,26 @@ def test_reuse_within_the_skin(box, tab, full, dtype):
 def test_captured(full):
     """One graph holds the copy of the positions, the update, the forces and the totals; replayed at two position sets.  A
     table of the same size set afterwards keeps the device buffer: the next replay computes with the new table."""
-    torch = _torch()
-    dtype = np.float32
-    sets = [(_input("xyz", False), _ref("xyz", False, "morse")), (_moved("xyz")[0], _moved_ref("xyz", "morse"))]
-    nl = _handle("xyz", dtype, full, 2.9)
-    nl.set_skin(0.4)
-    nl.Initialize(N)
-    _set(nl, "morse", 2.9)
-    src = torch.from_numpy(sets[0][0].astype(dtype)).cuda()
-    qd = src.clone()
-    fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
-    wd = torch.empty(8, dtype=torch.float64, device="cuda")
-    nl.update(qd, sync=True)
-    nl.update(qd)
-    nl.table_virial(qd, wait=False, out=wd)  # once before the capture: the scratch exists
-    nl.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        qd.copy_(src)
-        nl.update(qd)
-        nl.table_forces(qd, wait=False, out=fd)
-        nl.table_virial(qd, wait=False, out=wd)
-    for q, refs in sets:
-        src.copy_(torch.from_numpy(q.astype(dtype)))
-        fd.fill_(-1.0), wd.fill_(-1.0)
-        g.replay()
-        torch.cuda.synchronize()
-        _check(fd, wd, refs, dtype)
-    nl.set_pair_table(*_tab("lj")[:2], R_MIN, R_MAX)
-    fd.fill_(-1.0), wd.fill_(-1.0)
-    g.replay()
-    torch.cuda.synchronize()
-    _check(fd, wd, _moved_ref("xyz", "lj"), dtype)
+    def before(nl, qd, fd, wd):
+        nl.table_virial(qd, wait=False, out=wd)  # once before the capture: the scratch exists
+        nl.synchronize()
+
+    def after(nl, replay):
+        nl.set_pair_table(*_tab("lj")[:2], R_MIN, R_MAX)
+        _check(*replay(), _moved_ref("xyz", "lj"), np.float32)
+
+    contract.captured(TABLE, full, before, after)
 
 
 @gpu
 def test_failed_list():
     """An enqueue behind an asynchronous build that overflowed its capacity: NaN forces and 8 NaN totals, NL_ERR_CAPACITY at
     synchronize; after the synchronous repeat both are finite."""
-    from md_neighbor_list_amd import NeighListGPU, inputs
-    from md_neighbor_list_amd._lib import NL_ERR_CAPACITY, NLError
+    def set_tables(nl):
+        F, U = pair_table.sample(*morse(), 1e-3, R_MAX, NK)  # (a uniform random box has close pairs: the table starts near 0)
+        nl.set_pair_table(F, U, 1e-3, R_MAX)
 
-    torch = _torch()
-    q, box = inputs.uniform_box(20000, dtype=np.float32, seed=28, box=(28.0, 28.0, 28.0))
-    nl = NeighListGPU(3.3, *box, dtype=torch.float32)
-    nl.set_skin(0.4)
-    nl.Initialize(len(q))
-    F, U = pair_table.sample(*morse(), 1e-3, R_MAX, NK)  # (a uniform random box has close pairs: the table starts near 0)
-    nl.set_pair_table(F, U, 1e-3, R_MAX)
-    nl.set_capacity(1000)
-    qd = torch.from_numpy(q).cuda()
-    nl.update(qd)
-    f, w = nl.table_forces(qd, wait=False), nl.table_virial(qd, wait=False)
-    with pytest.raises(NLError) as e:
-        nl.synchronize()
-    assert e.value.code == NL_ERR_CAPACITY
-    assert torch.isnan(f).all() and f.shape == (len(q), 4) and torch.isnan(w).all() and w.shape == (8,)
-    nl.update(qd, sync=True)  # grows the list
-    f, w = nl.table_forces(qd, wait=False), nl.table_virial(qd, wait=False)
-    assert torch.isfinite(f).all() and torch.isfinite(w).all() and w[7] > 0
+    contract.failed_list(TABLE, set_tables, lambda nl, qd: None)  # (no scratch before the capacity shrinks)
 
 
 @gpu
@@ -627,6 +500,7 @@ def test_state_and_arguments():
     torch = _torch()
     lib = load()
     F, U, _, _ = _tab("morse")
+    F3, U3, types, _ = _tab("typed3")
     q = _input("open", False)
     nl = _handle("open", np.float32, False, 2.9)
     nl.set_skin(0.3)
@@ -634,7 +508,8 @@ def test_state_and_arguments():
     qd = torch.from_numpy(q.astype(np.float32)).cuda()
     fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
     out = torch.empty(8, dtype=torch.float64, device="cuda")
-    calls = [(lib.nl_table_forces, fd), (lib.nl_table_forces_enqueue, fd), (lib.nl_table_virial, out), (lib.nl_table_virial_enqueue, out)]
+    calls = contract.entry_calls(TABLE, lib, fd, out)
+    set_one = lambda: nl.set_pair_table(F, U, R_MIN, R_MAX)  # noqa: E731
     # no table: the getter, the wrapper, and the calls after a build
     assert nl.pair_table() is None
     assert lib.nl_get_pair_table(nl._h, None, None, None, None) == NL_ERR_STATE
@@ -663,61 +538,12 @@ def test_state_and_arguments():
         nl.set_pair_table(F, U[:-1], R_MIN, R_MAX)
     with pytest.raises(TypeError):
         nl.set_pair_table(np.zeros((4, 8)), np.zeros((4, 8)), R_MIN, R_MAX)  # 4 rows are no ntypes (ntypes + 1) / 2
-    # the calls' arguments
-    for fn, o in calls:
-        assert fn(nl._h, qd.data_ptr(), 4, None, None) == NL_ERR_ARG
-        assert fn(nl._h, None, 4, o.data_ptr(), None) == NL_ERR_ARG
-        assert fn(None, qd.data_ptr(), 4, o.data_ptr(), None) == NL_ERR_ARG
-        for stride in (0, 2, 5):
-            assert fn(nl._h, qd.data_ptr(), stride, o.data_ptr(), None) == NL_ERR_ARG
-    # the setter does not touch the list: an update after it builds nothing
-    nl.update(qd, sync=True)
-    builds = nl.update_stats()[1]
-    nl.set_pair_table(F, U, R_MIN, R_MAX)
-    nl.update(qd, sync=True)
-    assert nl.update_stats()[1] == builds
-    # reach: rc = 2.9, skin = 0.3 -- r_max = 2.6 is within rc and within rc - skin, 2.7 only within rc, 3.0 within neither
-    for r_max, sync_ok, enq_ok in ((2.6, True, True), (2.7, True, False), (2.9, True, False), (3.0, False, False)):
-        nl.set_pair_table(*pair_table.sample(*morse(), R_MIN, r_max, NK), R_MIN, r_max)
-        for wait, ok in ((True, sync_ok), (False, enq_ok)):
-            for call in (nl.table_forces, nl.table_virial):
-                if ok:
-                    call(qd, wait=wait)
-                else:
-                    with pytest.raises(NLError) as e:
-                        call(qd, wait=wait)
-                    assert e.value.code == NL_ERR_ARG, (r_max, wait)
-    # clearing, both ways
-    nl.set_pair_table(F, U, R_MIN, R_MAX)
-    nl.clear_pair_table()
-    assert nl.pair_table() is None
-    nl.set_pair_table(F, U, R_MIN, R_MAX)
-    assert lib.nl_set_pair_table(nl._h, 1, 0, R_MIN, R_MAX, dp(F), dp(U)) == 0 and nl.pair_table() is None
-    for wait in (True, False):
-        with pytest.raises(NLError) as e:
-            nl.table_forces(qd, wait=wait)
-        assert e.value.code == NL_ERR_STATE
-    # a table of several types: needs a type table of its ntypes; a scalar table works with one set
-    F3, U3, types, rc_ab = _tab("typed3")
-    nl.set_pair_table(F3, U3, R_MIN, R_MAX)
-    for call in (nl.table_forces, nl.table_virial):
-        with pytest.raises(NLError) as e:
-            call(qd)
-        assert e.value.code == NL_ERR_STATE
-    nl.set_type_cutoffs(types % 2, [[2.9, 2.9], [2.9, 2.9]])
-    nl.MakeNeighList(qd, N)
-    with pytest.raises(NLError) as e:
-        nl.table_forces(qd)
-    assert e.value.code == NL_ERR_ARG  # ntypes 3 against the type table's 2
-    nl.set_pair_table(F, U, R_MIN, R_MAX)
-    assert torch.isfinite(nl.table_forces(qd)).all()
-    nl.set_type_cutoffs(types, [[2.9, 2.9, 0.0], [2.9, 2.55, 2.9], [0.0, 2.9, 2.9]])  # rc_ab: one pair short of r_max + skin
-    nl.MakeNeighList(qd, N)
-    nl.set_pair_table(F3, U3, R_MIN, R_MAX)
-    assert torch.isfinite(nl.table_virial(qd)).all()  # 2.5 <= 2.55; the pair with rc_ab = 0 has no entries
-    with pytest.raises(NLError) as e:
-        nl.table_virial(qd, wait=False)  # 2.5 > 2.55 - 0.3
-    assert e.value.code == NL_ERR_ARG
+    contract.call_arguments(calls, nl, qd)
+    contract.setter_keeps_the_list(nl, qd, set_one)
+    contract.reach(TABLE, nl, qd, lambda r_max: nl.set_pair_table(*pair_table.sample(*morse(), R_MIN, r_max, NK), R_MIN, r_max))
+    set_one()
+    contract.clearing(TABLE, nl, qd, set_one, lambda: lib.nl_set_pair_table(nl._h, 1, 0, R_MIN, R_MAX, dp(F), dp(U)))
+    contract.several_types(TABLE, nl, qd, types, set_one, lambda: nl.set_pair_table(F3, U3, R_MIN, R_MAX))
     # a first call of the totals inside a capture, on a handle whose scratch does not exist yet
     fresh = _handle("open", np.float32, False, 2.9)
     fresh.Initialize(N)
@@ -729,13 +555,4 @@ def test_state_and_arguments():
             fresh.table_virial(qd, wait=False)
         fresh.table_forces(qd, wait=False, out=fd)
     assert e.value.code == NL_ERR_STATE
-    # n == 0
-    empty = _handle("open", np.float32, False, 2.9)
-    empty.Initialize(16)
-    empty.set_pair_table(F, U, R_MIN, R_MAX)
-    empty.MakeNeighList(torch.zeros((0, 4), dtype=torch.float32, device="cuda"))
-    out.fill_(7.0)  # (an empty tensor has no address to pass: the positions are not read)
-    assert lib.nl_table_virial(empty._h, qd.data_ptr(), 4, out.data_ptr(), None) == 0
-    assert lib.nl_table_forces(empty._h, qd.data_ptr(), 4, fd.data_ptr(), None) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(out.cpu().numpy(), np.zeros(8))
+    contract.no_particles(TABLE, lib, False, lambda empty: empty.set_pair_table(F, U, R_MIN, R_MAX), qd, fd, out)

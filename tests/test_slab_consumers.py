@@ -16,10 +16,9 @@ import functools
 import numpy as np
 import pytest
 
+from tests.consumer_util import HIST_INPUTS, _handle, _torch
 from tests.hist_util import check_hist, hist_count, hist_r2
 from tests.slab_consumer_util import local_pairs, rank_forces, rank_hist_r2, rank_split, rank_virial, within
-from tests.test_lj_consumer import _handle, _torch
-from tests.test_pair_histogram import HIST_INPUTS
 from tests.test_slab_paths import slab_parts
 from tests.util import LJ_BOXES, LJ_M, check_lj, lj_drift, lj_lattice, lj_pairs, lj_reference
 from tests.virial_util import check_virial, virial_reference

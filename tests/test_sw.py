@@ -31,8 +31,11 @@ import numpy as np
 import pytest
 
 from md_neighbor_list_amd import pair_table, sw
-from tests.test_lj_consumer import _bonds, _handle, _torch
-from tests.test_pair_table import CASES, DTYPES, N, NK, R_MAX, R_MIN, _input, _moved, _pairs, _tab
+from tests import consumer_contract as contract
+from tests.consumer_util import CASES, DTYPES, N, NK, R_MAX, R_MIN, _bonds, _handle, _pair_tab, _tab, _torch
+from tests.consumer_util import _table_input as _input
+from tests.consumer_util import _table_moved as _moved
+from tests.consumer_util import _table_pairs as _pairs
 from tests.util import LJ_A, LJ_BOXES, LJ_M, ROOT, check_lj, lj_pairs, lj_ratio, lj_unit
 from tests.util_sw import (A_SIGMA, DEFECTS, SW_C, SW_CW, SwTables, sw_angular, sw_emulate, sw_energy, sw_functions, sw_reference)
 from tests.util_table import morse
@@ -54,7 +57,6 @@ def _tabs(kind, nk=NK, r_max_3=R_MAX, r_max_pair=R_MAX, r_min_pair=R_MIN, r_min_
     nt = 1 if kind == "one" else 3
     F, U, types, rc_ab = _tab("morse" if nt == 1 else "typed3", nk)
     if (r_min_pair, r_max_pair) != (R_MIN, R_MAX):
-        from tests.test_eam import _pair_tab
         F, U = _pair_tab(nt, r_min_pair, r_max_pair, nk)
     gs, dgs = sw_functions(nt)
     g, G = sw.sample(gs, dgs, r_min_3, r_max_3, nk) if nt > 1 else sw.sample(gs[0][0], dgs[0][0], r_min_3, r_max_3, nk)
@@ -389,10 +391,6 @@ def test_the_edge_inputs():
 
 
 # ------------------------------------------------------------------------------------------------------ GPU helpers
-def _tdt(dtype):
-    return _torch().float32 if dtype == np.float32 else _torch().float64
-
-
 def _set_tab(nl, tab):
     nl.set_pair_table(tab.F if tab.nt_pair > 1 else tab.F[0], tab.U if tab.nt_pair > 1 else tab.U[0], tab.r_min, tab.r_max)
     nl.set_sw(tab.g, tab.G, tab.r_min_3, tab.r_max_3, tab.lam, tab.cos0)
@@ -439,11 +437,12 @@ def _check(f, w, ref, dtype, rows=None):
     return f, w
 
 
-def _run(nl, qd, ref, dtype, wait=True, rows=None):
-    f = nl.sw_forces(qd, wait=wait)
-    w = nl.sw_virial(qd, wait=wait)
-    assert f.shape == (len(ref["want"]), 4) and f.dtype == _tdt(dtype) and w.shape == (8,) and w.dtype == _torch().float64
-    return _check(f, w, ref, dtype, rows)
+SW = contract.Consumer(
+    forces="sw_forces", virial="sw_virial", scratch="sw_virial", clear="clear_sw", info="sw",
+    entry=("nl_sw_forces", "nl_sw_forces_enqueue", "nl_sw_virial", "nl_sw_virial_enqueue"), set=_set, kinds=KINDS, ref=_ref,
+    moved_ref=_moved_ref, extra=lambda nl: (), check=lambda f, w, x, ref, dtype, rows=None: _check(f, w, ref, dtype, rows),
+    half_lists=False, local_slabs=False)
+_run = functools.partial(contract.run, SW)
 
 
 def _assert_nan_pattern(f, w, ref, dtype):
@@ -600,23 +599,7 @@ def test_exclusions(dtype):
 @pytest.mark.parametrize("box,kind", [("xyz", "one"), ("tilt", "three")])
 def test_reuse_within_the_skin(box, kind, dtype):
     """A list kept by nl_update_list, read at moved positions by the enqueue variants; no extra build."""
-    torch = _torch()
-    q1 = _moved(box)[0]
-    nl = _handle(box, dtype, True, 2.9)
-    nl.set_skin(0.4)
-    nl.Initialize(N)
-    _set(nl, kind, 2.9)
-    qd = torch.from_numpy(_input(box, False).astype(dtype)).cuda()
-    nl.update(qd, sync=True)
-    builds = nl.update_stats()[1]
-    nl.sw_virial(qd)  # (the scratch)
-    qd.copy_(torch.from_numpy(q1.astype(dtype)))
-    nl.update(qd)
-    f = nl.sw_forces(qd, wait=False)
-    w = nl.sw_virial(qd, wait=False)
-    torch.cuda.synchronize()
-    assert nl.update_stats()[1] == builds
-    _check(f, w, _moved_ref(box, kind), dtype)
+    contract.reuse_within_the_skin(SW, box, kind, True, dtype)
 
 
 @gpu
@@ -626,76 +609,40 @@ def test_captured():
     from md_neighbor_list_amd._lib import NL_ERR_STATE, NLError
 
     torch = _torch()
-    dtype = np.float32
-    sets = [(_input("xyz", False), _ref("xyz", False, "one")), (_moved("xyz")[0], _moved_ref("xyz", "one"))]
-    nl = _handle("xyz", dtype, True, 2.9)
-    nl.set_skin(0.4)
-    nl.Initialize(N)
-    _set(nl, "one", 2.9)
-    src = torch.from_numpy(sets[0][0].astype(dtype)).cuda()
-    qd = src.clone()
-    fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
-    wd = torch.empty(8, dtype=torch.float64, device="cuda")
-    nl.update(qd, sync=True)
-    nl.update(qd)
-    nl.synchronize()
-    g0 = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g0):
-        with pytest.raises(NLError) as e:
-            nl.sw_virial(qd, wait=False, out=wd)
-        assert e.value.code == NL_ERR_STATE
-        nl.sw_forces(qd, wait=False, out=fd)  # (the forces need no scratch)
-    nl.sw_virial(qd)  # synchronous, outside a capture: allocates
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        qd.copy_(src)
-        nl.update(qd)
-        nl.sw_forces(qd, wait=False, out=fd)
-        nl.sw_virial(qd, wait=False, out=wd)
-    for q, ref in sets:
-        src.copy_(torch.from_numpy(q.astype(dtype)))
-        fd.fill_(-1.0), wd.fill_(-1.0)
-        g.replay()
-        torch.cuda.synchronize()
-        _check(fd, wd, ref, dtype)
+
+    def before(nl, qd, fd, wd):
+        nl.synchronize()
+        g0 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g0):
+            with pytest.raises(NLError) as e:
+                nl.sw_virial(qd, wait=False, out=wd)
+            assert e.value.code == NL_ERR_STATE
+            nl.sw_forces(qd, wait=False, out=fd)  # (the forces need no scratch)
+        nl.sw_virial(qd)  # synchronous, outside a capture: allocates
+
+    contract.captured(SW, True, before, lambda nl, replay: None)  # (nothing is set afterwards)
 
 
 @gpu
 def test_failed_list():
     """An enqueue behind an asynchronous build that overflowed its capacity: NaN forces and totals, NL_ERR_CAPACITY at
     synchronize; after the synchronous repeat all are finite."""
-    from md_neighbor_list_amd import NeighListGPU, inputs
-    from md_neighbor_list_amd._lib import NL_ERR_CAPACITY, NLError
+    def set_tables(nl):
+        nl.set_pair_table(*pair_table.sample(*morse(), 1e-3, R_MAX, NK), 1e-3, R_MAX)  # (a uniform random box has close pairs)
+        gs, dgs = sw_functions(1)
+        nl.set_sw(*sw.sample(gs[0][0], dgs[0][0], 1e-3, 1.5, NK), 1e-3, 1.5, *sw_angular(1))  # (about 13 partners within 1.5)
 
-    torch = _torch()
-    q, box = inputs.uniform_box(20000, dtype=np.float32, seed=28, box=(28.0, 28.0, 28.0))
-    nl = NeighListGPU(3.3, *box, dtype=torch.float32, full_list=True)
-    nl.set_skin(0.4)
-    nl.Initialize(len(q))
-    nl.set_pair_table(*pair_table.sample(*morse(), 1e-3, R_MAX, NK), 1e-3, R_MAX)  # (a uniform random box has close pairs)
-    gs, dgs = sw_functions(1)
-    nl.set_sw(*sw.sample(gs[0][0], dgs[0][0], 1e-3, 1.5, NK), 1e-3, 1.5, *sw_angular(1))  # (about 13 partners within 1.5)
-    qd = torch.from_numpy(q).cuda()
-    nl.update(qd, sync=True)
-    nl.sw_virial(qd)  # (the scratch)
-    nl.set_capacity(1000)
-    nl.update(qd)
-    f, w = nl.sw_forces(qd, wait=False), nl.sw_virial(qd, wait=False)
-    with pytest.raises(NLError) as e:
-        nl.synchronize()
-    assert e.value.code == NL_ERR_CAPACITY
-    assert torch.isnan(f).all() and f.shape == (len(q), 4) and torch.isnan(w).all()
-    nl.update(qd, sync=True)  # grows the list
-    f, w = nl.sw_forces(qd, wait=False), nl.sw_virial(qd, wait=False)
-    assert torch.isfinite(f).all() and torch.isfinite(w).all() and w[7] > 0
+    def prepare(nl, qd):
+        nl.update(qd, sync=True)
+        nl.sw_virial(qd)  # (the scratch)
+
+    contract.failed_list(SW, set_tables, prepare)
 
 
 @gpu
 @pytest.mark.parametrize("off", [32, 64])
 def test_both_offset_widths(off):
-    nl, qd = _built(_input("hex", True), "hex", np.float32, 2.5, "three", off)
-    assert nl.build_info()["offset_bits"] == off
-    _run(nl, qd, _ref("hex", True, "three"), np.float32)
+    contract.both_offset_widths(SW, True, off)
 
 
 @gpu
@@ -714,7 +661,7 @@ def test_state_and_arguments():
     qd = torch.from_numpy(q.astype(np.float32)).cuda()
     fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
     out = torch.empty(8, dtype=torch.float64, device="cuda")
-    calls = [(lib.nl_sw_forces, fd), (lib.nl_sw_forces_enqueue, fd), (lib.nl_sw_virial, out), (lib.nl_sw_virial_enqueue, out)]
+    calls = contract.entry_calls(SW, lib, fd, out)
     set_one = lambda t=tab: nl.set_sw(t.g, t.G, t.r_min_3, t.r_max_3, t.lam, t.cos0)  # noqa: E731
     # nothing set; only the pair table; only the g tables
     assert nl.sw() is None and lib.nl_get_sw(nl._h, *([None] * 5)) == NL_ERR_STATE
@@ -760,32 +707,11 @@ def test_state_and_arguments():
         nl.set_sw(g, G[:-1], R_MIN, R_MAX, 2.0, -0.3)
     with pytest.raises(TypeError):
         nl.set_sw(tab3.g, tab3.G, R_MIN, R_MAX, 2.0, -0.3)  # 9 slots, one triple
-    # the calls' arguments
-    for fn, o in calls:
-        assert fn(nl._h, qd.data_ptr(), 4, None, None) == NL_ERR_ARG
-        assert fn(nl._h, None, 4, o.data_ptr(), None) == NL_ERR_ARG
-        assert fn(None, qd.data_ptr(), 4, o.data_ptr(), None) == NL_ERR_ARG
-        for stride in (0, 2, 5):
-            assert fn(nl._h, qd.data_ptr(), stride, o.data_ptr(), None) == NL_ERR_ARG
-    # the setter does not touch the list
-    nl.update(qd, sync=True)
-    builds = nl.update_stats()[1]
-    set_one()
-    nl.update(qd, sync=True)
-    assert nl.update_stats()[1] == builds
-    # reach of the g tables: rc = 2.9, skin = 0.3 (the pair table stays at 2.5); only the status is looked at (from 2.7 on some
-    # centres have more than 64 partners in range)
+    contract.call_arguments(calls, nl, qd)
+    contract.setter_keeps_the_list(nl, qd, set_one)
+    # reach of the g tables (the pair table stays at 2.5); from 2.7 on some centres have more than 64 partners in range
     gs, dgs = sw_functions(1)
-    for r_max, sync_ok, enq_ok in ((2.6, True, True), (2.7, True, False), (2.9, True, False), (3.0, False, False)):
-        nl.set_sw(*sw.sample(gs[0][0], dgs[0][0], R_MIN, r_max, NK), R_MIN, r_max, 2.0, -0.3)
-        for wait, ok in ((True, sync_ok), (False, enq_ok)):
-            for call in (nl.sw_forces, nl.sw_virial):
-                if ok:
-                    call(qd, wait=wait)
-                else:
-                    with pytest.raises(NLError) as e:
-                        call(qd, wait=wait)
-                    assert e.value.code == NL_ERR_ARG, (r_max, wait)
+    contract.reach(SW, nl, qd, lambda r_max: nl.set_sw(*sw.sample(gs[0][0], dgs[0][0], R_MIN, r_max, NK), R_MIN, r_max, 2.0, -0.3))
     # ... and of the pair table
     set_one()
     nl.set_pair_table(*pair_table.sample(*morse(), R_MIN, 2.7, NK), R_MIN, 2.7)
@@ -794,35 +720,9 @@ def test_state_and_arguments():
         nl.sw_forces(qd, wait=False)
     assert e.value.code == NL_ERR_ARG
     nl.set_pair_table(F, U, R_MIN, R_MAX)
-    # clearing, both ways
-    nl.clear_sw()
-    assert nl.sw() is None
-    set_one()
-    assert lib.nl_set_sw(nl._h, *args(nk=0)) == 0 and nl.sw() is None
-    for wait in (True, False):
-        with pytest.raises(NLError) as e:
-            nl.sw_forces(qd, wait=wait)
-        assert e.value.code == NL_ERR_STATE
+    contract.clearing(SW, nl, qd, set_one, lambda: lib.nl_set_sw(nl._h, *args(nk=0)))
     # several types: a type table of that ntypes, a pair table of 1 or ntypes types
-    set_one(tab3)
-    for call in (nl.sw_forces, nl.sw_virial):
-        with pytest.raises(NLError) as e:
-            call(qd)
-        assert e.value.code == NL_ERR_STATE
-    nl.set_type_cutoffs(types % 2, [[2.9, 2.9], [2.9, 2.9]])
-    nl.MakeNeighList(qd, N)
-    with pytest.raises(NLError) as e:
-        nl.sw_forces(qd)
-    assert e.value.code == NL_ERR_ARG  # ntypes 3 against the type table's 2
-    set_one()
-    assert torch.isfinite(nl.sw_forces(qd)).all()  # one type works with a type table set
-    nl.set_type_cutoffs(types, [[2.9, 2.9, 0.0], [2.9, 2.55, 2.9], [0.0, 2.9, 2.9]])
-    nl.MakeNeighList(qd, N)
-    set_one(tab3)
-    assert torch.isfinite(nl.sw_virial(qd)).all()  # a pair table of one type under nine g slots; 2.5 <= 2.55
-    with pytest.raises(NLError) as e:
-        nl.sw_virial(qd, wait=False)  # 2.5 > 2.55 - 0.3
-    assert e.value.code == NL_ERR_ARG
+    contract.several_types(SW, nl, qd, types, set_one, lambda: set_one(tab3))  # (a pair table of one type under nine g slots)
     nl.set_pair_table(tab3.F, tab3.U, R_MIN, R_MAX)
     assert torch.isfinite(nl.sw_forces(qd)).all()
     # a half list
@@ -833,72 +733,18 @@ def test_state_and_arguments():
     assert torch.isfinite(half.table_forces(qd)).all()  # (the pair table's calls take this list)
     for fn, o in calls:
         assert fn(half._h, qd.data_ptr(), 4, o.data_ptr(), None) == NL_ERR_STATE
-    # n == 0
-    empty = _handle("open", np.float32, True, 2.9)
-    empty.Initialize(16)
-    _set_tab(empty, tab)
-    empty.MakeNeighList(torch.zeros((0, 4), dtype=torch.float32, device="cuda"))
-    out.fill_(7.0)
-    assert lib.nl_sw_virial(empty._h, qd.data_ptr(), 4, out.data_ptr(), None) == 0
-    assert lib.nl_sw_forces(empty._h, qd.data_ptr(), 4, fd.data_ptr(), None) == 0
-    torch.cuda.synchronize()
-    assert np.array_equal(out.cpu().numpy(), np.zeros(8))
+    contract.no_particles(SW, lib, True, lambda empty: _set_tab(empty, tab), qd, fd, out)
 
 
 @gpu
 def test_slab_lists_are_refused():
     """A full-list slab build, with and without nl_set_local_ids: NL_ERR_STATE from all four calls (the force on an owned end needs
     the triples centred on ghosts)."""
-    from md_neighbor_list_amd._lib import NL_ERR_STATE, NLError
-    from tests.test_slab_paths import slab_parts
-
-    torch = _torch()
-    box, dtype, rc = "xyz", np.float32, 3.4
-    box6, mask = LJ_BOXES[box]
-    q = _input(box, False)
-    part = slab_parts(q[:, :3].astype(dtype), box6[:3], rc, ((0, 2), (2, 4)), mask)[0]
-    for local in (True, False):
-        nl = _handle(box, dtype, True, rc)
-        nl.set_local_ids(local)
-        nl.Initialize(N)
-        _set(nl, "one", rc)
-        qd = torch.from_numpy(np.ascontiguousarray(q[part["order"]].astype(dtype))).cuda()
-        nl.MakeNeighListSlab(qd, None, len(part["own"]), part["z_lo"], part["z_hi"])
-        if local:
-            assert torch.isfinite(nl.table_forces(qd)).all()  # (the pair table's calls take this list)
-        for call in (nl.sw_forces, nl.sw_virial):
-            for wait in (True, False):
-                with pytest.raises(NLError) as e:
-                    call(qd, wait=wait)
-                assert e.value.code == NL_ERR_STATE
+    contract.slab_lists_are_refused(SW, True)
 
 
 @gpu
 def test_distributed_lists_are_refused():
     """A distributed build of a world of one (nl_make_list_distributed: the whole box, the global ids in w): its list holds
     caller ids, and all four calls are NL_ERR_STATE, wait and enqueue."""
-    from md_neighbor_list_amd import _lib
-    from md_neighbor_list_amd._lib import NL_ERR_STATE
-
-    torch = _torch()
-    box, dtype, rc = "xyz", np.float32, 3.4
-    nl = _handle(box, dtype, True, rc)
-    nl.Initialize(N)
-    _set(nl, "one", rc)
-    lib = nl._lib
-    q = _input(box, False).astype(np.float32)
-    q[:, 3] = np.arange(N, dtype=np.int32).view(np.float32)  # NL_GID_IN_W
-    qd = torch.from_numpy(q).cuda()
-    fd = torch.empty((N, 4), dtype=torch.float32, device="cuda")
-    out = torch.empty(8, dtype=torch.float64, device="cuda")
-    cb = _lib.SENDRECV_FN(lambda *a: 1)  # (never called: a world of one exchanges nothing)
-    comm = C.c_void_p()
-    assert lib.nl_comm_create_callbacks(C.byref(comm), 0, 1, cb, None, torch.cuda.current_device()) == 0
-    try:
-        assert lib.nl_make_list_distributed(nl._h, comm, qd.data_ptr(), N, N, None, 1) == 0
-        npairs = C.c_int64()
-        assert lib.nl_number_of_pairs(nl._h, C.byref(npairs)) == 0 and npairs.value > 50 * N
-        for fn, o in ((lib.nl_sw_forces, fd), (lib.nl_sw_forces_enqueue, fd), (lib.nl_sw_virial, out), (lib.nl_sw_virial_enqueue, out)):
-            assert fn(nl._h, qd.data_ptr(), 4, o.data_ptr(), None) == NL_ERR_STATE
-    finally:
-        lib.nl_comm_destroy(comm)
+    contract.distributed_lists_are_refused(SW, True)
