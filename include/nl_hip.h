@@ -890,7 +890,8 @@ int nl_debug_occupancy(int32_t out[8]); /* LDS per CU/block (KiB), occupancy API
  * (k_sweep_class_f32: C = 2 or 4 classes of ids; NL_IDCLASS), else 0; bits 16..17 of info[7] = the binning the build
  * took: 0 = two passes over rows of x-cells, 1 = one pass into row buckets, 2 = atomic ranks into the cell histogram
  * (NL_BINNING=1, and every mesh of more than 12288 rows of x-cells or more than 4096 cells a row; such a build has no
- * fine rows and no id classes).  Asserted on both sides of those limits, lists against the oracle: tests/test_mesh_limits.py. */
+ * fine rows and no id classes); bit 18 of info[7] = 1 when the id-class search ran with the reach cull (partners no
+ * particle of the cell can reach leave the staged stream before the search; NL_CULL=0 turns it off).  Asserted on both sides of those limits, lists against the oracle: tests/test_mesh_limits.py. */
 int nl_get_build_info(nl_handle_t h, int32_t info[8]);
 /* How the builds of this handle ran: stats[0] = builds run again because a row of x-cells overflowed its bucket in the
  * one-pass binning, stats[1] = builds run again because cells whose stencil exceeds the LDS buffer were there while the

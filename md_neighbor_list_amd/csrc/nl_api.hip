@@ -90,12 +90,13 @@ struct BuildPlan {
   int32_t pbc = 0;      // axes of the minimum image (nl_set_periodic_axes)
   int32_t idc = 0;      // SEARCH_MASKS with id classes (k_sweep_class_f32, k_fill_masks<IDC>): C = 2 or 4 classes, 0 = off
   int32_t id_shift = 0; // class of an id: id >> id_shift
+  bool cull = false;    // an id-class build with the reach cull (cls_cull; NL_CULL): COUNT leaves cull_bits to the expansion
   bool id_rows = false; // no caller ids, no tilt, the two-level binning: the id of a particle is its input row, so sorted_row
                         // is the compact id array as well (tmp_row and sorted_gid are neither written nor read)
   Box box = {{0, 0, 0}, 0, 0, 0};  // the box of the build (nl_set_box): what its consumers (k_lj, the skin check) fold with
   int32_t tilt = 0;     // box.xy, box.xz or box.yz is not 0: binning and search in sheared coordinates
   auto tie() const {
-    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, images, pbc, idc, id_shift, id_rows,
+    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, images, pbc, idc, id_shift, cull, id_rows,
                     box.L[0], box.L[1], box.L[2], box.xy, box.xz, box.yz, tilt);
   }
   bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
@@ -183,6 +184,8 @@ struct nl_handle_s {
   DevBuf<int32_t> cell_start;     // [ncell + 1]
   DevBuf<int32_t> cls_start;      // id-class builds: [C ncell + 1] first slot of every (cell, class) (k_bin_cells<IDC>)
   int idclass_env = 2;            // NL_IDCLASS: classes of the id-class search where a build qualifies (2 or 4), 0 = never
+  DevBuf<uint64_t> cull_bits;     // reach-cull builds: [cells][CULL_WORDS] kept-slot ballots of every cell's stream (cls_cull)
+  int cull_env = 1;               // NL_CULL=0: id-class builds without the reach cull
   DevBuf<uint64_t> scan_look;     // k_scan_chained: [scan_blocks] entries + the two counters; all zero between launches
   int32_t scan_blocks = 0;
   DevBuf<int64_t> totals;     // [0] = particles (cell scan), [1] = pairs (row scan)
@@ -603,6 +606,7 @@ template <typename T> SweepArgs<T> sweep_args(nl_handle_t h) {
   a.dbg = h->dbg_flags;
   a.dbg_buf = h->dbg_buf;
   a.gate = h->gate;
+  a.cull_bits = h->plan.cull ? h->cull_bits.get() : nullptr;
   for (int d = 0; d < 3; d++) a.k[d] = (T)h->shear[d];
   a.lat = h->lat_dev;
   return a;
@@ -739,6 +743,11 @@ bool mask_rows_ready(nl_handle_t h, int64_t nb, size_t row_bytes = MASK_ROW_BYTE
   return true;
 }
 
+// The ballot words of a reach-cull build (cls_cull): allocated on first need, and again for a mesh of more cells.
+bool cull_bits_ready(nl_handle_t h, int64_t cells) {
+  return follow(h, h->cull_bits, cells, sizeof(uint64_t) * CULL_WORDS * (size_t)cells) == NL_OK;
+}
+
 // The two-level binning (k_bin_*): meshes of up to BIN_MAX_ROWS rows of x-cells and BIN_MAX_MX cells a row, unless
 // NL_BINNING=1 selects the atomic-rank path (k_hash / k_reorder).
 bool two_level_ok(nl_handle_t h, int32_t mzl) {
@@ -869,6 +878,7 @@ template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, in
       h->m[0] >= 3 && h->m[1] >= 3 && a.mzl >= 3 && n > 0) {
     p.idc = h->idclass_env;
     while (((uint32_t)(n - 1) >> p.id_shift) >= (uint32_t)p.idc) p.id_shift++;  // classes [k 2^s, (k + 1) 2^s) cover [0, n)
+    p.cull = h->cull_env != 0 && cull_bits_ready(h, ncl);
   }
   return p;
 }
@@ -1360,6 +1370,7 @@ int nl_create(nl_handle_t* out, int dtype, double rc, double Lx, double Ly, doub
     if (const char* v = getenv("NL_SWEEP_VARIANT")) h->sweep_variant = atoi(v) <= 1 ? 1 : 3;
     if (const char* v = getenv("NL_ROWS")) h->rows_env = std::max(-1, std::min(atoi(v), 4));
     if (const char* v = getenv("NL_IDCLASS")) h->idclass_env = atoi(v) >= 4 ? 4 : atoi(v) >= 2 ? 2 : 0;
+    if (const char* v = getenv("NL_CULL")) h->cull_env = atoi(v) != 0;
     if (const char* v = getenv("NL_OFFSET_WIDTH")) h->offset_width = atoi(v) == 64 ? 64 : atoi(v) == 32 ? 32 : 0;
     if (const char* v = getenv("NL_BINNING")) h->bin_two_level = atoi(v) != 1;
     if (const char* v = getenv("NL_BIN_BUCKETS")) h->bucket_env = atoi(v) != 0;
@@ -1882,9 +1893,10 @@ int nl_get_build_info(nl_handle_t h, int32_t info[8]) {
   info[4] = p.wide ? 64 : 32;
   info[5] = p.mask_nb;
   info[6] = p.search == SEARCH_ROWS ? 1 + p.rows_v : 0;  // fine-row search: the cell table of nl_get_sorted is the fine-row table
-  // (bits 8..15: classes of an id-class build; bits 16..17: the binning, 0 = two-pass, 1 = bucket, 2 = atomic rank)
+  // (bits 8..15: classes of an id-class build; bits 16..17: the binning, 0 = two-pass, 1 = bucket, 2 = atomic rank;
+  // bit 18: the reach cull)
   const int32_t binning = p.binning == BINNING_TWO_PASS ? 0 : p.binning == BINNING_BUCKET ? 1 : 2;
-  info[7] = (p.small ? 1 : 0) | p.idc << 8 | binning << 16;
+  info[7] = (p.small ? 1 : 0) | p.idc << 8 | binning << 16 | (p.cull ? 1 : 0) << 18;
   info[0] = p.search != SEARCH_SWEEPS ? 1 : 0;
   info[1] = h->sweep_variant;
   info[2] = h->dtype == NL_F32 ? SweepCfg<float>::CAP : SweepCfg<double>::CAP;

@@ -995,6 +995,7 @@ template <typename T> struct SweepArgs {
   // the box (nl_set_box; read by the PBC kernels only): a segment reached through faces w is staged at S(w)
   T k[3];                         // the shear of Grid::k (screened fp64 search: the Cartesian centre of a sheared cell)
   const double* lat;              // Grid::lat
+  uint64_t* cull_bits = nullptr;   // reach cull (cls_cull): [cell][CULL_WORDS] kept-slot ballots, COUNT -> expansion; null = off
 };
 
 // The image shift of a stencil segment reached through the periodic faces w (wr = its CellCtx::wrap code): S(w), which
@@ -1922,6 +1923,151 @@ __device__ __forceinline__ void cls_stage(const E* __restrict__ from, const ClsC
   }
 }
 
+// ---- reach cull (BuildPlan::cull, NL_CULL).  The COUNT sweep of an id-class build drops from the
+// staged stream every slot that lies farther than the cut-off from the bounding box of the cell's own particles, and
+// compacts the stream stably in place; the search then walks the compacted stream, and the hit words count its slots.
+// The ballots -- bit l of word t: slot 64 t + l of the staged stream was kept -- go to SweepArgs::cull_bits, CULL_WORDS
+// words per cell, and the expansion compacts the staged ids with them.
+constexpr int CULL_WORDS = SweepCfg<float>::CAP / WAVE;
+// a slot is dropped only if G2 > rc2 (1 + CULL_DELTA), G2 = its squared distance to the box.  The pair test's r2 is
+// never below G2 (the same operations in the same order, each monotonic in its arguments: DESIGN.md section 4), so the
+// margin is not needed for exactness; it keeps the decision away from the last bit.
+constexpr float CULL_DELTA = 1.0f / (float)(1 << 20);
+
+// v_min_f32 as the hardware has it: one instruction, the operand that is a number where the other is not (fminf comes
+// with an instruction per operand that quiets signalling NaNs first)
+__device__ __forceinline__ float min_raw(float a, float b) {
+  float r;
+  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// The minima of six values over the wave, in every lane's place 63 -> uniform.  One DPP instruction per value and step
+// (v = min(v shifted, v); a lane without a source keeps its value); the six values take turns, which keeps the two
+// wait states between the write of a register and its DPP read (inline assembly is not padded).
+__device__ __forceinline__ void wave_min6(float (&v)[6]) {
+#define NL_MIN6_STEP(ctrl) \
+  "v_min_f32_dpp %0, %0, %0 " ctrl "\n\tv_min_f32_dpp %1, %1, %1 " ctrl "\n\tv_min_f32_dpp %2, %2, %2 " ctrl "\n\t" \
+  "v_min_f32_dpp %3, %3, %3 " ctrl "\n\tv_min_f32_dpp %4, %4, %4 " ctrl "\n\tv_min_f32_dpp %5, %5, %5 " ctrl "\n\t"
+  asm("s_nop 1\n\t" NL_MIN6_STEP("row_shr:1 row_mask:0xf bank_mask:0xf") NL_MIN6_STEP("row_shr:2 row_mask:0xf bank_mask:0xf")
+      NL_MIN6_STEP("row_shr:4 row_mask:0xf bank_mask:0xf") NL_MIN6_STEP("row_shr:8 row_mask:0xf bank_mask:0xf")
+      NL_MIN6_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf") NL_MIN6_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf") "s_nop 1"
+      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
+#undef NL_MIN6_STEP
+#pragma unroll
+  for (int k = 0; k < 6; k++) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int32_t, v[k]), 63));
+}
+
+// The kept slots of a cell's stream: lane t holds the ballot of tile t (0 from the stream's last tile on).
+struct CullMap {
+  uint32_t lo, hi;  // the ballot of tile `lane`
+  int32_t excl;     // kept slots in front of tile `lane`
+  int32_t kept;     // kept slots of the stream (uniform)
+};
+__device__ __forceinline__ CullMap cull_map(uint64_t word) {
+  CullMap m;
+  m.lo = (uint32_t)word, m.hi = (uint32_t)(word >> 32);
+  const int32_t cnt = __popc(m.lo) + __popc(m.hi);
+  const int32_t incl = scan64_dpp(cnt);
+  m.excl = incl - cnt;
+  m.kept = __builtin_amdgcn_readlane(incl, 63);
+  return m;
+}
+// where slot s of the staged stream lies in the compacted one: the kept slots in front of it (per lane; s <= CAP)
+__device__ __forceinline__ int32_t cull_rank(const CullMap& m, int32_t s) {
+  const int32_t at = (s >> 6) << 2, b = s & 63;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(at, (int32_t)m.lo), hi = (uint32_t)__builtin_amdgcn_ds_bpermute(at, (int32_t)m.hi);
+  const int32_t ex = __builtin_amdgcn_ds_bpermute(at, m.excl);
+  const uint32_t below_lo = b >= 32 ? 0xFFFFFFFFu : (1u << (b & 31)) - 1u, below_hi = b > 32 ? (1u << (b & 31)) - 1u : 0u;
+  return ex + __popc(lo & below_lo) + __popc(hi & below_hi);
+}
+// tile t (uniform) of the staged stream: whether this lane's slot was kept, and where it goes
+__device__ __forceinline__ bool cull_slot(const CullMap& m, int32_t t, int32_t& dst) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)m.lo, t), hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)m.hi, t);
+  dst = __builtin_amdgcn_readlane(m.excl, t) + (int32_t)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+  return (((uint64_t)hi << 32 | lo) >> (threadIdx.x & 63) & 1u) != 0;
+}
+// the window offsets of the compacted stream
+template <int IDC> __device__ __forceinline__ void cull_offsets(const CullMap& m, ClsCtx<IDC>& c) {
+#pragma unroll
+  for (int j = 0; j < ClsCtx<IDC>::NT; j++) c.off[j] = cull_rank(m, c.off[j]);
+  c.total_j = m.kept;
+}
+
+// The cull pass of k_sweep_class_f32, behind the staging barrier: the box of the cell's own particles (windows 27 k +
+// CLS_OWN, the particles themselves: one filed into an edge cell from outside the box is inside it), a ballot per tile,
+// the compaction -- every wave holds its tiles in registers across the barrier behind which the stream is overwritten
+// -- and the tables of the compacted stream.  The ballots pass from wave to wave through the last CULL_WORDS words of
+// the buffer (no second __shared__ object: DESIGN.md section 5), which a stream of more than CAP - 64 slots would reach:
+// such a cell keeps every slot.  Ends with the barrier behind which the compacted stream may be read.
+template <int IDC, int NW, int CAP>
+__device__ __forceinline__ void cls_cull(const SweepArgs<float>& a, ClsCtx<IDC>& c, Pos<float>* buf, int32_t cell, int tid, int lane, int wave) {
+  constexpr int TW = (CAP / WAVE + NW - 1) / NW;  // tiles a wave holds
+  static_assert(CAP / WAVE == CULL_WORDS && CAP % WAVE == 0, "a ballot word per tile of the buffer");
+  const int32_t nj = c.total_j, ntiles = (nj + WAVE - 1) / WAVE;
+  uint64_t* const out = a.cull_bits + (size_t)cell * CULL_WORDS;
+  if (ntiles * WAVE > CAP - WAVE) {  // (uniform; rare) no room for the ballots: every slot kept
+    if (wave == 0 && lane < ntiles) out[lane] = lane + 1 < ntiles ? ~0ull : ~0ull >> (ntiles * WAVE - nj);
+    return;
+  }
+  uint64_t* const words = reinterpret_cast<uint64_t*>(buf + CAP) - CULL_WORDS;
+  // the box of the own particles: the cell's ni slots are its class runs in turn, a lane each
+  const float inf = __builtin_inff();
+  float bx[6] = {inf, inf, inf, inf, inf, inf};  // lower corner, minus the upper corner
+  float chk = 0.f;
+  for (int32_t kb = 0; kb < c.ni; kb += WAVE) {
+    int32_t i = min(kb + lane, c.ni - 1), slot = 0;
+#pragma unroll
+    for (int k = IDC - 1; k >= 0; k--) {
+      const int32_t own = c.get(c.off, 27 * k + CLS_OWN), first = c.get(c.src, 27 * k + CLS_OWN) - c.ibeg;
+      slot = (k == IDC - 1 || i < first + c.get(c.len, 27 * k + CLS_OWN)) ? own + (i - first) : slot;
+    }
+    const Pos<float> p = buf[slot];
+    bx[0] = min_raw(bx[0], p.x), bx[1] = min_raw(bx[1], p.y), bx[2] = min_raw(bx[2], p.z);
+    bx[3] = min_raw(bx[3], -p.x), bx[4] = min_raw(bx[4], -p.y), bx[5] = min_raw(bx[5], -p.z);
+    chk = chk + ((p.x + p.y) + p.z);
+  }
+  wave_min6(bx);
+  const float lx = bx[0], ly = bx[1], lz = bx[2], hx = -bx[3], hy = -bx[4], hz = -bx[5];
+  // (an own particle that is not a number is in no box: nothing is dropped then)
+  const float reach = __builtin_amdgcn_ballot_w64(chk != chk) != 0 ? inf : mul_rn(a.rc2, 1.0f + CULL_DELTA);
+  Pos<float> p[TW];
+#pragma unroll
+  for (int u = 0; u < TW; u++) p[u] = buf[min(wave + u * NW, ntiles - 1) * WAVE + lane];  // (all reads in flight together)
+#pragma unroll
+  for (int u = 0; u < TW; u++) {
+    const int32_t t = wave + u * NW;  // (uniform)
+    if (t >= ntiles) break;
+    // the gap along each axis, from differences formed as the pair test forms them (partner minus own)
+    const float gx = fmaxf(fmaxf(sub_rn(p[u].x, hx), sub_rn(lx, p[u].x)), 0.f);
+    const float gy = fmaxf(fmaxf(sub_rn(p[u].y, hy), sub_rn(ly, p[u].y)), 0.f);
+    const float gz = fmaxf(fmaxf(sub_rn(p[u].z, hz), sub_rn(lz, p[u].z)), 0.f);
+    float g2 = add_rn(add_rn(mul_rn(gx, gx), mul_rn(gy, gy)), mul_rn(gz, gz));
+    // (the maxima pass over a NaN: a coordinate that is none makes g2 one, and the slot stays)
+    g2 = __builtin_fmaf(add_rn(add_rn(p[u].x, p[u].y), p[u].z), 0.f, g2);
+    uint64_t kept = __builtin_amdgcn_ballot_w64(!(g2 > reach));
+    if (t == ntiles - 1) kept &= ~0ull >> (ntiles * WAVE - nj);  // the sentinels behind the stream
+    if (lane == 0) words[t] = kept;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // every wave holds its tiles; the ballots are in place
+  const CullMap m = cull_map(lane < ntiles ? words[lane] : 0ull);
+  if (wave == 0 && lane < ntiles) out[lane] = (uint64_t)m.hi << 32 | m.lo;
+#pragma unroll
+  for (int u = 0; u < TW; u++) {
+    const int32_t t = wave + u * NW;
+    if (t >= ntiles) break;
+    int32_t dst;
+    if (cull_slot(m, t, dst)) buf[dst] = p[u];
+  }
+  const int32_t pad = m.kept + tid;
+  if (pad < ((m.kept + WAVE - 1) & ~(WAVE - 1))) {
+    Pos<float> sentinel;  // as behind the staged stream
+    sentinel.x = 1.0e18f, sentinel.y = 0.f, sentinel.z = 0.f, sentinel.gid = INT32_MIN;
+    buf[pad] = sentinel;
+  }
+  cull_offsets<IDC>(m, c);
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // slots of a row k_fill_masks assembles in LDS: rows shorter than this (one slot stays free for the lanes without an
 // entry; rows of this length and more are written entry by entry); half list: 5 + 5 KiB of LDS = 16 workgroups per CU
 template <bool FULL> constexpr int EXPAND_RMAX_OF = FULL ? 192 : 160;
@@ -1953,6 +2099,12 @@ k_fill_masks(SweepArgs<T> a) {
   };
 #endif
   const int64_t total = a.total[0];  // read together with the cell table: one round trip, not two
+  // reach cull: the cell's ballots (lane t: tile t), in the same round trip; meaningful for a cell COUNT has searched
+  uint64_t kept_word = 0;
+  if constexpr (IDC > 0) {
+    static_assert(EW * 4 * EXPAND_RMAX >= CAP, "the staged ids of a cull build land in the row buffers");
+    if (a.cull_bits) kept_word = a.cull_bits[(size_t)xcd_cell_index() * CULL_WORDS + min(lane, CULL_WORDS - 1)];
+  }
   typename std::conditional<(IDC > 0), ClsCtx<IDC ? IDC : 2>, CellCtx>::type c;
   bool ok;
   if constexpr (IDC > 0) ok = cls_setup<IDC>(a, lane, c);
@@ -1984,7 +2136,15 @@ k_fill_masks(SweepArgs<T> a) {
   const int32_t r_beg = min(wave * per_wave, c.ni), r_end = min(r_beg + per_wave, c.ni);
   uint32_t w[RB];
   OFF base_l;  // lane u: list offset of row r0 + u
-  const bool hi_plane = hi_plane_used(1, (c.total_j + WAVE - 1) / WAVE);
+  // (reach cull: the hit words count the slots of the compacted stream, cm.kept of them)
+  CullMap cm = {0u, 0u, 0, 0};
+  bool cull = false;
+  const int32_t staged_tiles = (c.total_j + WAVE - 1) / WAVE;
+  if constexpr (IDC > 0) {
+    cull = a.cull_bits != nullptr;  // (uniform)
+    if (cull) cm = cull_map(lane < staged_tiles ? kept_word : 0ull);
+  }
+  const bool hi_plane = hi_plane_used(1, ((cull ? cm.kept : c.total_j) + WAVE - 1) / WAVE);
   auto load_rows = [&](int32_t r0) {
     {
       // key_pointer[sorted_row[slot]] of the batch's rows, a lane per row: two dependent loads per batch in the shadow
@@ -2023,14 +2183,12 @@ k_fill_masks(SweepArgs<T> a) {
   // write instructions, and every segment's loads are in flight together.  (Loading and writing segment by segment
   // through registers cost one memory round trip per segment, 9 per wave.)
   // id classes: rows [cls_row[k], cls_row[k + 1]) of the cell are of class k, their words start at stream slot cls_t0[k]
+  // (reach cull: the ids land in the row buffers, not yet in use, and are compacted into `gids` behind the barrier)
   int32_t cls_row[IDC > 0 ? IDC : 1], cls_t0[IDC > 0 ? IDC : 1];
+  int32_t* const staged = cull ? lds + CAP : gids;
+  (void)staged;
   if constexpr (IDC > 0) {
-#pragma unroll
-    for (int k = 0; k < IDC; k++) {
-      cls_row[k] = c.get(c.src, 27 * k + CLS_OWN) - c.ibeg;
-      cls_t0[k] = c.get(c.off, 27 * k) & ~(WAVE - 1);
-    }
-    cls_stage<IDC, EW>(a.sorted_gid, c, gids, lane, wave);
+    cls_stage<IDC, EW>(a.sorted_gid, c, staged, lane, wave);
   } else
 #pragma unroll
   for (int s = 0; s < (NSEG + EW - 1) / EW; s++) {
@@ -2051,6 +2209,22 @@ k_fill_masks(SweepArgs<T> a) {
 #if NL_STAMP_FILL
   fstamp(2);  // barrier (DMA landed)
 #endif
+  if constexpr (IDC > 0) {
+    if (cull) {  // the kept ids, in the order COUNT compacted the stream to
+      for (int32_t t = wave; t < staged_tiles; t += EW) {
+        int32_t dst;
+        const int32_t id = staged[t * WAVE + lane];
+        if (cull_slot(cm, t, dst)) gids[dst] = id;
+      }
+      cull_offsets<IDC>(cm, c);
+      __syncthreads();  // before a row buffer is written, before `gids` is read
+    }
+#pragma unroll
+    for (int k = 0; k < IDC; k++) {
+      cls_row[k] = c.get(c.src, 27 * k + CLS_OWN) - c.ibeg;
+      cls_t0[k] = c.get(c.off, 27 * k) & ~(WAVE - 1);
+    }
+  }
 
   const int32_t* const g = gids + lane;
   for (int32_t r0 = r_beg; r0 < r_end; r0 += RB) {

@@ -258,7 +258,8 @@ __device__ __forceinline__ void class_search(const SweepArgs<float>& a, const Cl
 }
 
 // k_sweep_lean_f32 for an id-class build (fp32 half list, open box, ids 0..n-1, IDC = C classes): the class-major
-// stream, the class-paired groups; a cell whose stream does not fit goes to k_sweep_list_f32 as there.
+// stream, the class-paired groups; a cell whose stream does not fit goes to k_sweep_list_f32 as there (decided on the
+// staged length, before the reach cull of cls_cull shortens the stream).
 template <int IDC, int NW = SWEEP_WAVES, int CAP = SweepCfg<float>::CAP>
 __global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80))) k_sweep_class_f32(SweepArgs<float> a) {
   if (gate_closed(a.gate)) return;  // (nl_update_list: no build this time)
@@ -279,6 +280,8 @@ __global__ void __launch_bounds__(NW* WAVE, 8) __attribute__((amdgpu_num_sgpr(80
     buf[pad] = sentinel;
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // reach cull (uniform): from here on c and buf describe the compacted stream
+  if (a.cull_bits) cls_cull<IDC, NW, CAP>(a, c, buf, c.cx + (c.cy + c.cz * a.my) * a.mx, tid, lane, wave);
   PipePending pend;
   pend.gcount = 0, pend.mine = 0, pend.row_l = 0, pend.slot0 = 0;
   class_search<IDC, NW>(a, c, buf, lane, wave, pend);

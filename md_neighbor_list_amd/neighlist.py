@@ -780,16 +780,18 @@ class NeighListGPU:
     def build_info(self):
         """{'masks': bool, 'variant': int, 'lds_batch': int, 'cus': int, 'offset_bits': 32 | 64, 'mask_rows': int,
         'fine_rows': 0 | 1 + RowsCfg, 'small_cells': 0 | 1, 'id_classes': 0 | 2 | 4, 'binning': 'two_pass' | 'bucket' |
-        'atomic'} of the last build (masks: the list was expanded from hit masks; mask_rows > 1: dense build; fine_rows: the
-        fine-row search of nl_rows.hpp; id_classes: the half-list search by id class, NL_IDCLASS; binning: two passes over
-        rows of x-cells, one pass into row buckets, or atomic ranks into the cell histogram -- NL_BINNING=1 and meshes
-        beyond the row tables)."""
+        'atomic', 'reach_cull': bool} of the last build (masks: the list was expanded from hit masks; mask_rows > 1: dense
+        build; fine_rows: the fine-row search of nl_rows.hpp; id_classes: the half-list search by id class, NL_IDCLASS;
+        binning: two passes over rows of x-cells, one pass into row buckets, or atomic ranks into the cell histogram --
+        NL_BINNING=1 and meshes beyond the row tables; reach_cull: the id-class search dropped the partners no particle of
+        the cell can reach before it searched, NL_CULL)."""
         info = (C.c_int32 * 8)()
         check(self._lib.nl_get_build_info(self._h, C.byref(info)), "nl_get_build_info")
         return {"masks": bool(info[0]), "variant": int(info[1]), "lds_batch": int(info[2]), "cus": int(info[3]),
                 "offset_bits": int(info[4]), "mask_rows": int(info[5]), "fine_rows": int(info[6]),
                 "small_cells": int(info[7]) & 0xFF, "id_classes": int(info[7]) >> 8 & 0xFF,
-                "binning": ("two_pass", "bucket", "atomic")[int(info[7]) >> 16 & 3]}
+                "binning": ("two_pass", "bucket", "atomic")[int(info[7]) >> 16 & 3],
+                "reach_cull": bool(int(info[7]) >> 18 & 1)}
 
     def build_stats(self):
         """{'row_overflow_reruns', 'list_reruns', 'cap_row', 'list_launched'}: builds of this handle run again (a row
