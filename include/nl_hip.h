@@ -300,8 +300,10 @@ int nl_synchronize(nl_handle_t h);
  *   nl_set_skin: skin >= 0 (default 0: every particle that moved at all triggers a build); forces the next update to build.
  *   nl_update_list: builds as nl_make_list does (the same list) exactly when
  *     (a) the host knows a reason: no list of an update to keep (first update; nl_initialize, nl_set_list_kind,
- *         nl_set_periodic(_axes), nl_set_offset_width, nl_set_capacity, nl_set_skin, nl_set_pair_images (a changed value) or nl_resort called, or a build other than
- *         an update's run, since; the host has seen the last build fail) or q_dev, q_stride or n differ from that build's;
+ *         nl_set_periodic(_axes), nl_set_offset_width, nl_set_capacity, nl_set_skin, nl_set_pair_images (a changed value),
+ *         nl_set_box, nl_set_exclusions(_global), nl_set_type_cutoffs or nl_resort called, or a build other than an update's
+ *         run -- nl_make_list, a slab build, nl_profile_stages, nl_profile_last_build -- since; the host has seen the last
+ *         build fail) or q_dev, q_stride or n differ from that build's;
  *     (b) the status word of the last performed build is not OK (an asynchronous build that overflowed its capacity);
  *     (c) for some particle i < n, with d = q_now - snap per component in the position type (round to nearest, no
  *         contraction), dd = (double)d, folded to the minimum image on every axis of the nl_set_periodic_axes mask
@@ -917,7 +919,11 @@ enum {
 int nl_profile_stages(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, int32_t reps,
                       double ms[NL_NUM_STAGES]);
 /* Same, re-running the last successful build (single-device or slab) with the arguments it was given; the
- * position / id buffers of that build must still be alive. */
+ * position / id buffers of that build must still be alive.  Not a passive timer: the build is planned again as one whole,
+ * ungated build (a begin / finish pair runs as one call; a build that was run again, or an update's, keeps the two-pass
+ * binning and every launch it ran with), run `reps` times into the handle's own buffers from the positions the buffer
+ * holds now, and adopted -- the list, the plan and nl_get_build_info / nl_get_build_stats afterwards are that build's,
+ * and like any build other than an update's it makes the next nl_update_list build (rule (a) above). */
 int nl_profile_last_build(nl_handle_t h, int32_t reps, double ms[NL_NUM_STAGES]);
 
 /* --------------------------------------------------------------------------------- buffers (cuda_ptr shim) */

@@ -95,8 +95,9 @@ struct BuildPlan {
                         // is the compact id array as well (tmp_row and sorted_gid are neither written nor read)
   Box box = {{0, 0, 0}, 0, 0, 0};  // the box of the build (nl_set_box): what its consumers (k_lj, the skin check) fold with
   int32_t tilt = 0;     // box.xy, box.xz or box.yz is not 0: binning and search in sheared coordinates
+  bool rerun = false;   // planned as a build that runs one again (finish(), an update's): the profiler plans it that way too
   auto tie() const {
-    return std::tie(binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, images, pbc, idc, id_shift, cull, id_rows,
+    return std::tie(rerun, binning, cap_row, split, search, rows_v, mask_nb, small, rows12, list, full, wide, filter, images, pbc, idc, id_shift, cull, id_rows,
                     box.L[0], box.L[1], box.L[2], box.xy, box.xz, box.yz, tilt);
   }
   bool operator==(const BuildPlan& o) const { return tie() == o.tie(); }
@@ -800,6 +801,7 @@ template <typename T> int32_t bucket_cap(nl_handle_t h, int32_t n, int32_t mzl) 
 // binning and every launch of its path.
 template <typename T> BuildPlan plan_build(nl_handle_t h, const BuildArgs& a, int part, bool rerun) {
   BuildPlan p;
+  p.rerun = rerun;
   p.full = h->list_kind == NL_LIST_FULL;
   p.pbc = h->pbc;
   p.box = box_of(h);
@@ -1926,7 +1928,14 @@ int nl_profile_last_build(nl_handle_t h, int32_t reps, double ms[NL_NUM_STAGES])
   HIPCHK(h, hipStreamSynchronize(h->last_stream));
   BuildArgs a = h->args;
   a.n = h->n;  // (a distributed build: the particles finish() has counted)
-  const BuildPlan p = plan_for(h, a, PART_ALL, false);
+  // the builds below replace the list with one of the positions as they are now: not an update's build, and the snapshot
+  // is no longer the list's (as nl_make_list); nor is a transposed list made before them
+  h->upd_valid = false, h->last_update = false;
+  h->built = false;
+  h->t_valid = false;
+  // one whole build, planned as the last one was: with the two-pass binning and every launch where finish() had run
+  // it again or an update had built it, so that build_info() keeps describing the build the caller made
+  const BuildPlan p = plan_for(h, a, PART_ALL, h->plan.rerun);
   for (int r = 0; r < reps; r++) {
     rc = dispatch_build(h, a, p, s, h->ev);
     if (rc) return rc;

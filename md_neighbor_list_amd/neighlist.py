@@ -802,7 +802,12 @@ class NeighListGPU:
                 "list_launched": bool(st[3])}
 
     def profile_last_build(self, reps=10):
-        """Same for the last build (also a slab build); its position/id tensors are kept alive by this object."""
+        """Same for the last build (also a slab build); its position/id tensors are kept alive by this object.  Not a
+        passive timer (nl_profile_last_build): the build is planned again as one whole, ungated build (a begin / finish pair as
+        one call; a build that was run again, or an update's, with the two-pass binning and every launch it ran with), run
+        ``reps`` times into the handle's own buffers from the positions the tensor holds now, and adopted -- the list,
+        ``build_info()`` and ``build_stats()`` afterwards are that build's, and like any build other than an update's it
+        makes the next ``update()`` build."""
         ms = (C.c_double * _lib.NL_NUM_STAGES)()
         check(self._lib.nl_profile_last_build(self._h, int(reps), C.byref(ms)), "nl_profile_last_build")
         return dict(zip(_lib.STAGE_NAMES, (float(v) for v in ms)))

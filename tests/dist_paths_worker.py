@@ -202,13 +202,14 @@ TESTS = {  # name: (world, environment, cases)
     "host_counted": (3, {"NL_BINNING": "1"}, _cases_host_counted()),
     "host_counted_crowd": (2, {"NL_BINNING": "1"}, [dict(scenario="crowd_arrives", dtype=dt, mask=mask, full=full, two_level=False)
                                                     for dt, mask, full in ((F32, 0, False), (F64, 7, True))]),
+    "profiled_rank": (2, None, [dict(scenario="profiled", key=("A", 30, F32, "uniform", 0), mask=0, full=False)]),
 }
 
 
 def lists_of_case(case):
     """Every (input key, mask, full list) a case builds: what the CPU test checks the expectations of."""
     s = case["scenario"]
-    if s == "plain":
+    if s in ("plain", "profiled"):
         return [(case["key"], case["mask"], case["full"])]
     if s == "empty_rank":
         base = ("A", 30, case["dtype"], "vacated", 0)
@@ -394,6 +395,32 @@ def scenario_empty_rank(R, case):
     R.check("owned and ghost counts after the move", changed)
 
 
+def scenario_profiled(R, case):
+    """Rank 0 alone profiles its last build, as bench.py does at world > 1 (nl_profile_last_build with the device-side
+    ghost counts: a.n = h->n, BuildArgs::dyn set): its rows, ghost counts and checksum stay the oracle's, its peer's are
+    untouched, and the next collective build is exact on both."""
+    key, mask, full = case["key"], case["mask"], case["full"]
+    what = f"{key} mask {mask} {'full' if full else 'half'}"
+    nl, dn = R.new_handle(key[0], key[2], mask, full)
+    scatter(dn, key)
+    me = build_pair(R, nl, dn, key, mask, full, what)
+    glob = get_list(key, mask, full)
+
+    def profile():
+        ms = nl.profile_last_build(reps=2)
+        assert len(ms) == 7 and all(np.isfinite(v) and v >= 0 for v in ms.values()) and ms["total"] > 0, ms
+
+    def record(stage):
+        cs = R.check(f"{what}: {stage}", check_build, nl, dn, me, glob, f"{what}: {stage}", None)
+        R.records.append((f"{what}: {stage}", dn.n_owned, cs, len(glob[0]), list_sum(key, mask, full)))
+
+    if R.rank == 0:  # (no collective call inside: the peer does not wait for it)
+        R.check(f"{what}: profile_last_build on rank 0", profile)
+    record("after rank 0 profiled")
+    R.build(dn, True, f"{what}: the build after profiling")
+    record("the build after profiling")
+
+
 def exact_rows(t, rows):
     """A buffer of exactly `rows` rows (its own allocation)."""
     return t[:rows].clone()
@@ -509,7 +536,7 @@ def scenario_renegotiation(R, case):
     R.check("4. handles that outlive their communicator", survivors)
 
 
-SCENARIOS = dict(plain=scenario_plain, empty_rank=scenario_empty_rank, rows_boundary=scenario_rows_boundary,
+SCENARIOS = dict(plain=scenario_plain, profiled=scenario_profiled, empty_rank=scenario_empty_rank, rows_boundary=scenario_rows_boundary,
                  crowd_arrives=scenario_crowd_arrives, renegotiation=scenario_renegotiation)
 
 

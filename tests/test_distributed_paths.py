@@ -179,3 +179,11 @@ def test_host_counted_path(name):
     on box B); with the crowd on box C (world 2) the capacity flags travel through that branch and a synchronous build
     renegotiates."""
     _run(name)
+
+
+@gpu
+def test_profiling_one_rank_of_a_distributed_build():
+    """World 2 on box A: after a synchronous and an asynchronous build rank 0 alone calls profile_last_build (what bench.py
+    does at world > 1), which plans and runs the build again with the ghost counts on the device; both ranks' rows, ghost
+    counts and checksums are still the oracle's, and so are those of the next collective build."""
+    _run("profiled_rank")

@@ -248,9 +248,18 @@ def test_host_known_reasons_force_a_build():
     nl.update(qd, sync=True)
     nl.update(qd, sync=True)
     assert nl.update_stats() == (2, 1)
+    two_pairs = np.array([[0, 1], [5, 2]], dtype=np.int32)
+    two_types = (np.arange(len(q)) % 2).astype(np.int32)
+    # every cause rule (a) of include/nl_hip.h names, each followed by an update that builds and one that does not
     setters = [lambda: nl.set_capacity(40_000_000), lambda: nl.set_offset_width(0), lambda: nl.set_periodic(False),
                lambda: nl.set_full_list(False), lambda: nl.set_skin(0.4), lambda: nl.Initialize(len(q)),
-               lambda: nl.MakeNeighList(qd, len(q))]
+               lambda: nl.MakeNeighList(qd, len(q)),
+               lambda: nl.set_periodic(axes="xy"), lambda: nl.set_periodic(False),
+               lambda: nl.set_pair_images(True), lambda: nl.set_pair_images(False),
+               lambda: nl.set_exclusions(two_pairs, len(q)), lambda: nl.clear_exclusions(),
+               lambda: nl.set_type_cutoffs(two_types, np.full((2, 2), rc)), lambda: nl.clear_type_cutoffs(),
+               lambda: nl.set_box(28.3, 28.0, 28.0), lambda: nl.set_box(*box),  # (8 cells a side either way)
+               lambda: nl.profile_last_build(reps=1), lambda: nl.profile_stages(qd, reps=1)]
     for k, setter in enumerate(setters):
         setter()
         nl.update(qd, sync=True)
