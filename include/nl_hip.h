@@ -815,6 +815,63 @@ int nl_sw_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, voi
 int nl_sw_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 int nl_sw_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 
+/* Per-particle charges: forces, per-particle energies and the 8 totals of E = sum_pairs [ phi_{t_i t_j}(r) + q_i q_j C(r) ]
+ * over the entries of the list of the last build (the filtered list where an exclusion or type table is set).  C(r) is any
+ * short-range electrostatic pair term the caller has sampled: the real-space part of Ewald / PME erfc(alpha r) / r, damped
+ * shifted force, Wolf, reaction field, Debye-Hueckel (md_neighbor_list_amd/coulomb.py samples them).  A pair table has one
+ * slot per pair of types, so it cannot carry a charge per particle; this consumer can.  The rule, both position types T, one
+ * rounding per operation, no contraction:
+ *   - Pair part.  phi is the handle's pair table (nl_set_pair_table), evaluated by exactly the rule stated there, slots and
+ *     all: fr_phi, pe_phi, in_phi.  It must be set (NL_ERR_STATE otherwise); a model without a pair part passes zeros, as for
+ *     nl_set_eam.
+ *   - Charge table.  One slot on a grid of its own, with the grid rule of nl_set_pair_table: D = (r_max_c^2 - r_min_c^2) /
+ *     (nknots - 1), x_k = r_min_c^2 + k D.  The caller passes C[k] = C(r) and K[k] = -C'(r) / r at r = sqrt(x_k), nknots
+ *     doubles each, finite; the Coulomb constant and the dielectric are folded in by the caller.  Device form: the knot
+ *     {K_k, dK_k, C_k, dC_k} in T, differences taken in double and rounded once, 0 at the last knot; x0_c = (T)(r_min_c^2),
+ *     xc_c = (T)(r_max_c^2), iD = (T)(1 / D).
+ *   - Charges.  charge_dev holds one T per row of q_dev, in its order; after a local-index slab build these are the n
+ *     positions of the build, ghosts included (the ghosts' charges arrive with the caller's halo, as their positions do).  It
+ *     is read, never copied, and is the caller's to keep valid; a caller who re-sorts permutes it with nl_resort like any
+ *     other array.  NULL: NL_ERR_ARG.  A NaN or infinite charge propagates by the arithmetic; nothing validates charges
+ *     (that would need a sync).
+ *   - Per entry (row i, partner j): d from the image rule of nl_lj_forces; r2 = dx dx + dy dy + dz dz as the pair table's
+ *     pair function writes it; qq = q_i q_j; in_c = r2 < xc_c && r2 > 0; s = (r2 - x0_c) iD, k = min((int)s, nknots - 2),
+ *     t = s - (T)k.  Where in_c: kc = K_k + t dK_k, cc = C_k + t dC_k, fc = qq kc, ec = qq cc; otherwise both are 0.  A pair
+ *     that is in_c with r2 < x0_c has no value: fc and ec are NaN whatever the charges (two neutral particles included), by
+ *     the deliberate rule of a pair below the pair table.  fr = fr_phi + fc, pe = pe_phi + ec, (fx, fy, fz) = fr d, the force
+ *     on i; in = in_phi || in_c.
+ *   - Everything else is nl_table_forces / nl_table_virial: the layouts of f_dev (n_rows x 4 of T: fx, fy, fz, pe_i) and
+ *     out_dev (8 doubles, n_in the pairs with `in`), the half list's reaction by atomics after zeroing and full rows written
+ *     once, the factor 1/2 of a full list in the totals, the ghost rules of local-index slab lists, which are accepted (there
+ *     only a one-type pair table is reachable), NaN on a non-zero status word, n == 0, the shared scratch of the totals with
+ *     its first-call rule, totals reproducible bit for bit, enqueue variants that copy nothing and can be captured, and
+ *     NL_ERR_STATE after a distributed build or a slab build made without nl_set_local_ids.
+ *   - Reach, at the calls: r_max of the pair table and r_max_c <= rc for the synchronous calls, <= rc - skin for the enqueue
+ *     calls; with a type table <= rc_ab (less the skin) for every rc_ab > 0.  Else NL_ERR_ARG.  A pair of types with
+ *     rc_ab = 0 has no entries and therefore no charge term either: a model whose charged types must always interact gives
+ *     every pair of them a cut-off.
+ *   - nl_set_coulomb_table: 2 <= nknots <= NL_TABLE_MAX_KNOTS, 0 < r_min < r_max, finite values, `which` == NL_COUL_LIST,
+ *     else NL_ERR_ARG and the old table is kept.  nknots == 0, or K_host and C_host both NULL, clears the table (one of them
+ *     alone NULL is NL_ERR_ARG).  Synchronous; the device buffer is kept where the new table fits; the list is not touched.
+ *     nl_get_coulomb_table: the scalars and whether the calls read both tables from LDS; NL_ERR_STATE while no table is set.
+ *     `which` names the table: NL_COUL_LIST is the term over the list; every other value is NL_ERR_ARG (a second table for the
+ *     pairs that nl_set_exclusions removed, Ewald's correction for bonded pairs, is not built: DESIGN.md section 8u).
+ *   - Kernels.  The persistent grid of the table kernels.  The pair table and the charge table both in LDS where together
+ *     they fit NL_TABLE_LDS_BYTES, else both from global memory.  NL_TABLE_LDS=0 in the environment of nl_set_coulomb_table
+ *     forces the global path.  Both paths compute the same bits.
+ * Tested contract (tests/test_coulomb.py): every component of every particle within COUL_C u S and the
+ * totals within COUL_CW u S of an O(N^2) float64 evaluation of the same rule, S the uncancelled sums including the
+ * conditioning of s on the rounding of r2 for both tables. */
+enum { NL_COUL_LIST = 0 };
+int nl_set_coulomb_table(nl_handle_t h, int which, int32_t nknots, double r_min, double r_max, const double* K_host,
+                         const double* C_host);
+int nl_get_coulomb_table(nl_handle_t h, int which, int32_t* nknots, double* r_min, double* r_max, int32_t* lds);
+int nl_coul_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, void* f_dev, void* stream);
+int nl_coul_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, void* f_dev, void* stream);
+int nl_coul_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, double* out_dev, void* stream);
+int nl_coul_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, double* out_dev,
+                           void* stream);
+
 /* The pair-distance histogram of the list, the counts behind a radial distribution function g(r): for everybody
  * (nl_pair_histogram) or per unordered pair of types (nl_pair_histogram_typed).  The rule:
  *   - Entries.  The sum runs over the entries (row i, partner j) of the list of the last build: the filtered list where an

@@ -275,6 +275,8 @@ struct nl_handle_s {
   // nl_set_sw (nl_sw.inc): the radial tables of a three-body potential, {G, dG, g, dg}, slot t_i ntypes + t_j, and behind them
   // in sw.tab [ntypes^3] knots {Lambda, -, cos0, -} of [t_i][t_j][t_k]; the pair part is tb
   TableSet sw;
+  // nl_set_coulomb_table (nl_coulomb.inc): the charge table, {K, dK, C, dC}, one slot; the pair part is tb
+  TableSet cl;
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -2025,4 +2027,5 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_table.inc"
 #include "nl_eam.inc"
 #include "nl_sw.inc"
+#include "nl_coulomb.inc"
 #include "nl_histogram.inc"

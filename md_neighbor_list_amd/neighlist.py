@@ -79,6 +79,7 @@ class NeighListGPU:
         if tilt is not None and any(float(t) != 0.0 for t in tilt):
             self.set_box(Lx, Ly, Lz, *(float(t) for t in tilt))
         self._q = None  # keeps the positions of an asynchronous build alive
+        self._charges = None  # set_charges
         self.skin = 0.0
 
     def __del__(self):
@@ -511,7 +512,7 @@ class NeighListGPU:
     def _consume(self, name, q, lj, wait, out, totals):
         """The consumers' call: the output (the ``(n_rows, 4)`` rows of the list's dtype, or the 8 float64 ``totals``), the
         stream, the pick of ``name`` or ``name``_enqueue and the call.  lj: (epsilon, sigma, rc_force) for the scalar
-        Lennard-Jones forms, () for every other consumer."""
+        Lennard-Jones forms, () for every other consumer; an argument that is a device pointer (the charges) is a c_void_p."""
         n = self._check_q(q, None)
         if n != self._n:
             raise ValueError("q must hold the particles the list was built from")
@@ -525,10 +526,11 @@ class NeighListGPU:
             if o.shape != (rows, 4) or o.dtype != self.dtype or not o.is_contiguous():
                 raise TypeError("out must be a contiguous (n_rows, 4) tensor of the list's dtype")
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if lj and lj[2] is None:
+        if len(lj) == 3 and lj[2] is None:
             lj = (lj[0], lj[1], self.search_length if wait else self.search_length - self.skin)
         name += "" if wait else "_enqueue"
-        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], *(float(v) for v in lj), o.data_ptr(), stream), name)
+        extra = (v if isinstance(v, C.c_void_p) else float(v) for v in lj)
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], *extra, o.data_ptr(), stream), name)
         return o
 
     def lj_virial(self, q, epsilon=1.0, sigma=1.0, rc_force=None, wait=True, out=None):
@@ -685,6 +687,79 @@ class NeighListGPU:
         ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, every pair and every triple once, n_in the pairs within the longer of
         the two ranges.  No atomics: bit for bit reproducible.  The first call allocates scratch: make it before a graph capture."""
         return self._consume("nl_sw_virial", q, (), wait, out, totals=True)
+
+    # ------------------------------------------------------------------ per-particle charges
+    def set_coulomb_table(self, K, C, r_min, r_max, excluded=False):
+        """The charge table of coul_forces and coul_virial (nl_set_coulomb_table): ``C = C(r)`` and ``K = -C'(r) / r`` at the
+        knots ``pair_table.knots(r_min, r_max, nknots)``, both ``(nknots,)``, the Coulomb constant folded in (the samplers of
+        ``md_neighbor_list_amd.coulomb`` make them).  The pair part is the table of set_pair_table, which must be set as well
+        (zeros for a model without one).  Synchronous; keeps its device buffer where the table fits.  ``excluded``: the table
+        of the pairs that set_exclusions removed, which this library does not have yet (ValueError)."""
+        import ctypes  # (C is the table here)
+
+        import numpy as np
+
+        if excluded:
+            raise ValueError("the excluded-pair term is not built: only the table over the list (excluded=False)")
+        K, C = (np.ascontiguousarray(np.asarray(m, dtype=np.float64)) for m in (K, C))
+        if K.shape != C.shape or K.ndim != 1:
+            raise TypeError("K and C must both be (nknots,)")
+        ptrs = [m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for m in (K, C)]
+        check(self._lib.nl_set_coulomb_table(self._h, 0, int(K.shape[0]), float(r_min), float(r_max), *ptrs), "nl_set_coulomb_table")
+
+    def clear_coulomb_table(self, excluded=False):
+        if excluded:
+            raise ValueError("the excluded-pair term is not built: only the table over the list (excluded=False)")
+        check(self._lib.nl_set_coulomb_table(self._h, 0, 0, 0.0, 0.0, None, None), "nl_set_coulomb_table")
+
+    def coulomb_table_info(self, excluded=False):
+        """``{"nknots", "r_min", "r_max", "lds"}`` of the charge table (nl_get_coulomb_table), or None without one.  lds: the
+        calls read the pair table and the charge table from LDS."""
+        if excluded:
+            raise ValueError("the excluded-pair term is not built: only the table over the list (excluded=False)")
+        nk, lds = C.c_int32(), C.c_int32()
+        lo, hi = C.c_double(), C.c_double()
+        code = self._lib.nl_get_coulomb_table(self._h, 0, C.byref(nk), C.byref(lo), C.byref(hi), C.byref(lds))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_coulomb_table")
+        return {"nknots": nk.value, "r_min": lo.value, "r_max": hi.value, "lds": bool(lds.value)}
+
+    def set_charges(self, t):
+        """The charges coul_forces and coul_virial read unless they are given others: a contiguous ``(n,)`` device tensor of
+        the handle's dtype, one charge per row of the positions (after a slab build under set_local_ids the ghosts'
+        included).  A reference is kept, nothing is copied: the tensor may be updated in place, and is permuted with
+        ``resort`` like any other per-particle array.  None forgets it."""
+        if t is not None:
+            self._check_charges(t)
+        self._charges = t
+
+    def _check_charges(self, t):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != self.dtype or t.dim() != 1
+                or not t.is_contiguous()):
+            raise TypeError("charges must be a contiguous (n,) device tensor of the list's dtype")
+
+    def _charge_ptr(self, charges):
+        t = self._charges if charges is None else charges
+        if t is None:
+            return C.c_void_p(None)  # (nl_coul_*: NL_ERR_ARG)
+        self._check_charges(t)
+        if t.shape[0] != self._n:
+            raise ValueError("charges must hold one value per particle of the list's build")
+        return C.c_void_p(t.data_ptr())
+
+    def coul_forces(self, q, wait=True, out=None, charges=None):
+        """table_forces with the charge term (nl_coul_forces; ``wait=False``: nl_coul_forces_enqueue):
+        ``(n, 4) = {fx, fy, fz, pe_i}`` of ``E = sum_pairs [phi(r) + q_i q_j C(r)]``, phi the table of set_pair_table, C the
+        table of set_coulomb_table, the charges those of set_charges or ``charges``.  Both r_max within the list's cut-off
+        (less the skin with ``wait=False``).  A pair closer than either r_min gives NaN to both its particles."""
+        return self._consume("nl_coul_forces", q, (self._charge_ptr(charges),), wait, out, totals=False)
+
+    def coul_virial(self, q, wait=True, out=None, charges=None):
+        """The totals that belong to coul_forces (nl_coul_virial; ``wait=False``: nl_coul_virial_enqueue):
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, n_in the pairs within the longer of the two ranges; the same for a
+        half and a full list, bit for bit reproducible.  The first call allocates scratch: make it before a graph capture."""
+        return self._consume("nl_coul_virial", q, (self._charge_ptr(charges),), wait, out, totals=True)
 
     def pair_histogram(self, q, r_max, nbins, typed=False, wait=True, out=None):
         """Pair-distance histogram of the list of the last build (nl_pair_histogram): every stored pair once, half or
