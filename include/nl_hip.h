@@ -854,8 +854,9 @@ int nl_sw_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, dou
  *     else NL_ERR_ARG and the old table is kept.  nknots == 0, or K_host and C_host both NULL, clears the table (one of them
  *     alone NULL is NL_ERR_ARG).  Synchronous; the device buffer is kept where the new table fits; the list is not touched.
  *     nl_get_coulomb_table: the scalars and whether the calls read both tables from LDS; NL_ERR_STATE while no table is set.
- *     `which` names the table: NL_COUL_LIST is the term over the list; every other value is NL_ERR_ARG (a second table for the
- *     pairs that nl_set_exclusions removed, Ewald's correction for bonded pairs, is not built: DESIGN.md section 8u).
+ *     `which` names the table: NL_COUL_LIST is the term over the list; every other value is NL_ERR_ARG (the term over the
+ *     pairs that nl_set_exclusions removed, Ewald's correction for bonded pairs, has a table and entry points of its own:
+ *     nl_set_coul_excl_table below).
  *   - Kernels.  The persistent grid of the table kernels.  The pair table and the charge table both in LDS where together
  *     they fit NL_TABLE_LDS_BYTES, else both from global memory.  NL_TABLE_LDS=0 in the environment of nl_set_coulomb_table
  *     forces the global path.  Both paths compute the same bits.
@@ -871,6 +872,58 @@ int nl_coul_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, c
 int nl_coul_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, double* out_dev, void* stream);
 int nl_coul_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, double* out_dev,
                            void* stream);
+
+/* The excluded-pair term of the charges: forces, per-particle energies and the 8 totals of E = sum q_i q_j C(r) over the
+ * pairs of the handle's exclusion table.  nl_set_exclusions takes the bonded pairs out of the list, but the reciprocal sum of
+ * Ewald / PME still contains them, so the real-space side owes -q_i q_j erf(alpha r) / r for each of them
+ * (md_neighbor_list_amd/coulomb.py ewald_excluded samples it; ewald_self is the self-energy).  nl_coul_forces followed by
+ * nl_coul_excl_forces with `add` on the same stream leaves the complete real-space force in one buffer.  The rule, both
+ * position types T, one rounding per operation, no contraction:
+ *   - Table.  One slot on a grid of its own, with the grid rule and the device form of nl_set_coulomb_table: the knot
+ *     {K_k, dK_k, C_k, dC_k} in T with C[k] = C(r), K[k] = -C'(r) / r at r = sqrt(x_k); x0 = (T)(r_min^2), xc = (T)(r_max^2),
+ *     iD = (T)(1 / D).  The sign belongs to the table (Ewald's is C = -prefactor erf(alpha r) / r).  No pair table is needed:
+ *     this term has no phi.
+ *   - Entries.  The sum runs over the handle's exclusion table as it is at the call: the symmetric, sorted, deduplicated CSR
+ *     of nl_get_exclusions, after any relabelling by nl_resort.  Row i holds each partner j once, and row j holds i.
+ *   - Per entry (row i, partner j): d = r_i - r_j from the image rule of nl_lj_forces with the box and mask of the last build
+ *     (folded with rint in z, y, x order with the tilts): the nearest image, which does not depend on the list -- the pairs are
+ *     not in it.  r2 = dx dx + dy dy + dz dz as nl_coul_forces writes it; qq = q_i q_j; s = (r2 - x0) iD,
+ *     k = min((int)s, nknots - 2), t = s - (T)k; fc = qq (K_k + t dK_k), ec = qq (C_k + t dC_k); the force on i is fc d.
+ *   - No cut-off.  An excluded pair is owed its term wherever it is, and the calls do not test any reach against rc or the
+ *     skin.  A pair with !(r2 >= x0 && r2 < xc) -- r2 == 0 and a NaN r2 included -- is NaN in fc and ec whatever the charges:
+ *     the deliberate rule of a pair below the pair table (a zero would be silently wrong physics).
+ *   - Forces.  f_dev is n x 4 of T, {fx, fy, fz, pe_i}, pe_i half the row's ec.  Every row is produced by one group of 8 lanes
+ *     and stored once.  add == 0: the row's four values are written (an empty row: zeros).  add != 0: they are added to what
+ *     f_dev holds, by one plain read-modify-write per row and no atomic.  The sums have one fixed order: lane g of the group
+ *     its entries g, g + 8, ... of the row, then the lanes g and g ^ 4, ^ 2, ^ 1; two calls give the same bits.
+ *   - Totals.  The 8 doubles of nl_lj_virial, every entry weighted 1/2 (exact), terms formed in T, converted and summed in
+ *     double in one fixed order; n_in is the number of distinct excluded pairs.  Any NaN entry makes all 8 values NaN.  They
+ *     use the scratch of nl_lj_virial with its first-call rule.
+ *   - State and ordering: those of nl_coul_forces / nl_coul_forces_enqueue, and: the last build must be a whole single-device
+ *     build whose ids are its rows -- slab builds (local-index ones included) and distributed builds are NL_ERR_STATE; no
+ *     exclusion table, or no table of this term: NL_ERR_STATE; an exclusion table whose n differs from the build's n (a global
+ *     table with n_ids > n, the only way to get there): NL_ERR_ARG; charge_dev == NULL: NL_ERR_ARG.  n == 0 (looked at before
+ *     the table's n): nothing is written and the totals are 8 zeros.  A non-zero status word in the enqueue variants: NaN rows
+ *     (with `add` as well) and 8 NaN totals.  The enqueue variants copy nothing from the host and can be captured; a caller
+ *     who captured them captures again after nl_set_exclusions*, which may move the table.
+ *   - nl_set_coul_excl_table: the arguments, the clearing rule and the buffer rule of nl_set_coulomb_table; NL_TABLE_LDS=0 in
+ *     its environment forces the global path.  nl_get_coul_excl_table: the scalars and whether the calls read the table from
+ *     LDS (it fits NL_TABLE_LDS_BYTES); NL_ERR_STATE while no table is set.
+ *   - Kernels.  A wave takes 8 consecutive rows, 8 lanes per row; blocks of 256 threads (32 rows) on persistent grids, the
+ *     totals' of min(ceil(n / 32), NL_COUL_EXCL_BLOCKS) blocks, each of which leaves one partial of 8 doubles.  Both table
+ *     paths compute the same bits.
+ * Tested contract (tests/test_coul_excl.py): every component of every particle within COULX_C u S and
+ * the totals within COULX_CW u S of a float64 loop over the table's pairs. */
+#define NL_COUL_EXCL_BLOCKS 256 /* most blocks of the totals of the excluded-pair term */
+int nl_set_coul_excl_table(nl_handle_t h, int32_t nknots, double r_min, double r_max, const double* K_host, const double* C_host);
+int nl_get_coul_excl_table(nl_handle_t h, int32_t* nknots, double* r_min, double* r_max, int32_t* lds);
+int nl_coul_excl_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, void* f_dev, int add,
+                        void* stream);
+int nl_coul_excl_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, void* f_dev, int add,
+                                void* stream);
+int nl_coul_excl_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, double* out_dev, void* stream);
+int nl_coul_excl_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, double* out_dev,
+                                void* stream);
 
 /* The pair-distance histogram of the list, the counts behind a radial distribution function g(r): for everybody
  * (nl_pair_histogram) or per unordered pair of types (nl_pair_histogram_typed).  The rule:

@@ -5,8 +5,10 @@ sampler returns ``(K, C)`` with ``C = C(r)`` and ``K = -C'(r) / r`` at the knots
 uniform in r^2, ready for ``NeighListGPU.set_coulomb_table``.  ``prefactor`` multiplies both: the Coulomb constant over the
 dielectric in the caller's units (1 in Gaussian / reduced units, 332.06371 kcal A / (mol e^2), 138.935458 kJ nm / (mol e^2)).
 
-What is not here is not a pair sum over the list: the reciprocal-space sum of Ewald / PME, the self-energy
-``-alpha / sqrt(pi) sum q_i^2``, the net-charge term, and the correction for the bonded pairs that nl_set_exclusions removed.
+The correction an Ewald / PME sum owes for the bonded pairs that nl_set_exclusions removed is a sum over the exclusion table
+with a table of its own (nl_set_coul_excl_table, ``NeighListGPU.set_excluded_coulomb_table``): ``ewald_excluded`` samples it, and
+``ewald_self`` is the self-energy ``-alpha / sqrt(pi) sum q_i^2``, a host scalar.  What is not here is no pair sum at all: the
+reciprocal-space sum of Ewald / PME and the net-charge term.
 """
 from __future__ import annotations
 
@@ -38,6 +40,22 @@ def ewald_real(alpha, r_min, r_max, nknots, prefactor=1.0):
     r = pair_table.knots(r_min, r_max, nknots)
     c, f = _damped(float(alpha), r)
     return _out(prefactor, f / r, c)
+
+
+def ewald_excluded(alpha, r_min, r_max, nknots, prefactor=1.0):
+    """The term of an excluded pair under Ewald / PME, whose reciprocal sum still contains it: C = -erf(alpha r) / r (the sign
+    belongs to the table), K = -C'(r) / r = 2 alpha / sqrt(pi) exp(-alpha^2 r^2) / r^2 - erf(alpha r) / r^3.  With ewald_real on
+    the same grid: ewald_real.C - ewald_excluded.C = prefactor / r."""
+    r = pair_table.knots(r_min, r_max, nknots)
+    a = float(alpha)
+    e = np.array([math.erf(a * v) for v in r])
+    return _out(prefactor, _TWO_OVER_SQRT_PI * a * np.exp(-(a * r) ** 2) / r ** 2 - e / r ** 3, -e / r)
+
+
+def ewald_self(alpha, charges, prefactor=1.0):
+    """The self-energy of Ewald / PME, ``-prefactor alpha / sqrt(pi) sum q_i^2``: a host scalar from a host array of charges."""
+    q = np.asarray(charges, dtype=np.float64)
+    return -float(prefactor) * float(alpha) / math.sqrt(math.pi) * float((q * q).sum())
 
 
 def wolf(alpha, r_cut, r_min, r_max, nknots, prefactor=1.0):

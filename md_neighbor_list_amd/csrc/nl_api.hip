@@ -277,6 +277,8 @@ struct nl_handle_s {
   TableSet sw;
   // nl_set_coulomb_table (nl_coulomb.inc): the charge table, {K, dK, C, dC}, one slot; the pair part is tb
   TableSet cl;
+  // nl_set_coul_excl_table (nl_coul_excl.inc): the table of the excluded-pair term, {K, dK, C, dC}, one slot, a grid of its own
+  TableSet cx;
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -2028,4 +2030,5 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_eam.inc"
 #include "nl_sw.inc"
 #include "nl_coulomb.inc"
+#include "nl_coul_excl.inc"
 #include "nl_histogram.inc"

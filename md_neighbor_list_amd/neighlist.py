@@ -509,10 +509,11 @@ class NeighListGPU:
         of the global result (a ghost partner receives no reaction: its owner evaluates the pair in its own row)."""
         return self._consume("nl_lj_forces", q, (epsilon, sigma, rc_force), wait, out, totals=False)
 
-    def _consume(self, name, q, lj, wait, out, totals):
+    def _consume(self, name, q, lj, wait, out, totals, tail=()):
         """The consumers' call: the output (the ``(n_rows, 4)`` rows of the list's dtype, or the 8 float64 ``totals``), the
         stream, the pick of ``name`` or ``name``_enqueue and the call.  lj: (epsilon, sigma, rc_force) for the scalar
-        Lennard-Jones forms, () for every other consumer; an argument that is a device pointer (the charges) is a c_void_p."""
+        Lennard-Jones forms, () for every other consumer; an argument that is a device pointer (the charges) is a c_void_p.
+        tail: integer arguments between the output and the stream (the ``add`` of coul_excl_forces)."""
         n = self._check_q(q, None)
         if n != self._n:
             raise ValueError("q must hold the particles the list was built from")
@@ -530,7 +531,7 @@ class NeighListGPU:
             lj = (lj[0], lj[1], self.search_length if wait else self.search_length - self.skin)
         name += "" if wait else "_enqueue"
         extra = (v if isinstance(v, C.c_void_p) else float(v) for v in lj)
-        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], *extra, o.data_ptr(), stream), name)
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], *extra, o.data_ptr(), *tail, stream), name)
         return o
 
     def lj_virial(self, q, epsilon=1.0, sigma=1.0, rc_force=None, wait=True, out=None):
@@ -694,13 +695,13 @@ class NeighListGPU:
         knots ``pair_table.knots(r_min, r_max, nknots)``, both ``(nknots,)``, the Coulomb constant folded in (the samplers of
         ``md_neighbor_list_amd.coulomb`` make them).  The pair part is the table of set_pair_table, which must be set as well
         (zeros for a model without one).  Synchronous; keeps its device buffer where the table fits.  ``excluded``: the table
-        of the pairs that set_exclusions removed, which this library does not have yet (ValueError)."""
+        of the pairs that set_exclusions removed is not set here but with set_excluded_coulomb_table (ValueError)."""
         import ctypes  # (C is the table here)
 
         import numpy as np
 
         if excluded:
-            raise ValueError("the excluded-pair term is not built: only the table over the list (excluded=False)")
+            raise ValueError("the excluded-pair term has methods of its own: set_excluded_coulomb_table, coul_excl_forces (excluded=False here)")
         K, C = (np.ascontiguousarray(np.asarray(m, dtype=np.float64)) for m in (K, C))
         if K.shape != C.shape or K.ndim != 1:
             raise TypeError("K and C must both be (nknots,)")
@@ -709,14 +710,14 @@ class NeighListGPU:
 
     def clear_coulomb_table(self, excluded=False):
         if excluded:
-            raise ValueError("the excluded-pair term is not built: only the table over the list (excluded=False)")
+            raise ValueError("the excluded-pair term has methods of its own: set_excluded_coulomb_table, coul_excl_forces (excluded=False here)")
         check(self._lib.nl_set_coulomb_table(self._h, 0, 0, 0.0, 0.0, None, None), "nl_set_coulomb_table")
 
     def coulomb_table_info(self, excluded=False):
         """``{"nknots", "r_min", "r_max", "lds"}`` of the charge table (nl_get_coulomb_table), or None without one.  lds: the
         calls read the pair table and the charge table from LDS."""
         if excluded:
-            raise ValueError("the excluded-pair term is not built: only the table over the list (excluded=False)")
+            raise ValueError("the excluded-pair term has methods of its own: set_excluded_coulomb_table, coul_excl_forces (excluded=False here)")
         nk, lds = C.c_int32(), C.c_int32()
         lo, hi = C.c_double(), C.c_double()
         code = self._lib.nl_get_coulomb_table(self._h, 0, C.byref(nk), C.byref(lo), C.byref(hi), C.byref(lds))
@@ -760,6 +761,52 @@ class NeighListGPU:
         ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, n_in the pairs within the longer of the two ranges; the same for a
         half and a full list, bit for bit reproducible.  The first call allocates scratch: make it before a graph capture."""
         return self._consume("nl_coul_virial", q, (self._charge_ptr(charges),), wait, out, totals=True)
+
+    # ------------------------------------------------------------------ the excluded-pair term of the charges
+    def set_excluded_coulomb_table(self, K, C, r_min, r_max):
+        """The table of coul_excl_forces and coul_excl_virial (nl_set_coul_excl_table): ``C = C(r)`` and ``K = -C'(r) / r`` at
+        the knots ``pair_table.knots(r_min, r_max, nknots)``, both ``(nknots,)``, sign and Coulomb constant folded in
+        (``coulomb.ewald_excluded`` makes Ewald's ``-erf(alpha r) / r``).  Every excluded pair must lie in [r_min, r_max): one
+        outside has no value and gives NaN.  Synchronous; keeps its device buffer where the table fits; no pair table needed."""
+        import ctypes  # (C is the table here)
+
+        import numpy as np
+
+        K, C = (np.ascontiguousarray(np.asarray(m, dtype=np.float64)) for m in (K, C))
+        if K.shape != C.shape or K.ndim != 1:
+            raise TypeError("K and C must both be (nknots,)")
+        ptrs = [m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for m in (K, C)]
+        check(self._lib.nl_set_coul_excl_table(self._h, int(K.shape[0]), float(r_min), float(r_max), *ptrs), "nl_set_coul_excl_table")
+
+    def clear_excluded_coulomb_table(self):
+        check(self._lib.nl_set_coul_excl_table(self._h, 0, 0.0, 0.0, None, None), "nl_set_coul_excl_table")
+
+    def excluded_coulomb_table_info(self):
+        """``{"nknots", "r_min", "r_max", "lds"}`` of the excluded-pair table (nl_get_coul_excl_table), or None without one.
+        lds: the calls read the table from LDS."""
+        nk, lds = C.c_int32(), C.c_int32()
+        lo, hi = C.c_double(), C.c_double()
+        code = self._lib.nl_get_coul_excl_table(self._h, C.byref(nk), C.byref(lo), C.byref(hi), C.byref(lds))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_coul_excl_table")
+        return {"nknots": nk.value, "r_min": lo.value, "r_max": hi.value, "lds": bool(lds.value)}
+
+    def coul_excl_forces(self, q, wait=True, out=None, charges=None, add=False):
+        """The excluded-pair term (nl_coul_excl_forces; ``wait=False``: nl_coul_excl_forces_enqueue):
+        ``(n, 4) = {fx, fy, fz, pe_i}`` of ``E = sum q_i q_j C(r)`` over the pairs of set_exclusions at their nearest image, C
+        the table of set_excluded_coulomb_table, the charges those of set_charges or ``charges``.  No cut-off.  ``add``: the
+        rows are added to ``out`` (required then) instead of written, so ``coul_excl_forces(q, out=coul_forces(q), add=True)``
+        is the complete real-space force.  Whole single-device builds only; no atomics, bit for bit reproducible."""
+        if add and out is None:
+            raise ValueError("add=True adds to out, which must be given")
+        return self._consume("nl_coul_excl_forces", q, (self._charge_ptr(charges),), wait, out, totals=False, tail=(1 if add else 0,))
+
+    def coul_excl_virial(self, q, wait=True, out=None, charges=None):
+        """The totals that belong to coul_excl_forces (nl_coul_excl_virial; ``wait=False``: nl_coul_excl_virial_enqueue):
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, every excluded pair once, n_in their number; 8 NaN where a pair
+        lies outside the table.  The first call allocates scratch (lj_virial's): make it before a graph capture."""
+        return self._consume("nl_coul_excl_virial", q, (self._charge_ptr(charges),), wait, out, totals=True)
 
     def pair_histogram(self, q, r_max, nbins, typed=False, wait=True, out=None):
         """Pair-distance histogram of the list of the last build (nl_pair_histogram): every stored pair once, half or
