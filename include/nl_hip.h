@@ -185,6 +185,13 @@ int nl_destroy(nl_handle_t h);
  * exchange) and nothing else: positions written on ANOTHER stream must be fenced by the caller.  sync != 0 waits for the build and returns its status; sync == 0 only
  * enqueues (the reference's timing loop, make_list.cu:124-127) and errors surface at the next nl_synchronize /
  * getter.  tblock_size and smem_hei of the reference select among its CUDA variants and have no counterpart.
+ * A pending build on another stream is waited for on the host before the new one is enqueued.
+ * Tested on a caller's non-blocking stream that a delay holds back, the positions written behind the delay (whatever the
+ * build issued on the null stream would read a decoy: the harness checks for every stream it holds that the null stream
+ * runs meanwhile; the handle's private stream or an earlier build's stream runs ahead only where the runtime gives it
+ * another hardware queue, which is not checked), on every search path, both waits, a grown list, a build that runs
+ * again and a second build on another stream; sync == 0 on a handle that has built before returns while the stream is
+ * still held: tests/test_caller_stream.py.
  * Tested against the oracle at the mesh sizes where the build changes its binning, its row tables are full and its
  * scans take more than 64 blocks (needles, plates, dilute cubes): tests/test_mesh_limits.py.
  * The cut-off decision itself is pinned down at the last bit -- pairs at rc (1 +- k ulp) in cell corners, on the fine rows'
@@ -318,7 +325,10 @@ int nl_synchronize(nl_handle_t h);
  *   growth) or that would wait for another stream is NL_ERR_STATE there.  Slab and distributed builds have no update.
  *   nl_get_update_stats: stats[0] = updates enqueued, stats[1] = builds they performed (device counters, including the
  *   replays of captured updates); waits for the device.
- * Tested on every search path, binning, offset width and list kind, skipped updates byte for byte: tests/test_update_paths.py. */
+ * Tested on every search path, binning, offset width and list kind, skipped updates byte for byte: tests/test_update_paths.py.
+ * Tested in stream order on a caller's non-blocking stream: five steps, each a copy of the positions and an update, enqueued
+ * behind one delay while the stream is held, as plain launches and from the handle's graph (captured on the handle's
+ * private stream, launched on the caller's): tests/test_caller_stream.py. */
 int nl_set_skin(nl_handle_t h, double skin);
 int nl_update_list(nl_handle_t h, const void* q_dev, int32_t q_stride, int32_t n, void* stream, int sync);
 int nl_get_update_stats(nl_handle_t h, int64_t stats[2]);
@@ -525,7 +535,13 @@ int nl_number_of_pairs(nl_handle_t h, int64_t* npairs);
  *   nl_resort: array[s] <- array[order[s]] in place for one per-particle array of elem_bytes (4, 8, 12, 16, 24 or 32)
  *     per particle: positions, velocities, ids, ... -- call it once per array, then rebuild: the new list is the list
  *     of the permuted particles (indices are the NEW positions in the arrays).  Enqueued on `stream`; single-device
- *     builds only.  Synchronises with the last build first. */
+ *     builds only.  Synchronises with the last build first (on the host: the permutation is that build's result; the
+ *     relabelling of an exclusion or type table runs on a private stream and is waited for), then gathers and copies back
+ *     on `stream`, ordered behind whatever wrote the array there.
+ *     Tested on a caller's held non-blocking stream, the arrays written behind the delay, followed by a rebuild on that
+ *     stream, with and without the tables: behind a synchronised build, where the calls only enqueue (the first re-sort
+ *     after a build relabels the tables and waits for the device; later ones do not), and behind an asynchronous build,
+ *     which is waited for: tests/test_caller_stream.py. */
 int nl_get_cell_order(nl_handle_t h, const int32_t** order_dev, int32_t* n);
 int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream);
 
@@ -546,7 +562,10 @@ int nl_resort(nl_handle_t h, void* array_dev, size_t elem_bytes, void* stream);
  * pairs further than 64 ulp (in r) from it.  After a NL_LIST_FULL build every row gathers its partners and
  * writes its force once; after a NL_LIST_HALF build every pair is evaluated once and the reaction is added to the
  * partner with floating-point atomics (f_dev is zeroed first).  Enqueued on `stream` (NULL = the null stream);
- * waits for the build first.
+ * waits for the build first -- on the host, whichever stream the build was enqueued on, so the call may be made on another
+ * stream than the build's.  Tested for every consumer (Lennard-Jones, pair table, EAM, Stillinger-Weber, Coulomb, the
+ * excluded-pair term, the histogram, nl_pair_vectors) from the null stream and from a second non-blocking stream behind an
+ * asynchronous build on a held stream: tests/test_caller_stream.py.
  * On a local-index slab list (nl_set_local_ids): f_dev is n_rows x 4, q_dev holds the n positions of the build.  Per entry
  * (row i owned, partner j; j is a ghost iff j >= n_rows): a full list is read as ever; in a half list an owned partner
  * receives the reaction, a ghost partner receives nothing -- its owner evaluates the same pair in its own row, so there are
@@ -557,7 +576,10 @@ int nl_lj_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsi
 /* nl_lj_forces without the wait: stream-ordered behind the last nl_update_list, which must have been enqueued on the same
  * stream (or behind a build that has been synchronised); a pending plain asynchronous build is NL_ERR_STATE.
  * rc_force <= rc - skin (what a list reused within the skin guarantees), else NL_ERR_ARG.  Where the build's status word
- * says the list is invalid the forces are NaN; the error itself surfaces at the next nl_synchronize. */
+ * says the list is invalid the forces are NaN; the error itself surfaces at the next nl_synchronize.
+ * Only enqueues: on a handle whose calls have all run once (nothing left to allocate) it returns while the stream is still
+ * held back.  Tested for every consumer's enqueue variants behind an update on a caller's held non-blocking stream, the
+ * positions and charges written behind the delay: tests/test_caller_stream.py. */
 int nl_lj_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double epsilon, double sigma, double rc_force,
                          void* f_dev, void* stream);
 /* Typed Lennard-Jones for a list built with a type table: epsilon, sigma and rc_force of a pair are [t_i][t_j] of
@@ -595,7 +617,9 @@ int nl_lj_forces_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_strid
  *   - Rows are dealt to one wave each over a grid of min(ceil(n / 4), NL_VIRIAL_BLOCKS) blocks of 4 waves; each block
  *     leaves one partial of 8 doubles in a scratch buffer of the handle, which a second kernel adds up.  The first call
  *     allocates that buffer: on a stream that is being captured it returns NL_ERR_STATE (call once before the capture).
- *     Calls on one handle share it, so they must be ordered against each other, as everything else on a handle.
+ *     Calls on one handle share it, so they must be ordered against each other, as everything else on a handle: two calls
+ *     of any totals on two streams need the caller's fence (an event recorded behind the first, waited for by the second
+ *     stream); the library adds none.  Tested fenced, two enqueue variants on two streams: tests/test_caller_stream.py.
  *   - The enqueue variants copy nothing from the host and can be captured, as nl_lj_forces_enqueue.
  *   - On a local-index slab list (nl_set_local_ids) the rows are the n_rows owned particles and every entry (row i owned,
  *     partner j; j is a ghost iff j >= n_rows) has a weight, applied in double: after a NL_LIST_FULL build 1/2 for every
