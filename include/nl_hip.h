@@ -949,6 +949,81 @@ int nl_coul_excl_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, cons
 int nl_coul_excl_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* charge_dev, double* out_dev,
                                 void* stream);
 
+/* The DPD pair thermostat: forces, per-particle energies and the 8 totals of
+ *   F_ij = -phi'(r) e_ij + [ -gamma w(r)^2 (e_ij . v_ij) + sigma w(r) xi_ij / sqrt(dt) ] e_ij
+ * over the entries of the list of the last build (LAMMPS pair_style dpd and dpd/tstat, HOOMD md.pair.DPD): dissipative
+ * particle dynamics proper where phi is a soft conservative table (md_neighbor_list_amd/dpd.py samples it), and the
+ * momentum-conserving, Galilean-invariant thermostat of any other tabulated potential.  The rule, both position types T, one
+ * rounding per operation, no contraction:
+ *   - Pair part.  phi is the handle's pair table (nl_set_pair_table), evaluated by exactly the rule stated there: fr_phi,
+ *     pe_phi, in_phi.  It must be set (NL_ERR_STATE otherwise); a pure thermostat passes zeros, as for nl_set_eam.
+ *   - Weight table.  One slot on a grid of its own, with the grid rule of nl_set_pair_table: D = (r_max^2 - r_min^2) /
+ *     (nknots - 1), x_k = r_min^2 + k D.  The caller passes A[k] = w(r) / r at r = sqrt(x_k), nknots finite doubles.  Device
+ *     form: the knot {A_k, dA_k, 0, 0} in T, dA_k = (T)(A[k+1] - A[k]), 0 at the last knot; x0_d = (T)(r_min^2), xc_d =
+ *     (T)(r_max^2), iD = (T)(1 / D).  No square root per pair: w e = (w / r) d and w^2 (e . v) e = (w / r)^2 (d . v) d; the
+ *     dissipative weight is the square of the interpolated A, so w_D = w_R^2 holds exactly, as the fluctuation-dissipation
+ *     relation asks.
+ *   - Parameters.  gamma_host and sigma_host: nslots = ntypes (ntypes + 1) / 2 doubles each, at slot(a, b) of
+ *     nl_pair_histogram_typed, finite and >= 0; dt > 0 and finite.  The device holds g = (T)gamma and sg = (T)(sigma /
+ *     sqrt(dt)) per slot, the quotient taken in double and rounded once.  sigma = sqrt(2 gamma kT) is the caller's choice
+ *     (dpd.sigma_for); sigma = 0 is pure friction.  ntypes = 1 works with or without a type table; ntypes > 1 needs a type
+ *     table of exactly that ntypes (NL_ERR_STATE without one, NL_ERR_ARG for another ntypes) and a pair table of 1 or ntypes
+ *     types: nl_set_eam's rules.
+ *   - Pair noise.  Integers only, the same for both T, all arithmetic modulo 2^64.  fin(z): z ^= z >> 30; z *=
+ *     0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.  Per call key = fin(fin(seed) + step), step =
+ *     *step_dev, read on the device by the kernel and never by the host.  Per entry (row i, partner j): lo = min(i, j), hi =
+ *     max(i, j) as unsigned 32-bit values, z = fin(key + ((uint64)lo << 32 | hi)), m = z >> 40 (24 bits), xi = (T)(2 m + 1 -
+ *     2^24) (T)(sqrt(3) / 2^24).  The integer is odd and below 2^24 in magnitude: exact in fp32, never 0, symmetric about 0;
+ *     xi is uniform with unit variance, which is sufficient for DPD (Groot & Warren 1997), and is the same number from both
+ *     rows of a full list, from a half list, in fp32 and in fp64.
+ *   - Per entry: d from the image rule of nl_lj_forces; r2 = dx dx + dy dy + dz dz as the pair table's pair function writes
+ *     it; in_d = r2 < xc_d && r2 > 0; s = (r2 - x0_d) iD, k = min((int)s, nknots - 2), t = s - (T)k, A = A_k + t dA_k;
+ *     dv = v_i - v_j per component, dot = (dx dvx + dy dvy) + dz dvz; fd = -((g (A A)) dot), fn = (sg A) xi; f_dpd = in_d ?
+ *     fd + fn : 0, selected, not multiplied.  fr = fr_phi + f_dpd, pe = pe_phi, (fx, fy, fz) = fr d, the force on i; in =
+ *     in_phi || in_d.  A pair that is in_d with r2 < x0_d has no value: fr and pe are NaN whatever gamma and sigma, by the
+ *     deliberate rule of a pair below the pair table.
+ *   - Symmetry.  The image and a - b are odd under the swap of the two particles; dot, r2, A and xi are even.  So after a full
+ *     build the two rows of a pair compute the same fr, bit for bit, and exactly opposite forces; the sums of the rows differ
+ *     only by their order.
+ *   - Arguments.  v_dev: n rows in the position type, v_stride 3 or 4, read and never copied.  step_dev: one 64-bit device
+ *     word, the caller's, which the caller advances in stream order (a captured step that increments it draws fresh noise at
+ *     every replay).  NULL for either, or another v_stride: NL_ERR_ARG.
+ *   - Everything else is nl_coul_forces / nl_coul_virial: the layouts of f_dev (n x 4 of T) and out_dev (8 doubles: W from
+ *     the whole fr, U = sum pe_phi, n_in the pairs with `in`), the half list's reaction by atomics after zeroing and full rows
+ *     written once, the factor 1/2 of a full list, NaN on a non-zero status word, n == 0, the shared scratch of the totals
+ *     with its first-call rule, enqueue variants that copy nothing and can be captured.  The totals are reproducible bit for
+ *     bit for the same positions, velocities and step.
+ *   - Reach, at the calls: r_max of both tables <= rc, <= rc - skin for the enqueue calls; with a type table <= rc_ab (less
+ *     the skin) for every rc_ab > 0.  Else NL_ERR_ARG.
+ *   - Lists served: whole single-device builds whose ids are their rows, half and full.  Lists of caller ids, distributed
+ *     builds and every slab build, local-index ones included, are NL_ERR_STATE: a crossing pair would be keyed by two different
+ *     local row pairs on its two ranks, and momentum conservation would be lost.  After nl_resort (positions and velocities
+ *     permuted alike) the rows, and hence the noise assigned to a physical pair, change; the statistics do not.
+ *   - nl_set_dpd: 2 <= nknots <= NL_TABLE_MAX_KNOTS, 0 < r_min < r_max, 1 <= ntypes <= NL_MAX_TYPES, values as above, else
+ *     NL_ERR_ARG and the old state is kept.  nknots == 0, or the three arrays all NULL, clears the state (some of them NULL
+ *     is NL_ERR_ARG).  Synchronous; the device buffer is kept where the new state fits, so a captured graph then reads a
+ *     changed gamma, sigma, dt or seed; the list is not touched.  nl_get_dpd: the scalars and whether the calls read their
+ *     tables from LDS; NL_ERR_STATE while nothing is set.
+ *   - Kernels.  The persistent grid of the table kernels.  The pair table, the weight table and the slot parameters in LDS
+ *     where together they fit NL_TABLE_LDS_BYTES, else all from global memory.  NL_TABLE_LDS=0 in the environment of
+ *     nl_set_dpd forces the global path.  Both paths compute the same bits.  The key is computed once per wave.
+ * Tested contract (tests/test_dpd.py): every component of every particle within DPD_C u S and the totals
+ * within DPD_CW u S of an O(N^2) float64 evaluation of the same rule, S the uncancelled sums including the conditioning of
+ * both table reads on the rounding of r2 and of dot on the rounding of dv; the integer m itself, recovered from the forces of
+ * isolated dimers. */
+int nl_set_dpd(nl_handle_t h, int32_t ntypes, int32_t nknots, double r_min, double r_max, const double* A_host,
+               const double* gamma_host, const double* sigma_host, double dt, uint64_t seed);
+int nl_get_dpd(nl_handle_t h, int32_t* ntypes, int32_t* nknots, double* r_min, double* r_max, double* dt, uint64_t* seed,
+               int32_t* lds);
+int nl_dpd_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* v_dev, int32_t v_stride,
+                  const uint64_t* step_dev, void* f_dev, void* stream);
+int nl_dpd_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* v_dev, int32_t v_stride,
+                          const uint64_t* step_dev, void* f_dev, void* stream);
+int nl_dpd_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* v_dev, int32_t v_stride,
+                  const uint64_t* step_dev, double* out_dev, void* stream);
+int nl_dpd_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, const void* v_dev, int32_t v_stride,
+                          const uint64_t* step_dev, double* out_dev, void* stream);
+
 /* The pair-distance histogram of the list, the counts behind a radial distribution function g(r): for everybody
  * (nl_pair_histogram) or per unordered pair of types (nl_pair_histogram_typed).  The rule:
  *   - Entries.  The sum runs over the entries (row i, partner j) of the list of the last build: the filtered list where an

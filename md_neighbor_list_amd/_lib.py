@@ -104,6 +104,13 @@ PROTOTYPES = {
     "nl_coul_excl_forces_enqueue": (C.c_int, [_P, _P, _I32, _P, _P, C.c_int, _P]),
     "nl_coul_excl_virial": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
     "nl_coul_excl_virial_enqueue": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
+    "nl_set_dpd": (C.c_int, [_P, _I32, _I32, _D, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D, C.c_uint64]),
+    "nl_get_dpd": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(C.c_uint64),
+                             C.POINTER(_I32)]),
+    "nl_dpd_forces": (C.c_int, [_P, _P, _I32, _P, _I32, _P, _P, _P]),
+    "nl_dpd_forces_enqueue": (C.c_int, [_P, _P, _I32, _P, _I32, _P, _P, _P]),
+    "nl_dpd_virial": (C.c_int, [_P, _P, _I32, _P, _I32, _P, _P, _P]),
+    "nl_dpd_virial_enqueue": (C.c_int, [_P, _P, _I32, _P, _I32, _P, _P, _P]),
     "nl_pair_histogram": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_enqueue": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_typed": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),

@@ -279,6 +279,12 @@ struct nl_handle_s {
   TableSet cl;
   // nl_set_coul_excl_table (nl_coul_excl.inc): the table of the excluded-pair term, {K, dK, C, dC}, one slot, a grid of its own
   TableSet cx;
+  // nl_set_dpd (nl_dpd.inc): the weight table of the DPD pair term, {A, dA, 0, 0}, one slot, a grid of its own (dp.ntypes: the
+  // slot parameters'), and behind it in dp.tab [dp_nslots] knots {g, 0, sg, 0} and one knot that holds fin(seed); the pair part is tb
+  TableSet dp;
+  int32_t dp_nslots = 0;
+  double dp_dt = 0;
+  uint64_t dp_seed = 0;
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -2031,4 +2037,5 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_sw.inc"
 #include "nl_coulomb.inc"
 #include "nl_coul_excl.inc"
+#include "nl_dpd.inc"
 #include "nl_histogram.inc"

@@ -512,7 +512,8 @@ class NeighListGPU:
     def _consume(self, name, q, lj, wait, out, totals, tail=()):
         """The consumers' call: the output (the ``(n_rows, 4)`` rows of the list's dtype, or the 8 float64 ``totals``), the
         stream, the pick of ``name`` or ``name``_enqueue and the call.  lj: (epsilon, sigma, rc_force) for the scalar
-        Lennard-Jones forms, () for every other consumer; an argument that is a device pointer (the charges) is a c_void_p.
+        Lennard-Jones forms, () for every other consumer; an argument that is a device pointer (the charges, the velocities)
+        is a c_void_p, a stride a c_int32.
         tail: integer arguments between the output and the stream (the ``add`` of coul_excl_forces)."""
         n = self._check_q(q, None)
         if n != self._n:
@@ -530,7 +531,7 @@ class NeighListGPU:
         if len(lj) == 3 and lj[2] is None:
             lj = (lj[0], lj[1], self.search_length if wait else self.search_length - self.skin)
         name += "" if wait else "_enqueue"
-        extra = (v if isinstance(v, C.c_void_p) else float(v) for v in lj)
+        extra = (v if isinstance(v, (C.c_void_p, C.c_int32)) else float(v) for v in lj)
         check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], *extra, o.data_ptr(), *tail, stream), name)
         return o
 
@@ -807,6 +808,85 @@ class NeighListGPU:
         ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, every excluded pair once, n_in their number; 8 NaN where a pair
         lies outside the table.  The first call allocates scratch (lj_virial's): make it before a graph capture."""
         return self._consume("nl_coul_excl_virial", q, (self._charge_ptr(charges),), wait, out, totals=True)
+
+    # ------------------------------------------------------------------ the DPD pair thermostat
+    def set_dpd(self, A, gamma, sigma, r_min, r_max, dt, seed=0):
+        """The weight table and the parameters of dpd_forces and dpd_virial (nl_set_dpd): ``A = w(r) / r`` at the knots
+        ``pair_table.knots(r_min, r_max, nknots)``, ``(nknots,)`` (``dpd.weight`` makes it); ``gamma`` and ``sigma`` scalars, or
+        ``(nslots,)`` with the entry ``rdf.slot(a, b, ntypes)`` per pair of types of set_type_cutoffs, ntypes taken from nslots
+        (``dpd.sigma_for(gamma, kT)`` is the sigma of a temperature); ``dt`` the time step the noise is scaled by, ``seed``
+        any 64-bit integer.  The pair part is the table of set_pair_table, which must be set as well (zeros for a pure
+        thermostat).  Synchronous; keeps its device buffer where the state fits, so a captured graph reads the new values."""
+        import numpy as np
+
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+        g, s = (np.ascontiguousarray(np.atleast_1d(np.asarray(m, dtype=np.float64))) for m in (gamma, sigma))
+        if A.ndim != 1 or g.ndim != 1 or g.shape != s.shape:
+            raise TypeError("A must be (nknots,), gamma and sigma scalars or both (nslots,)")
+        nslots = g.shape[0]
+        nt = int(round(((8 * nslots + 1) ** 0.5 - 1) / 2))
+        if nt * (nt + 1) // 2 != nslots:
+            raise TypeError(f"{nslots} slots are not ntypes (ntypes + 1) / 2 for any ntypes")
+        ptrs = [m.ctypes.data_as(C.POINTER(C.c_double)) for m in (A, g, s)]
+        check(self._lib.nl_set_dpd(self._h, nt, int(A.shape[0]), float(r_min), float(r_max), *ptrs, float(dt),
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF), "nl_set_dpd")
+
+    def clear_dpd(self):
+        check(self._lib.nl_set_dpd(self._h, 0, 0, 0.0, 0.0, None, None, None, 0.0, 0), "nl_set_dpd")
+
+    def dpd_info(self):
+        """``{"ntypes", "nknots", "r_min", "r_max", "dt", "seed", "lds"}`` of set_dpd (nl_get_dpd), or None while nothing is
+        set.  lds: the calls read the pair table, the weight table and the parameters from LDS."""
+        nt, nk, lds = C.c_int32(), C.c_int32(), C.c_int32()
+        lo, hi, dt, seed = C.c_double(), C.c_double(), C.c_double(), C.c_uint64()
+        code = self._lib.nl_get_dpd(self._h, C.byref(nt), C.byref(nk), C.byref(lo), C.byref(hi), C.byref(dt), C.byref(seed), C.byref(lds))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_dpd")
+        return {"ntypes": nt.value, "nknots": nk.value, "r_min": lo.value, "r_max": hi.value, "dt": dt.value, "seed": seed.value,
+                "lds": bool(lds.value)}
+
+    def _dpd_args(self, v, step, wait):
+        """(v pointer, v stride, step pointer) of the DPD calls and what keeps the step word alive.  v: ``(n, 3)`` or
+        ``(n, 4)`` of the list's dtype; step: a one-element int64 device tensor (the 64 bits are the counter), or, with
+        ``wait=True`` only, a Python int, which is copied to the device for the call."""
+        if v is None:
+            vp, vs = C.c_void_p(None), 3  # (nl_dpd_*: NL_ERR_ARG)
+        else:
+            if (not isinstance(v, torch.Tensor) or v.device.type != "cuda" or v.dtype != self.dtype or v.dim() != 2
+                    or not v.is_contiguous()):
+                raise TypeError("v must be a contiguous (n, 3) or (n, 4) device tensor of the list's dtype")
+            if v.shape[0] != self._n:
+                raise ValueError("v must hold one row per particle of the list's build")
+            vp, vs = C.c_void_p(v.data_ptr()), int(v.shape[1])
+        if step is None:
+            return (vp, C.c_int32(vs), C.c_void_p(None)), None
+        if not isinstance(step, torch.Tensor):
+            if not wait:
+                raise TypeError("with wait=False the step is a one-element int64 device tensor: nothing is copied from the host")
+            u = int(step) & 0xFFFFFFFFFFFFFFFF
+            step = torch.tensor([u - (1 << 64) if u >= (1 << 63) else u], dtype=torch.int64, device=self.device)
+        if step.device.type != "cuda" or step.dtype != torch.int64 or step.numel() != 1:
+            raise TypeError("step must be a one-element int64 device tensor")
+        return (vp, C.c_int32(vs), C.c_void_p(step.data_ptr())), step
+
+    def dpd_forces(self, q, v, step, wait=True, out=None):
+        """table_forces with the DPD pair term (nl_dpd_forces; ``wait=False``: nl_dpd_forces_enqueue):
+        ``(n, 4) = {fx, fy, fz, pe_i}`` of ``F_ij = fr_phi d + [-gamma w^2 (e . v_ij) + sigma w xi_ij / sqrt(dt)] e``, phi the
+        table of set_pair_table, the rest that of set_dpd, ``v`` the velocities and ``step`` the counter of the noise, read
+        on the device: the caller advances it in stream order, and the same step gives the same noise.  Whole single-device
+        builds only.  After ``resort`` (q and v permuted alike) a physical pair draws another number; the statistics stay."""
+        # (keep: the step word of a Python int, an allocation of this stream, which orders its reuse behind the kernel)
+        args, keep = self._dpd_args(v, step, wait)
+        return self._consume("nl_dpd_forces", q, args, wait, out, totals=False)
+
+    def dpd_virial(self, q, v, step, wait=True, out=None):
+        """The totals that belong to dpd_forces (nl_dpd_virial; ``wait=False``: nl_dpd_virial_enqueue):
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, W from the whole pair force, U of phi alone, n_in the pairs within
+        the longer of the two ranges; bit for bit reproducible for the same positions, velocities and step.  The first call
+        allocates scratch (lj_virial's): make it before a graph capture."""
+        args, keep = self._dpd_args(v, step, wait)
+        return self._consume("nl_dpd_virial", q, args, wait, out, totals=True)
 
     def pair_histogram(self, q, r_max, nbins, typed=False, wait=True, out=None):
         """Pair-distance histogram of the list of the last build (nl_pair_histogram): every stored pair once, half or

@@ -21,8 +21,13 @@ The rebuild trigger (--trigger):
 
 --pressure prints P = N kT / V + tr W / (3 V) at the end, W from nl_lj_virial on the loop's list (V: the whole box).
 
+--dpd GAMMA KT adds the DPD pair thermostat (nl_set_dpd over a pair table of zeros, weight 1 - r / rc): f = lj_forces +
+dpd_forces, the friction taken at the velocities of the force evaluation, sigma = sqrt(2 GAMMA KT).  The step word of the
+noise lives on the device and is advanced inside the step, so a captured step draws fresh noise at every replay.  The run
+then also prints the kinetic temperature, averaged over its second half, against KT, and the drift of the total momentum.
+
 usage: tools/md_loop.py [--cells 12] [--steps 400] [--dtype f64] [--trigger host|device] [--graph]
-                        [--periodic none|xyz|xy] [--pressure]
+                        [--periodic none|xyz|xy] [--pressure] [--dpd GAMMA KT]
 """
 import argparse
 import os
@@ -33,10 +38,11 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from md_neighbor_list_amd import NeighListGPU  # noqa: E402
+from md_neighbor_list_amd import NeighListGPU, dpd  # noqa: E402
 
 SORT_FREQ = 50
 SORT_CHECK = 50  # device trigger: steps between two looks at the build count (a host sync)
+DPD_R_MIN, DPD_KNOTS, DPD_SEED = 0.5, 512, 2024  # the weight table's grid (the LJ core keeps every pair beyond 0.5) and the seed
 
 
 def fcc_droplet(cells, a, box, dtype, seed=1):
@@ -68,7 +74,7 @@ def fcc_slab(cells, a, box, dtype, seed=1):
 
 
 class Simulation:
-    def __init__(self, q, v, box, rc=2.5, skin=0.4, dt=0.004, device="cuda", trigger="host", graph=False, periodic=""):
+    def __init__(self, q, v, box, rc=2.5, skin=0.4, dt=0.004, device="cuda", trigger="host", graph=False, periodic="", thermostat=None):
         if trigger not in ("host", "device") or (graph and trigger != "device"):
             raise ValueError("trigger is 'host' or 'device'; graph needs the device trigger")
         self.trigger, self.use_graph, self.graph, self.steps = trigger, graph, None, 0
@@ -86,15 +92,35 @@ class Simulation:
         self.nl.Initialize(len(q))
         self.builds = self.sorts = 0
         self.q_built = None
+        # thermostat: (gamma, kT) of the DPD pair term, over a pair table of zeros; ke_sum: sum of v^2 over the steps since
+        # it was last zeroed, kept on the device
+        self.thermostat = thermostat
+        self.ke_sum = torch.zeros((), dtype=torch.float64, device=device)
+        if thermostat is not None:
+            gamma, kT = thermostat
+            zeros = np.zeros(DPD_KNOTS)
+            self.nl.set_pair_table(zeros, zeros, DPD_R_MIN, rc)
+            self.nl.set_dpd(dpd.weight(DPD_R_MIN, rc, DPD_KNOTS), gamma, dpd.sigma_for(gamma, kT), DPD_R_MIN, rc, dt, DPD_SEED)
+            self.step_word = torch.zeros(1, dtype=torch.int64, device=device)
+            self.fd = torch.empty((len(q), 4), dtype=self.tdt, device=device)
         if trigger == "device":
             self.nl.set_skin(skin)
             self.nl.update(self.q, sync=True)
             self.sorted_at = 0  # build count at the last re-sort
             self.f = torch.empty((len(q), 4), dtype=self.tdt, device=device)
-            self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc, wait=False, out=self.f)
+            self.forces(wait=False)
             return
         self.rebuild()
-        self.f = self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc)
+        self.f = torch.empty((len(q), 4), dtype=self.tdt, device=device)
+        self.forces(wait=True)
+
+    def forces(self, wait):
+        """f = lj_forces, plus dpd_forces at the current velocities and step word, which is then advanced on the device."""
+        self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc, wait=wait, out=self.f)
+        if self.thermostat is not None:
+            self.nl.dpd_forces(self.q, self.v, self.step_word, wait=wait, out=self.fd)
+            self.f += self.fd
+            self.step_word += 1
 
     def rebuild(self):
         if self.builds and self.builds % SORT_FREQ == 0:
@@ -118,8 +144,9 @@ class Simulation:
         moved = d.square().sum(dim=1).max()
         if float(moved) > (0.5 * self.skin) ** 2:  # (one host sync per step: the rebuild decision)
             self.rebuild()
-        self.f = self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc)
+        self.forces(wait=True)
         self.v += 0.5 * dt * self.f[:, :3]
+        self.ke_sum += self.v.square().sum()
 
     def wrap(self):
         """Periodic axes: positions back into [0, L) (the list takes every pair at its minimum image)."""
@@ -132,8 +159,9 @@ class Simulation:
         self.q[:, :3] += dt * self.v
         self.wrap()
         self.nl.update(self.q)  # (the rebuild decision on the device, no host sync)
-        self.nl.lj_forces(self.q, 1.0, 1.0, rc_force=self.rc, wait=False, out=self.f)
+        self.forces(wait=False)
         self.v += 0.5 * dt * self.f[:, :3]
+        self.ke_sum += self.v.square().sum()
 
     def step_device(self):
         if self.steps and self.steps % SORT_CHECK == 0:
@@ -159,6 +187,15 @@ class Simulation:
     def build_count(self):
         return self.nl.update_stats()[1] if self.trigger == "device" else self.builds
 
+    def temperature_since(self, steps):
+        """The mean kinetic temperature sum v^2 / (3 N - 3) over the last `steps` steps; zeroes the sum (one host sync)."""
+        t = float(self.ke_sum) / (steps * (3 * len(self.q) - 3))
+        self.ke_sum.zero_()
+        return t
+
+    def momentum(self):
+        return self.v.to(torch.float64).sum(dim=0).cpu().numpy()
+
     def energy(self):
         return float(self.f[:, 3].sum() + 0.5 * self.v.square().sum())
 
@@ -180,22 +217,25 @@ def main():
     ap.add_argument("--periodic", default="none", choices=["none", "xyz", "xy"],
                     help="minimum image: none (a droplet in an open box), xyz (a crystal filling the box), xy (a film)")
     ap.add_argument("--pressure", action="store_true", help="print the pressure and the potential energy from nl_lj_virial")
+    ap.add_argument("--dpd", type=float, nargs=2, metavar=("GAMMA", "KT"), help="the DPD pair thermostat: friction and temperature")
     args = ap.parse_args()
     a, box = 1.56, 4.0 * args.cells
     dt_np = np.float32 if args.dtype == "f32" else np.float64
     if args.periodic == "none":
         q, v = fcc_droplet(args.cells, a, box, dt_np)
-        sim = Simulation(q, v, box, trigger=args.trigger, graph=args.graph)
+        sim = Simulation(q, v, box, trigger=args.trigger, graph=args.graph, thermostat=args.dpd)
     else:
         c = args.cells
         cells = (c, c, c) if args.periodic == "xyz" else (c, c, max(c // 2, 2))
         edges = (c * a, c * a, c * a if args.periodic == "xyz" else box)
         q, v = fcc_slab(cells, a, edges, dt_np)
-        sim = Simulation(q, v, edges, trigger=args.trigger, graph=args.graph, periodic=args.periodic)
-    e0 = sim.energy()
+        sim = Simulation(q, v, edges, trigger=args.trigger, graph=args.graph, periodic=args.periodic, thermostat=args.dpd)
+    e0, p0 = sim.energy(), sim.momentum()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for k in range(args.steps):
+        if args.dpd and k == args.steps // 2:
+            sim.temperature_since(max(k, 1))  # (the second half starts here)
         sim.step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -203,6 +243,10 @@ def main():
     print(f"N={len(q)} periodic={args.periodic} trigger={args.trigger}{'+graph' if args.graph else ''} steps={args.steps} builds={sim.build_count()} "
           f"re-sorts={sim.sorts} E0={e0:.6f} E1={e1:.6f} "
           f"drift={(e1 - e0) / abs(e0):.2e} {1e3 * dt / args.steps:.3f} ms/step")
+    if args.dpd:
+        t2 = sim.temperature_since(args.steps - args.steps // 2)
+        print(f"DPD gamma={args.dpd[0]:g} kT={args.dpd[1]:g}: kinetic temperature over the second half {t2:.4f} ({t2 / args.dpd[1]:.4f} kT); "
+              f"total momentum {np.abs(p0).max():.3e} -> {np.abs(sim.momentum()).max():.3e} (largest component)")
     if args.pressure:
         p, u = sim.pressure()
         print(f"P={p:.6f} U={u:.6f} (nl_lj_virial)")
