@@ -839,6 +839,97 @@ int nl_sw_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, voi
 int nl_sw_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 int nl_sw_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
 
+/* Tersoff-type bond-order potentials (LAMMPS pair_style tersoff, HOOMD md.many_body.Tersoff: silicon, germanium and carbon in
+ * the Tersoff 1988/89 forms, SiC, SiGe, GaN, BN, the Albe-Erhart parametrisations): forces, per-particle energies and the 8
+ * totals of
+ *   E = sum_pairs phi(r) + sum_i sum_{j != i} 1/2 b(zeta_ij) u_{t_i t_j}(r_ij),
+ *   zeta_ij = p_{t_i t_j}(r_ij) sum_{k != i, j} g_{t_i t_j t_k}(cos theta_jik) q_{t_i t_k}(r_ik),
+ * j, k the partners of the centre i in the list.  For Tersoff the caller samples phi = f_C A exp(-lambda_1 r) into the pair
+ * table, u = -f_C B exp(-lambda_2 r), q = f_C exp(-lambda_3 r), p = exp(lambda_3 r): the m = 1 form, whose exponential of
+ * r_ij - r_ik factorises (md_neighbor_list_amd/tersoff.py samples them).  The rule, for both position types T, with one rounding
+ * per operation, no contraction, and sqrt and / the correctly rounded IEEE operations:
+ *   - Pair part.  phi is the handle's pair table (nl_set_pair_table), evaluated by exactly the rule stated there: fr_phi,
+ *     pe_phi, in_phi.  It must be set (NL_ERR_STATE otherwise); a model without a pair part passes zeros.
+ *   - Radial tables u, q, p.  The knot format and the grid rule of nl_set_sw's g tables, one grid r_min_3, r_max_3, nknots for
+ *     all three: ntypes x ntypes slots each, slot a ntypes + b for centre type a and end type b (not necessarily symmetric).
+ *     The caller passes u[slot][k] = u(r) and U[slot][k] = -u'(r) / r at r = sqrt(x_k), finite, and q, Q, p, P alike.  One knot
+ *     index k and one t serve the three reads: v = v_k + t dv_k.  in_3 = r2 < xc_3 && r2 > 0; a partner that is in_3 with
+ *     r2 < x0_3 has no value: u = U = q = Q = p = P = NaN.  p and P may both be NULL (lambda_3 = 0): then p = 1 and P = 0 by
+ *     value and nothing is read (one of them NULL: NL_ERR_ARG).
+ *   - Angular function.  gamma, c2_over_d2 = c^2 / d^2, d2 = d^2 and hh = h: ntypes^3 doubles each, [a][b][c] with a the centre;
+ *     it need not be symmetric in (b, c).  The host forms gc = gamma c2_over_d2 in double; gamma, gc, d2, h are rounded to T
+ *     once.  With x = h - cs, x2 = x x, den = d2 + x2:
+ *       g = gamma + gc (x2 / den)          g' = dg/dcs = -((((gc + gc) d2) x) / (den den))
+ *     This is gamma (1 + c^2/d^2 - c^2 / (d^2 + (h - cos theta)^2)) rearranged: silicon has c^2/d^2 = 3.8e7, and in fp32 the
+ *     difference of two numbers of that size would leave g, which is of order 1, without a correct digit.
+ *   - Bond order.  beta and nn = n: ntypes^2 doubles each, [a][b], centre and end.  The device holds beta, n and
+ *     e2 = (T)(-1 / (2 n)), the quotient taken in double.  zeta <= 0: b = 1, b' = 0.  Otherwise (a NaN zeta included, which so
+ *     propagates)
+ *       t = beta zeta      tn = pow(t, n)      b = pow(1 + tn, e2)      b' = (((T)(-0.5) b) (tn / (1 + tn))) / zeta
+ *     The two pow calls (powf in fp32) are the only operations of the rule that are not one correctly rounded IEEE operation:
+ *     the tested bound assumes each within 2 ulp of the exact power (an assumption: DESIGN.md section 8y).
+ *   - Partners.  j and k range over the entries of row i of the list of the last build (the filtered list where an exclusion or
+ *     type table is set) that are in_3: an excluded partner, or one of a pair of types with rc_ab = 0, forms no bond and enters
+ *     no zeta.
+ *   - Per partner j of centre i, once: a = r_i - r_j from the image rule of nl_lj_forces, r2_a = ax ax + ay ay + az az;
+ *     ir_a = 1 / sqrt(r2_a), ir2_a = ir_a ir_a; u_j, U_j, q_j, Q_j, p_j, P_j from the slot (t_i, t_j).
+ *   - First pass, per ordered pair of partners (j, k), k != j, with b_vec, ir_b, q_k of k and the parameters of (t_i, t_j, t_k):
+ *       cs = (((ax bx + ay by) + az bz) ir_a) ir_b       g_jk as above       S_j = sum_k g_jk q_k  (a sum in T, no promised order)
+ *     Then zeta_j = p_j S_j, b_j and b'_j as above, e_j = b_j u_j, w_j = ((T)0.5 u_j) b'_j, wp_j = w_j p_j.
+ *   - Second pass, per ordered pair (j, k), k != j, g'_jk from the parameters of (t_i, t_j, t_k), g_kj and g'_kj from those of
+ *     (t_i, t_k, t_j), all at the same cs, every product and sum one operation in the order the brackets give:
+ *       cc = (wp_j g'_jk) q_k + (wp_k g'_kj) q_j       cb = cc (ir_a ir_b)       ca = cc (cs ir2_a) + (wp_k g_kj) Q_j
+ *     sa = sum_k ca, sb = sum_k (cb b_vec) (per component), sums in T in no promised order; then
+ *       rad = ((T)0.5 b_j) U_j + (w_j P_j) S_j       sat = sa + rad       F_j = sb - sat a
+ *     one product and one difference per component.  This is the force on the end j from the bonds of the centre i,
+ *       F_j = -(1/2 b_j U_j + w_j P_j S_j) a + sum_k [(w_j p_j g'_jk q_k + w_k p_k g'_kj q_j)(b_vec ir_a ir_b - cs a ir2_a) - w_k p_k g_kj Q_j a],
+ *     and the centre receives F_i = -(sum_j F_j), the sum over its partners in T, negated.
+ *   - f_dev is n x 4 of T: {fx, fy, fz, pe_i}.  It is zeroed by a kernel, then every centre i adds its own value {pair force of
+ *     its row + F_i, half its pair energies + (sum_j e_j) (T)0.25} -- each of the two a sum in T as nl_table_forces forms it,
+ *     then one addition -- and to each partner j {F_j, e_j (T)0.25}, by floating-point atomics.  So pe_i holds half the pair
+ *     energies and a quarter of e_j for each end of every ordered bond (the LAMMPS per-atom convention): sum pe_i = E.
+ *   - Totals, the 8 doubles of nl_lj_virial.  The pair part is nl_table_virial's, with in = in_phi || in_3 for n_in.  The bond
+ *     part adds, per centre i and partner j, W_cd -= a_c F_j,d for (c, d) = xx, yy, zz, xy, xz, yz -- the product in T, negated,
+ *     converted -- and U += e_j / 2, each ordered bond once (the kernel hands 2 x the W term and e_j, both exact in double, to
+ *     the factor 1/2 of a full list).  Summed in double in one fixed order, no atomic.
+ *   - Full lists only: after a NL_LIST_HALF build the four calls return NL_ERR_STATE.  Slab builds (local-index ones included)
+ *     and distributed builds: NL_ERR_STATE.
+ *   - At most NL_TERSOFF_MAX_NEAR partners in_3 per centre.  A centre with more has no value: NaN in all four columns of the
+ *     centre and of every partner of it that is in_3, and in all 8 totals.
+ *   - NaN otherwise: where the arithmetic above gives it.  A partner below r_min_3 makes the centre and all its in_3 partners
+ *     NaN (all four columns) and all 8 totals.  Unlike Stillinger-Weber a centre with a single partner still has a bond
+ *     (zeta = 0, b = 1), so a lone partner below r_min_3 is NaN too.
+ *   - Reproducibility.  The totals use no atomic and one fixed order: two nl_tersoff_virial calls on the same list and positions
+ *     give the same 8 doubles, bit for bit.  f_dev is reproducible only within the tested bound.
+ *   - Types, reach: nl_set_sw's rules, with ntypes <= NL_TERSOFF_MAX_TYPES.
+ *   - nl_set_tersoff: 2 <= nknots <= NL_TABLE_MAX_KNOTS, 0 < r_min_3 < r_max_3, 1 <= ntypes <= NL_TERSOFF_MAX_TYPES, every value
+ *     finite, d2 > 0, beta >= 0, n > 0, else NL_ERR_ARG and the old state is kept.  nknots == 0 or all arrays NULL clear it.
+ *     Synchronous; the device buffer is kept where the new tables fit; the list is not touched.  nl_get_tersoff: the scalars,
+ *     has_p: whether p is set, and lds: whether the forces and totals read their tables from LDS; NL_ERR_STATE while nothing
+ *     is set.
+ *   - Kernels.  The persistent grid of the table kernels, one wave per centre row, nl_sw_forces' walk and strip; then two
+ *     loops over the partners, the bond order between them.  The pair table and the radial tables are staged in LDS where
+ *     together with the block's copy of the parameters ((ntypes^3 + ntypes^2) x 4 sizeof(T) bytes, always in LDS) and strips
+ *     they fit NL_TABLE_LDS_BYTES, else both are read from global memory; NL_TABLE_LDS=0 in the environment of nl_set_tersoff
+ *     forces the global path.  Both paths compute the same totals bit for bit.
+ *   - Everything else (ordering, state, NaN on a non-zero status word, n == 0, the totals' scratch with its first-call rule, the
+ *     enqueue variants copy nothing and can be captured) is nl_table_forces' / nl_table_virial's.
+ * Out of scope: m = 3 with lambda_3 != 0, slab and distributed lists, more than 64 partners, the Tersoff-ZBL and tersoff/mod forms.
+ * Tested contract (tests/test_tersoff.py): every component of every particle within TERSOFF_C u S and the
+ * totals within TERSOFF_CW u S of an O(N m^2) float64 evaluation of the same rule (md_neighbor_list_amd.tersoff bond_energy), S
+ * the uncancelled sums including the conditioning of each table read on its r2 and of b and b' on zeta. */
+#define NL_TERSOFF_MAX_TYPES 4
+#define NL_TERSOFF_MAX_NEAR 64
+int nl_set_tersoff(nl_handle_t h, int32_t ntypes, int32_t nknots, double r_min_3, double r_max_3, const double* u_host,
+                   const double* U_host, const double* q_host, const double* Q_host, const double* p_host, const double* P_host,
+                   const double* gamma_host, const double* c2_over_d2_host, const double* d2_host, const double* h_host,
+                   const double* beta_host, const double* n_host);
+int nl_get_tersoff(nl_handle_t h, int32_t* ntypes, int32_t* nknots, double* r_min_3, double* r_max_3, int32_t* has_p, int32_t* lds);
+int nl_tersoff_forces(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_tersoff_forces_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, void* f_dev, void* stream);
+int nl_tersoff_virial(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+int nl_tersoff_virial_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double* out_dev, void* stream);
+
 /* Per-particle charges: forces, per-particle energies and the 8 totals of E = sum_pairs [ phi_{t_i t_j}(r) + q_i q_j C(r) ]
  * over the entries of the list of the last build (the filtered list where an exclusion or type table is set).  C(r) is any
  * short-range electrostatic pair term the caller has sampled: the real-space part of Ewald / PME erfc(alpha r) / r, damped

@@ -92,6 +92,12 @@ PROTOTYPES = {
     "nl_sw_forces_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_sw_virial": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_sw_virial_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_set_tersoff": (C.c_int, [_P, _I32, _I32, _D, _D] + [C.POINTER(_D)] * 12),
+    "nl_get_tersoff": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I32), C.POINTER(_I32)]),
+    "nl_tersoff_forces": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_tersoff_forces_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_tersoff_virial": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "nl_tersoff_virial_enqueue": (C.c_int, [_P, _P, _I32, _P, _P]),
     "nl_set_coulomb_table": (C.c_int, [_P, C.c_int, _I32, _D, _D, C.POINTER(_D), C.POINTER(_D)]),
     "nl_get_coulomb_table": (C.c_int, [_P, C.c_int, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I32)]),
     "nl_coul_forces": (C.c_int, [_P, _P, _I32, _P, _P, _P]),

@@ -275,6 +275,11 @@ struct nl_handle_s {
   // nl_set_sw (nl_sw.inc): the radial tables of a three-body potential, {G, dG, g, dg}, slot t_i ntypes + t_j, and behind them
   // in sw.tab [ntypes^3] knots {Lambda, -, cos0, -} of [t_i][t_j][t_k]; the pair part is tb
   TableSet sw;
+  // nl_set_tersoff (nl_tersoff.inc): the radial tables of a bond-order potential on one grid, {U, dU, u, du}, {Q, dQ, q, dq} and
+  // (tf_p) {P, dP, p, dp}, slot t_i ntypes + t_j each, and behind them in tf.tab [ntypes^3] {gamma, -, gc, -}, [ntypes^3]
+  // {d2, -, h, -}, [ntypes^2] {beta, -, n, -}, [ntypes^2] {e2, -, e2, -}; the pair part is tb
+  TableSet tf;
+  bool tf_p = false;
   // nl_set_coulomb_table (nl_coulomb.inc): the charge table, {K, dK, C, dC}, one slot; the pair part is tb
   TableSet cl;
   // nl_set_coul_excl_table (nl_coul_excl.inc): the table of the excluded-pair term, {K, dK, C, dC}, one slot, a grid of its own
@@ -2035,6 +2040,7 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_table.inc"
 #include "nl_eam.inc"
 #include "nl_sw.inc"
+#include "nl_tersoff.inc"
 #include "nl_coulomb.inc"
 #include "nl_coul_excl.inc"
 #include "nl_dpd.inc"

@@ -690,6 +690,57 @@ class NeighListGPU:
         the two ranges.  No atomics: bit for bit reproducible.  The first call allocates scratch: make it before a graph capture."""
         return self._consume("nl_sw_virial", q, (), wait, out, totals=True)
 
+    # ------------------------------------------------------------------ Tersoff bond-order potentials
+    def set_tersoff(self, u, U, q, Q, r_min, r_max, gamma, c2_over_d2, d2, h, beta, n, p=None, P=None):
+        """The radial tables and parameters of a bond-order potential (nl_set_tersoff); the repulsive part is the table of
+        set_pair_table, which must be set as well.  ``u, U = -u'/r``, ``q, Q`` and (optionally, lambda_3 != 0) ``p, P`` at the
+        knots ``pair_table.knots(r_min, r_max, nknots)`` (``tersoff.sample`` makes them from callables): ``(nknots,)`` for one
+        type, ``(ntypes^2, nknots)`` with row ``a ntypes + b`` for centre type a and end type b.  ``gamma, c2_over_d2, d2, h``:
+        ``(ntypes,) * 3`` as ``tersoff.angular`` returns them; ``beta, n``: ``(ntypes,) * 2`` as ``tersoff.bond_order`` returns
+        them (scalars for one type).  Synchronous; keeps its device buffer where the tables fit."""
+        import numpy as np
+
+        if (p is None) != (P is None):
+            raise TypeError("p and P are given together or not at all")
+        tabs = [np.ascontiguousarray(np.atleast_2d(np.asarray(m, dtype=np.float64))) for m in (u, U, q, Q) + (() if p is None else (p, P))]
+        ang = [np.ascontiguousarray(np.asarray(m, dtype=np.float64)).reshape(-1) for m in (gamma, c2_over_d2, d2, h)]
+        bo = [np.ascontiguousarray(np.asarray(m, dtype=np.float64)).reshape(-1) for m in (beta, n)]
+        nt = int(round(tabs[0].shape[0] ** 0.5))
+        if any(t.shape != tabs[0].shape or t.ndim != 2 for t in tabs) or nt * nt != tabs[0].shape[0] or \
+                any(a.shape != (nt ** 3,) for a in ang) or any(b.shape != (nt ** 2,) for b in bo):
+            raise TypeError("u, U, q, Q (p, P) must all be (ntypes^2, nknots), the angular arrays hold ntypes^3 values, beta and n ntypes^2")
+        ptr = lambda m: m.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        radial = [ptr(t) for t in tabs] + ([None, None] if p is None else [])
+        check(self._lib.nl_set_tersoff(self._h, nt, int(tabs[0].shape[1]), float(r_min), float(r_max), *radial, *(ptr(a) for a in ang),
+                                       *(ptr(b) for b in bo)), "nl_set_tersoff")
+
+    def clear_tersoff(self):
+        check(self._lib.nl_set_tersoff(self._h, 0, 0, 0.0, 0.0, *([None] * 12)), "nl_set_tersoff")
+
+    def get_tersoff(self):
+        """``{"ntypes", "nknots", "r_min", "r_max", "p", "lds"}`` of the tables set (nl_get_tersoff), or None without them.  p:
+        the p tables are set; lds: the forces and totals read the pair table and the radial tables from LDS."""
+        nt, nk, hp, lds = (C.c_int32() for _ in range(4))
+        lo, hi = C.c_double(), C.c_double()
+        code = self._lib.nl_get_tersoff(self._h, C.byref(nt), C.byref(nk), C.byref(lo), C.byref(hi), C.byref(hp), C.byref(lds))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_tersoff")
+        return {"ntypes": nt.value, "nknots": nk.value, "r_min": lo.value, "r_max": hi.value, "p": bool(hp.value), "lds": bool(lds.value)}
+
+    def tersoff_forces(self, q, wait=True, out=None):
+        """Tersoff forces and per-particle energies (nl_tersoff_forces; ``wait=False``: nl_tersoff_forces_enqueue):
+        ``(n, 4) = {fx, fy, fz, pe_i}``, pe_i = half the pair energies of i + a quarter of b u for each end of every ordered bond,
+        so that ``pe.sum()`` is the energy.  Full lists of whole builds only.  A centre with more than 64 partners within r_max
+        of the radial tables, or one closer than their r_min, gives NaN to itself and to those partners."""
+        return self._consume("nl_tersoff_forces", q, (), wait, out, totals=False)
+
+    def tersoff_virial(self, q, wait=True, out=None):
+        """The totals that belong to tersoff_forces (nl_tersoff_virial; ``wait=False``: nl_tersoff_virial_enqueue):
+        ``{W_xx, W_yy, W_zz, W_xy, W_xz, W_yz, U, n_in}``, n_in the pairs within the longer of the two ranges.  No atomics: bit
+        for bit reproducible.  The first call allocates scratch: make it before a graph capture."""
+        return self._consume("nl_tersoff_virial", q, (), wait, out, totals=True)
+
     # ------------------------------------------------------------------ per-particle charges
     def set_coulomb_table(self, K, C, r_min, r_max, excluded=False):
         """The charge table of coul_forces and coul_virial (nl_set_coulomb_table): ``C = C(r)`` and ``K = -C'(r) / r`` at the
