@@ -1168,6 +1168,64 @@ int nl_pair_histogram_typed(nl_handle_t h, const void* q_dev, int32_t q_stride, 
 int nl_pair_histogram_typed_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, int32_t nbins,
                                     uint64_t* hist_dev, void* stream);
 
+/* Steinhardt bond-orientational order parameters of every particle, from the list: q_l, the normalised third-order invariant
+ * w_l and their neighbour-averaged forms (Lechner and Dellago), for one degree l per call.  The rule:
+ *   - Neighbours.  The neighbours of a centre i are the entries j of row i of the list of the last build with 0 < r2 < X: the
+ *     filtered list where an exclusion or type table is set, so an excluded partner is no neighbour, and neither is a partner
+ *     of a type pair with rc_ab = 0 (the supported way to an order parameter over chosen species: give the pairs of types
+ *     that shall not count rc_ab = 0).  d = r_i - r_j at the image of nl_lj_forces (lj_image), r2 = (dx dx + dy dy) + dz dz in
+ *     the position type T, without FMA; X is the largest T <= r_max r_max taken in double (the rounding of the histogram's
+ *     edges).  N_b(i) is their number.
+ *   - The bond.  ir = 1 / sqrt(r2); u = (x, y, z) = ((-dx) ir, (-dy) ir, (-dz) ir), the unit vector from i to j.
+ *   - Y_lm(u) for m = 0 .. l, complex with the Condon-Shortley phase (scipy's sph_harm), without a trigonometric function:
+ *       c_0 = 1,  c_m = c_{m-1} (x + i y):  re' = re x - im y,  im' = re y + im x                     ((x + i y)^m)
+ *       P_m = S_m,  P_k = (A_km z) P_{k-1} - B_km P_{k-2}  for k = m + 1 .. l  (P_{m-1} = 0)          (degree recurrence)
+ *       Y_lm = (P_l re(c_m), P_l im(c_m))
+ *     with  A_km = sqrt((4 k^2 - 1) / (k^2 - m^2)),  B_km = A_km sqrt(((k - 1)^2 - m^2) / (4 (k - 1)^2 - 1))  and
+ *     S_m = (-1)^m sqrt((2 m + 1) / (4 pi) prod_{i = 1 .. m} (2 i - 1) / (2 i)),  formed in double on the host and rounded to T
+ *     once.  Every operation is + - x or a correctly rounded sqrt or division, one rounding each.  A bond along z (x = y = 0)
+ *     needs no special case: c_m = 0 exactly for m > 0.
+ *   - q_lm(i) = (sum over the neighbours of Y_lm) / (T)N_b, the sum taken lane by lane along the row and then across the
+ *     wave's lanes, real and imaginary part apart.  m < 0 follows from q_{l,-m} = (-1)^m conj(q_lm) and is not stored.
+ *   - s = |q_l0|^2 + 2 sum_{m>0} |q_lm|^2 (|q|^2 = re re + im im);  q_l = sqrt(c s) with c = 4 pi / (2 l + 1) rounded to T.
+ *   - w_l = (sum over m1, m2 = -l .. l with |m1 + m2| <= l of W[m1][m2] Re((q_lm1 q_lm2) q_lm3), m3 = -m1 - m2) / (s sqrt(s)),
+ *     (a b) = (a_r b_r - a_i b_i, a_r b_i + a_i b_r) and Re(p c) = p_r c_r - p_i c_i, W the caller's 3j table rounded to T.  Where
+ *     s = 0 (q_l = 0: an odd l at a centre of inversion) w_l is 0 / 0 = NaN.
+ *   - With average != 0:  qa_lm(i) = (q_lm(i) + sum over the neighbours k of q_lm(k)) / (T)(N_b(i) + 1), the sum as above and
+ *     taken first, over the same neighbours; the averaged q_l and w_l come from qa_lm by the same two formulas.
+ *   - NaN rule.  A centre with N_b = 0 has no value: NaN in all four columns and in its q_lm (0 / 0).  A particle without
+ *     neighbours is nobody's neighbour, so nothing spreads.  No clamp and no error word.
+ * nl_set_steinhardt: 1 <= l <= NL_STEIN_MAX_L, r_max > 0 and finite; w3j_host: (2 l + 1)^2 finite doubles,
+ * [m1 + l][m2 + l] = (l l l; m1 m2 -m1-m2) and 0 where |m1 + m2| > l, or NULL: no w_l, its columns are NaN.  Anything else is
+ * NL_ERR_ARG and keeps the old setting; l == 0 clears it.  Synchronous: the tables are rounded to T once and uploaded.  The
+ * list is not touched and nothing of a build changes: the next nl_update_list does not build because of it.
+ * nl_steinhardt / nl_steinhardt_enqueue: out_dev is n x 4 of T, {q_l, w_l, averaged q_l, averaged w_l}; with average == 0
+ * columns 2 and 3 are written as NaN ("not computed"), not left as they were.
+ *   - Lists served: NL_LIST_FULL lists of whole single-device builds.  A row must hold every neighbour of its centre, for its
+ *     own sum and again for the average, which needs q_lm of every partner.  A NL_LIST_HALF build, a slab build (a local-index
+ *     one included: the average needs the ghosts' q_lm) and a distributed build are NL_ERR_STATE, and so is a call without a
+ *     setting.
+ *   - Reach.  r_max <= rc, and with a type table r_max <= rc_ab for every pair of types with rc_ab > 0; the enqueue variant:
+ *     the same less the skin.  Else NL_ERR_ARG.
+ *   - Scratch: q_lm and N_b of every row, sized by n_max and l, allocated by the first call (NL_ERR_STATE inside a capture: make
+ *     one call before); allocated anew by the first call after an nl_initialize with another n_max or a setting with a
+ *     larger l than any before.
+ *   - Ordering, state, n == 0 (nothing is written) and capture: those of nl_table_forces and nl_table_forces_enqueue.  The
+ *     enqueue variant copies nothing from the host; where it finds a non-zero status word it writes NaN to all four columns
+ *     and to q_lm, and the error itself surfaces at the next nl_synchronize.
+ *   - Reproducible.  No kernel uses an atomic: two calls on the same list and positions write the same bytes to out_dev and
+ *     q_lm.  The order of a row's partners differs from build to build, so across builds only the tested bound holds.
+ * nl_steinhardt_get_qlm: the un-averaged q_lm of the last call, [n][l + 1][2] of T (m = 0 .. l, {re, im}), and N_b as int32 [n];
+ * l is that call's.  NL_ERR_STATE before a call.  Valid until the next call, setting with a larger l or nl_initialize.
+ * Tested contract (tests/test_steinhardt.py): N_b exact and every value within STEIN_C u S of an O(N^2)
+ * float64 evaluation with scipy-convention harmonics, S a first-order propagation of the roundings. */
+#define NL_STEIN_MAX_L 12
+int nl_set_steinhardt(nl_handle_t h, int32_t l, double r_max, const double* w3j_host);
+int nl_get_steinhardt(nl_handle_t h, int32_t* l, double* r_max, int32_t* has_w);
+int nl_steinhardt(nl_handle_t h, const void* q_dev, int32_t q_stride, int average, void* out_dev, void* stream);
+int nl_steinhardt_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, int average, void* out_dev, void* stream);
+int nl_steinhardt_get_qlm(nl_handle_t h, const void** qlm_dev, const int32_t** count_dev, int32_t* n, int32_t* l);
+
 /* ------------------------------------------------------------------------------------------- introspection */
 
 int nl_get_mesh(nl_handle_t h, int32_t mesh[3], int64_t* ncell);

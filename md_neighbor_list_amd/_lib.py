@@ -121,6 +121,11 @@ PROTOTYPES = {
     "nl_pair_histogram_enqueue": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_typed": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
     "nl_pair_histogram_typed_enqueue": (C.c_int, [_P, _P, _I32, _D, _I32, _P, _P]),
+    "nl_set_steinhardt": (C.c_int, [_P, _I32, _D, C.POINTER(_D)]),
+    "nl_get_steinhardt": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_I32)]),
+    "nl_steinhardt": (C.c_int, [_P, _P, _I32, C.c_int, _P, _P]),
+    "nl_steinhardt_enqueue": (C.c_int, [_P, _P, _I32, C.c_int, _P, _P]),
+    "nl_steinhardt_get_qlm": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I32), C.POINTER(_I32)]),
     "nl_set_pair_images": (C.c_int, [_P, C.c_int]),
     "nl_get_pair_images": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64)]),
     "nl_pair_vectors": (C.c_int, [_P, _P, _I32, _P, _P]),

@@ -290,6 +290,14 @@ struct nl_handle_s {
   int32_t dp_nslots = 0;
   double dp_dt = 0;
   uint64_t dp_seed = 0;
+  // nl_set_steinhardt (nl_steinhardt.inc): the degree, the neighbour range and whether a 3j table came with them (st_l == 0: not set)
+  int32_t st_l = 0;
+  double st_rmax = 0;
+  bool st_w = false;
+  DevBuf<void> st_tab;             // the recurrence table and the 3j table in T, sized for NL_STEIN_MAX_L, allocated by the first set
+  DevBuf<void> st_part;            // q_lm [n_max + 16][st_cap_l + 1][2] in T and N_b int32 [n_max + 16] of the last call, allocated by the first call
+  int32_t st_cap_l = 0, st_cap_n = 0;  // the l and the n_max st_part was sized for
+  int32_t st_last_l = 0;           // the l of the last call (the row length of q_lm); 0: no call yet
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -2045,3 +2053,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_coul_excl.inc"
 #include "nl_dpd.inc"
 #include "nl_histogram.inc"
+#include "nl_steinhardt.inc"

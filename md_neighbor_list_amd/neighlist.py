@@ -992,6 +992,64 @@ class NeighListGPU:
         return _rdf.rdf(h[_rdf.slot(a, b, nt)], r_max, Lx * Ly * Lz, int(counts[a]), None if a == b else int(counts[b]),
                         frames=frames)
 
+    # ------------------------------------------------------------------ Steinhardt order parameters
+    def set_steinhardt(self, l, r_max, w=True):
+        """The degree ``l`` (1 .. 12) and the neighbour range ``r_max`` of steinhardt() (nl_set_steinhardt).  ``w``: True
+        uploads ``steinhardt.wigner3j_table(l)`` for the w_l columns, False leaves them NaN, an array of ``(2 l + 1, 2 l + 1)``
+        is taken as the table.  Synchronous; keeps the list."""
+        import numpy as np
+
+        from . import steinhardt as _st
+
+        l = int(l)
+        if w is True:
+            w = _st.wigner3j_table(l) if 1 <= l <= _st.MAX_L else None
+        ptr = None
+        if w is not None and w is not False:
+            w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+            if w.shape != (2 * l + 1, 2 * l + 1):
+                raise TypeError("w must be (2 l + 1, 2 l + 1)")
+            ptr = w.ctypes.data_as(C.POINTER(C.c_double))
+        check(self._lib.nl_set_steinhardt(self._h, l, float(r_max), ptr), "nl_set_steinhardt")
+
+    def clear_steinhardt(self):
+        check(self._lib.nl_set_steinhardt(self._h, 0, 0.0, None), "nl_set_steinhardt")
+
+    def steinhardt_info(self):
+        """``{"l", "r_max", "w"}`` of the setting (nl_get_steinhardt), or None without one."""
+        l, w, r = C.c_int32(), C.c_int32(), C.c_double()
+        code = self._lib.nl_get_steinhardt(self._h, C.byref(l), C.byref(r), C.byref(w))
+        if code == _lib.NL_ERR_STATE:
+            return None
+        check(code, "nl_get_steinhardt")
+        return {"l": l.value, "r_max": r.value, "w": bool(w.value)}
+
+    def steinhardt(self, q, average=False, wait=True, out=None):
+        """Steinhardt order parameters of every particle over its neighbours within r_max (nl_steinhardt; ``wait=False``:
+        nl_steinhardt_enqueue): ``(n, 4) = {q_l, w_l, averaged q_l, averaged w_l}`` in the list's dtype, w_l normalised, the
+        averaged forms those of Lechner and Dellago (NaN unless ``average``).  A particle without a neighbour gives NaN.
+        Full lists of whole builds only.  The first call allocates scratch: make it before a graph capture."""
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        rows = self._n_rows
+        o = torch.empty((rows, 4), dtype=self.dtype, device=self.device) if out is None else out
+        if o.shape != (rows, 4) or o.dtype != self.dtype or not o.is_contiguous():
+            raise TypeError("out must be a contiguous (n_rows, 4) tensor of the list's dtype")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        name = "nl_steinhardt" + ("" if wait else "_enqueue")
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], 1 if average else 0, o.data_ptr(), stream), name)
+        return o
+
+    def steinhardt_qlm(self):
+        """``(qlm, count)`` of the last steinhardt() call (nl_steinhardt_get_qlm): the un-averaged q_lm as a complex
+        ``(n, l + 1)`` tensor (m = 0 .. l) and N_b as int32 ``(n,)``, copies taken on the current stream."""
+        p, c, n, l = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        check(self._lib.nl_steinhardt_get_qlm(self._h, C.byref(p), C.byref(c), C.byref(n), C.byref(l)), "nl_steinhardt_get_qlm")
+        ts = "<f4" if self.dtype == torch.float32 else "<f8"
+        qlm = _as_tensor(p.value, (n.value, l.value + 1, 2), ts, self, self.device).clone()
+        return torch.view_as_complex(qlm), _as_tensor(c.value, (n.value,), "<i4", self, self.device).clone()
+
     # ------------------------------------------------------------------ periodic re-sorting (SORT_FREQ)
     def cell_order(self):
         """order[s] = input index of the particle at cell-ordered slot s of the last build (nl_get_cell_order; the
