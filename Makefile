@@ -46,6 +46,14 @@ build/sanitize_test: $(SANSRC) $(CSRC)/nl_devbuf.hpp oracle/nl_oracle.c oracle/n
 	gcc $(SANFLAGS) -std=c11 -ffp-contract=off -fopenmp -Wall -Wextra -c -o build/san_oracle.o oracle/nl_oracle.c
 	$(CXX) $(SANFLAGS) -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I$(CSRC) -isystem $(ROCM)/include -o $@ $(SANSRC) $(CSRC)/nl_inputs.cpp build/san_oracle.o -fopenmp
 
+# The union-find of nl_clusters (nl_unionfind.hpp) with its host atomics policy under 16 std::threads and ThreadSanitizer: a
+# stand-alone program with its own main, apart from tests/sanitize (whose every source goes into build/sanitize_test).  CPU only.
+tsan: build/unionfind_check
+	./build/unionfind_check
+build/unionfind_check: tests/tsan/unionfind_check.cpp $(CSRC)/nl_unionfind.hpp
+	@mkdir -p build
+	$(CXX) -fsanitize=thread -fno-omit-frame-pointer -g -O1 -std=c++17 -Wall -Wextra -pthread -I$(CSRC) -o $@ tests/tsan/unionfind_check.cpp
+
 # ISA + resource usage of the kernels, for DESIGN.md / tuning
 asm:
 	@mkdir -p build
@@ -55,4 +63,4 @@ clean:
 	rm -f $(LIBDIR)/*.so tools/make_list build/*
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib inputs tools oracle asm asan clean
+.PHONY: all lib inputs tools oracle asm asan tsan clean

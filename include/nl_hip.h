@@ -1226,6 +1226,66 @@ int nl_steinhardt(nl_handle_t h, const void* q_dev, int32_t q_stride, int averag
 int nl_steinhardt_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, int average, void* out_dev, void* stream);
 int nl_steinhardt_get_qlm(nl_handle_t h, const void** qlm_dev, const int32_t** count_dev, int32_t* n, int32_t* l);
 
+/* Clusters from the list: the connected components of the graph whose vertices are the member particles and whose edges are the
+ * stored pairs within r_max (nl_clusters), and the count of solid-like bonds per particle after ten Wolde, Ruiz-Montero and
+ * Frenkel (nl_solid_bonds), which turns the q_lm of nl_steinhardt into a member array.  The pipeline of a nucleation analysis:
+ * nl_steinhardt -> nl_solid_bonds(threshold, count) -> nl_clusters(r_max, count, n_min, ...): a particle with at least n_min solid
+ * bonds is solid, and solid particles within r_max of each other share a cluster.  The rule of nl_clusters:
+ *   - Members.  member_dev == NULL: every particle.  Otherwise member_dev is int32 [n] on the device and particle i is a member
+ *     iff member_dev[i] >= min_member: a 0/1 mask (min_member 1), a type array, or the counts of nl_solid_bonds.
+ *   - Edges.  An entry (row i, partner j) of the list of the last build is an edge iff i and j are members and r2 < X: the
+ *     filtered list where an exclusion or type table is set, so an excluded pair is no edge.  d, r2 and X are those of
+ *     nl_pair_histogram: d = r_i - r_j at the image of nl_lj_forces (lj_image), r2 = (dx dx + dy dy) + dz dz in the position
+ *     type T without FMA, X the largest T <= r_max r_max taken in double.  A coincident pair (r2 == 0) is an edge, a NaN r2 is
+ *     none.  After a NL_LIST_FULL build only the entries with j > i are used.  The graph is undirected, and periodic images
+ *     connect as the list found them (a cluster may span the box).
+ *   - Output, all written and never added to.  labels_dev, int32 [n]: the smallest particle index of the member's cluster, -1 for
+ *     a non-member -- the canonical label, which makes the answer unique.  sizes_dev, int32 [n] or NULL: the number of members
+ *     of the member's cluster, 0 for a non-member.  summary_dev, int64 [4] or NULL: {members, clusters, size of the largest
+ *     cluster, its label}, ties to the smallest label; without a member the last two are 0 and -1.
+ *   - Lists served: NL_LIST_HALF and NL_LIST_FULL lists of whole single-device builds.  A cluster spans ranks: slab and
+ *     distributed builds, local-index ones included, are NL_ERR_STATE.
+ *   - Arguments and reach.  r_max > 0 and finite and labels_dev != NULL, else NL_ERR_ARG.  The reach is the untyped
+ *     histogram's: r_max <= rc, and with a type table r_max <= min_ab rc_ab; the enqueue variant: the same less the skin.
+ *   - Ordering, state and n == 0 (nothing is written): those of nl_pair_histogram, checks in the same order.  The enqueue
+ *     variant copies nothing from the host; where it finds a non-zero status word it writes -1 to every label, 0 to every size
+ *     and -1 to all four summary words, and the error itself surfaces at the next nl_synchronize.
+ *   - Scratch: none where sizes_dev is given or summary_dev is not (labels_dev is the parent array of the union-find, sizes_dev
+ *     its counters): such a call can be captured from the first one on.  A call with summary_dev and without sizes_dev keeps its
+ *     counters in int32 [n_max] of the handle, allocated by the first such call (NL_ERR_STATE inside a capture: make one call
+ *     before) and anew by the first after an nl_initialize with another n_max.
+ *   - Exact and reproducible.  A lock-free union-find that hooks the larger root under the smaller: the root of a finished
+ *     component is its smallest index whatever the schedule, and all counts are integer adds.  Two calls, two builds of one
+ *     input (the order of a row's partners differs from build to build) and a half and a full build write the same bytes.
+ *   - Five kernels of 256 threads in the stream's order: parent[i] = i; one wave per row over the histogram's walk, unite(i, j)
+ *     per edge; labels and counts; sizes and summary; the summary's last two words.  No kernel waits for another workgroup.
+ * The rule of nl_solid_bonds, in T, every operation + - x or a correctly rounded sqrt, no FMA:
+ *   - The q_lm are those the last nl_steinhardt or nl_steinhardt_enqueue call on this handle left (nl_steinhardt_get_qlm), l
+ *     that call's; the neighbour range r_max is the setting's.  Calling nl_steinhardt on this list and these positions first is
+ *     the caller's job: the call cannot tell q_lm of other positions from these.
+ *   - The neighbours of i are Steinhardt's: the entries j of row i with 0 < r2 < X.
+ *   - D_ij = (re_i0 re_j0 + im_i0 im_j0) + 2 S,  S = sum over m = 1 .. l in ascending order of (re_im re_jm + im_im im_jm), 2 S
+ *     taken as S + S;  s_i = D_ii.  The bond is solid iff D_ij > (T)threshold sqrt(s_i s_j); no division is taken.
+ *   - A NaN on either side makes the bond not solid: a particle with N_b = 0 has NaN q_lm and counts 0, and it is nobody's
+ *     neighbour anyway.
+ *   - count_dev, int32 [n]: the number of solid bonds of row i, written.
+ *   - Lists, reach, ordering, state and n == 0: those of nl_steinhardt (NL_LIST_FULL lists of whole builds; NL_ERR_STATE
+ *     without a setting) and, behind them, NL_ERR_STATE where nl_steinhardt_get_qlm would return it.  -1 < threshold < 1, else
+ *     NL_ERR_ARG.  The enqueue variant on a failed list writes -1 to every count.  No call allocates.
+ *   - One wave per row, one gathered read of 2 (l + 1) values per neighbour, one sum across the wave per row; no atomic, so two
+ *     calls write the same bytes.
+ * Edges along solid bonds only (freud's SolidLiquid) are another rule and not offered.
+ * Tested contract (tests/test_clusters.py): labels, sizes and summary equal, element for element, to an
+ * O(N^2) float64 pair search followed by scipy's connected_components wherever no pair lies within 2^-17 (fp32; 2^-46 fp64;
+ * relative, r^2) of X; the counts equal to a float64 evaluation wherever no bond lies within SOLID_C u S of the threshold, and
+ * bracketed by the sure and the banded bonds elsewhere. */
+int nl_clusters(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, const int32_t* member_dev, int32_t min_member,
+                int32_t* labels_dev, int32_t* sizes_dev, int64_t* summary_dev, void* stream);
+int nl_clusters_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double r_max, const int32_t* member_dev,
+                        int32_t min_member, int32_t* labels_dev, int32_t* sizes_dev, int64_t* summary_dev, void* stream);
+int nl_solid_bonds(nl_handle_t h, const void* q_dev, int32_t q_stride, double threshold, int32_t* count_dev, void* stream);
+int nl_solid_bonds_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double threshold, int32_t* count_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------- introspection */
 
 int nl_get_mesh(nl_handle_t h, int32_t mesh[3], int64_t* ncell);

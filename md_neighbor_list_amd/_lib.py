@@ -126,6 +126,10 @@ PROTOTYPES = {
     "nl_steinhardt": (C.c_int, [_P, _P, _I32, C.c_int, _P, _P]),
     "nl_steinhardt_enqueue": (C.c_int, [_P, _P, _I32, C.c_int, _P, _P]),
     "nl_steinhardt_get_qlm": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I32), C.POINTER(_I32)]),
+    "nl_clusters": (C.c_int, [_P, _P, _I32, _D, _P, _I32, _P, _P, _P, _P]),
+    "nl_clusters_enqueue": (C.c_int, [_P, _P, _I32, _D, _P, _I32, _P, _P, _P, _P]),
+    "nl_solid_bonds": (C.c_int, [_P, _P, _I32, _D, _P, _P]),
+    "nl_solid_bonds_enqueue": (C.c_int, [_P, _P, _I32, _D, _P, _P]),
     "nl_set_pair_images": (C.c_int, [_P, C.c_int]),
     "nl_get_pair_images": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64)]),
     "nl_pair_vectors": (C.c_int, [_P, _P, _I32, _P, _P]),

@@ -298,6 +298,9 @@ struct nl_handle_s {
   DevBuf<void> st_part;            // q_lm [n_max + 16][st_cap_l + 1][2] in T and N_b int32 [n_max + 16] of the last call, allocated by the first call
   int32_t st_cap_l = 0, st_cap_n = 0;  // the l and the n_max st_part was sized for
   int32_t st_last_l = 0;           // the l of the last call (the row length of q_lm); 0: no call yet
+  // nl_clusters (nl_cluster.inc): the counters of a call that asks for the summary without the sizes
+  DevBuf<int32_t> cc_part;         // int32 [n_max + 16], allocated by the first such call
+  int32_t cc_cap_n = 0;            // the n_max it was sized for
 
   // nl_set_pair_images (nl_images.inc): the periodic image of every entry, written by a stage at the end of the build
   bool pair_images = false;        // the flag: builds run the stage, the handle holds the two buffers below
@@ -2054,3 +2057,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_dpd.inc"
 #include "nl_histogram.inc"
 #include "nl_steinhardt.inc"
+#include "nl_cluster.inc"

@@ -1050,6 +1050,60 @@ class NeighListGPU:
         qlm = _as_tensor(p.value, (n.value, l.value + 1, 2), ts, self, self.device).clone()
         return torch.view_as_complex(qlm), _as_tensor(c.value, (n.value,), "<i4", self, self.device).clone()
 
+    # ------------------------------------------------------------------ clusters and solid-like particles
+    def _int32_rows(self, t, what, rows):
+        if not isinstance(t, torch.Tensor) or t.shape != (rows,) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device:
+            raise TypeError(f"{what} must be a contiguous int32 tensor of ({rows},) on the list's device")
+        return t
+
+    def clusters(self, q, r_max, member=None, min_member=1, wait=True, sizes=True, summary=True):
+        """Connected components of the graph of the stored pairs within ``r_max`` (nl_clusters; ``wait=False``:
+        nl_clusters_enqueue).  ``member``: None, everybody; or an int32 ``(n,)`` device tensor, particle i taking part iff
+        ``member[i] >= min_member`` -- a 0/1 mask, a type array, or the counts of solid_bonds().  Returns
+        ``(labels, sizes, summary)``: ``labels`` int32 ``(n,)``, the smallest particle index of the particle's cluster, -1 for
+        a non-member; ``sizes`` int32 ``(n,)``, the size of that cluster, 0 for a non-member; ``summary`` int64 ``(4,)`` =
+        ``{members, clusters, size of the largest cluster, its label}``.  ``sizes`` / ``summary``: True for a new tensor,
+        a tensor to write into, or False for None.  Exact, and the same bytes for every call, build and list kind; half
+        and full lists of whole builds.  With ``summary`` and without ``sizes`` the first call allocates scratch."""
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        rows = self._n_rows
+        labels = torch.empty(rows, dtype=torch.int32, device=self.device)
+        if sizes is True:
+            sizes = torch.empty(rows, dtype=torch.int32, device=self.device)
+        sizes = None if sizes is None or sizes is False else self._int32_rows(sizes, "sizes", rows)
+        if summary is True:
+            summary = torch.empty(4, dtype=torch.int64, device=self.device)
+        elif summary is None or summary is False:
+            summary = None
+        elif (not isinstance(summary, torch.Tensor) or summary.shape != (4,) or summary.dtype != torch.int64
+              or not summary.is_contiguous() or summary.device != self.device):
+            raise TypeError("summary must be a contiguous int64 tensor of (4,) on the list's device")
+        if member is not None:
+            self._int32_rows(member, "member", rows)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        name = "nl_clusters" + ("" if wait else "_enqueue")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], float(r_max), ptr(member), int(min_member),
+                                       labels.data_ptr(), ptr(sizes), ptr(summary), stream), name)
+        return labels, sizes, summary
+
+    def solid_bonds(self, q, threshold, wait=True, out=None):
+        """The number of solid-like bonds of every particle (nl_solid_bonds; ``wait=False``: nl_solid_bonds_enqueue), int32
+        ``(n,)``: the neighbours j of steinhardt()'s setting with ``q_l(i) . q_l(j) > threshold |q_l(i)| |q_l(j)|``, from
+        the q_lm the last steinhardt() call left -- call it on this list and these positions first.  Full lists of whole
+        builds only; allocates nothing."""
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        rows = self._n_rows
+        o = torch.empty(rows, dtype=torch.int32, device=self.device) if out is None else self._int32_rows(out, "out", rows)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        name = "nl_solid_bonds" + ("" if wait else "_enqueue")
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], float(threshold), o.data_ptr(), stream), name)
+        return o
+
     # ------------------------------------------------------------------ periodic re-sorting (SORT_FREQ)
     def cell_order(self):
         """order[s] = input index of the particle at cell-ordered slot s of the last build (nl_get_cell_order; the
