@@ -1286,6 +1286,68 @@ int nl_clusters_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, doub
 int nl_solid_bonds(nl_handle_t h, const void* q_dev, int32_t q_stride, double threshold, int32_t* count_dev, void* stream);
 int nl_solid_bonds_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, double threshold, int32_t* count_dev, void* stream);
 
+/* Common neighbour analysis from the list: the crystal structure every particle sits in -- fcc, hcp, bcc, icosahedral or none of
+ * them -- from the Honeycutt-Andersen / Faken-Jonsson signatures of its bonds, with one fixed cut-off (NL_CNA_FIXED) or with
+ * Stukowski's per-particle cut-off (NL_CNA_ADAPTIVE, the rule as OVITO applies it).  All common neighbours of i and k are
+ * neighbours of i, so a centre is analysed from its own row and the positions alone.  The rule, every operation in the position
+ * type T, + - x / or a correctly rounded sqrt, one rounding each, no FMA:
+ *   - Candidates.  The candidates of a centre i are the entries j of row i of the list of the last build with 0 < r2 < X: the
+ *     filtered list where an exclusion or type table is set.  d, r2 and X are Steinhardt's: d = r_i - r_j at the image of
+ *     nl_lj_forces (lj_image), r2 = (dx dx + dy dy) + dz dz, X the largest T <= r_max r_max taken in double.  N_b is their
+ *     number.  A centre with N_b > NL_CNA_MAX_NEAR has no analysis: type NL_CNA_OTHER, bit 0 of its flags set, and it is counted
+ *     in word 5 of the summary (and in word 0, as every OTHER).
+ *   - Ranking.  The candidates are ranked by (r2, j) ascending; j is unique in a row (a box has at least 3 cells on an axis).
+ *   - The set and its bond threshold Y.
+ *       FIXED:     the set is all candidates, Y = X.
+ *       ADAPTIVE:  K = 1.2071067811865475 (the double nearest (1 + sqrt 2) / 2) rounded to T.
+ *                  the 12-set: the ranks 0 .. 11;  S = sum of sqrt(r2) in rank order, starting from the term of rank 0, one
+ *                  rounding per add;  c = (S / (T)12) K;  Y = c c.
+ *                  the 14-set: the ranks 0 .. 13;  S = the terms sqrt(r2 / (T)0.75) of the ranks 0 .. 7, then sqrt(r2) of the ranks
+ *                  8 .. 13, in rank order;  c = (S / (T)14) K;  Y = c c.
+ *   - Bonds.  Two members k and m of the set are bonded iff e = d_k - d_m, taken per component, has (ex ex + ey ey) + ez ez < Y
+ *     (two coincident members are bonded).  These are distances between the images the list found: with at least 3 cells of
+ *     edge >= rc on every periodic axis and r_max <= rc, both members lie within r_max of the centre, so every other image of
+ *     the pair (k, m) is at least L - 2 r_max >= rc apart: beyond a fixed threshold (sqrt Y <= rc), and beyond an adaptive one
+ *     (sqrt Y <= K r_max) wherever r_max <= rc / K.  The rule is the one stated either way: the images the list found.
+ *   - The signature of the bond (i, k), k a member: C = the members bonded to k (the common neighbours); ncn = |C|; nb = the
+ *     number of bonded unordered pairs inside C; lc = the largest number of bonds in one connected component of the graph
+ *     (C, those bonds) -- OVITO's "maximum chain length".  Counted: n421 = the members with (ncn, nb, lc) = (4, 2, 1), n422 with
+ *     (4, 2, 2), n444 with (4, 4, 4), n555 with (5, 5, 5), n666 with (6, 6, 6).
+ *   - Type of a set.  12-signature types: FCC iff n421 == 12, else HCP iff n421 == 6 and n422 == 6, else ICO iff n555 == 12.
+ *     14-signature type: BCC iff n444 == 6 and n666 == 8.
+ *       FIXED:     the set is analysed whatever its size; the type is the 12-signature type where N_b == 12, the 14-signature
+ *                  type where N_b == 14, else OTHER.
+ *       ADAPTIVE:  N_b < 12: nothing is analysed, OTHER.  Else the 12-set is analysed; where it gives none of FCC, HCP, ICO and
+ *                  N_b >= 14 the 14-set is analysed and gives BCC or OTHER; otherwise OTHER.
+ *   - Outputs, all written and never added to.  type_dev, int32 [n].  counts_dev, int32 [n][8] or NULL: {N_b (exact, also where
+ *     it exceeds 64), size of the last set analysed (0 if none), n421, n422, n444, n555, n666 of that set (0 if none), flags}.
+ *     summary_dev, int64 [6] or NULL: {OTHER, FCC, HCP, BCC, ICO, overflowed centres}, zeroed by the call and added to with
+ *     integer atomics: exact, the histogram of type_dev.
+ *   - Lists served, reach, ordering, state and capture: those of nl_steinhardt and nl_steinhardt_enqueue, checks in the same
+ *     order.  NL_LIST_FULL lists of whole single-device builds; a NL_LIST_HALF build, a slab build (local-index ones included)
+ *     and a distributed build are NL_ERR_STATE.  r_max > 0 and finite, mode NL_CNA_FIXED or NL_CNA_ADAPTIVE, type_dev != NULL,
+ *     else NL_ERR_ARG; r_max <= rc, and with a type table r_max <= rc_ab for every pair of types with rc_ab > 0 (the enqueue
+ *     variant: the same less the skin), else NL_ERR_ARG.  n == 0: nothing is written.  The enqueue variant copies nothing from
+ *     the host; where it finds a non-zero status word it writes -1 to every type, every counts word and every summary word, and
+ *     the error itself surfaces at the next nl_synchronize.  The list is not touched: the next nl_update_list does not build
+ *     because of a call.
+ *   - No scratch on the handle and no setting: the first call can be captured.  No floating-point atomic: two calls on the same
+ *     list and positions write the same bytes.
+ *   - One kernel of 256 threads, one wave per centre (k_cna, nl_cna.inc), behind a one-block kernel that zeroes the summary.
+ * For the adaptive mode any r_max that holds at least 14 candidates of every particle of interest and at most 64 of any serves;
+ * the conventional fixed cut-offs are md_neighbor_list_amd.cna.default_r_max.  Diamond-structure CNA, per-bond signatures and
+ * more than 64 candidates are not offered.
+ * Tested contract (tests/test_cna.py): type and all eight counts words equal to an O(N^2) float64
+ * evaluation of this rule at every particle none of whose decisions lies within 2^-17 (fp32; 2^-46 fp64; relative, r^2) of its
+ * threshold; the summary equal to the histogram of the types at all particles. */
+enum { NL_CNA_OTHER = 0, NL_CNA_FCC = 1, NL_CNA_HCP = 2, NL_CNA_BCC = 3, NL_CNA_ICO = 4 }; /* OVITO's numbering */
+enum { NL_CNA_FIXED = 0, NL_CNA_ADAPTIVE = 1 };
+#define NL_CNA_MAX_NEAR 64
+int nl_cna(nl_handle_t h, const void* q_dev, int32_t q_stride, int mode, double r_max, int32_t* type_dev, int32_t* counts_dev,
+           int64_t* summary_dev, void* stream);
+int nl_cna_enqueue(nl_handle_t h, const void* q_dev, int32_t q_stride, int mode, double r_max, int32_t* type_dev,
+                   int32_t* counts_dev, int64_t* summary_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------- introspection */
 
 int nl_get_mesh(nl_handle_t h, int32_t mesh[3], int64_t* ncell);

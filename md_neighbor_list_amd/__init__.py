@@ -5,9 +5,9 @@ The product is libnl_hip.so (HIP kernels + C ABI, include/nl_hip.h).  This packa
 the multi-GPU domain decomposition over torch.distributed.  Importing the package does not load the library;
 constructing a builder does, and fails loudly if it has not been built.
 """
-from . import cluster, inputs  # noqa: F401
+from . import cluster, cna, inputs  # noqa: F401
 
-__all__ = ["NeighListGPU", "NLError", "cluster", "inputs"]
+__all__ = ["NeighListGPU", "NLError", "cluster", "cna", "inputs"]
 
 
 def __getattr__(name):

@@ -130,6 +130,8 @@ PROTOTYPES = {
     "nl_clusters_enqueue": (C.c_int, [_P, _P, _I32, _D, _P, _I32, _P, _P, _P, _P]),
     "nl_solid_bonds": (C.c_int, [_P, _P, _I32, _D, _P, _P]),
     "nl_solid_bonds_enqueue": (C.c_int, [_P, _P, _I32, _D, _P, _P]),
+    "nl_cna": (C.c_int, [_P, _P, _I32, C.c_int, _D, _P, _P, _P, _P]),
+    "nl_cna_enqueue": (C.c_int, [_P, _P, _I32, C.c_int, _D, _P, _P, _P, _P]),
     "nl_set_pair_images": (C.c_int, [_P, C.c_int]),
     "nl_get_pair_images": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64)]),
     "nl_pair_vectors": (C.c_int, [_P, _P, _I32, _P, _P]),

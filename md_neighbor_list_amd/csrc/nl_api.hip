@@ -2058,3 +2058,4 @@ int nl_device_synchronize(void) { return hipDeviceSynchronize() == hipSuccess ? 
 #include "nl_histogram.inc"
 #include "nl_steinhardt.inc"
 #include "nl_cluster.inc"
+#include "nl_cna.inc"

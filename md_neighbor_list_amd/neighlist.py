@@ -1104,6 +1104,41 @@ class NeighListGPU:
         check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], float(threshold), o.data_ptr(), stream), name)
         return o
 
+    # ------------------------------------------------------------------ common neighbour analysis
+    def cna(self, q, r_max, adaptive=True, counts=False, summary=True, wait=True):
+        """Common neighbour analysis of every particle over its candidates within ``r_max`` (nl_cna; ``wait=False``:
+        nl_cna_enqueue).  ``adaptive``: Stukowski's per-particle cut-off on the 12 and 14 nearest candidates (any ``r_max``
+        that holds at least 14 candidates of every particle and at most 64), else one fixed cut-off ``r_max``
+        (``cna.default_r_max``).  Returns ``(types, counts, summary)``: ``types`` int32 ``(n,)``, 0 other, 1 fcc, 2 hcp, 3 bcc,
+        4 icosahedral (``cna.NAMES``); ``counts`` int32 ``(n, 8)`` = ``{N_b, size of the set analysed, n421, n422, n444, n555,
+        n666, flags}``; ``summary`` int64 ``(6,)`` = the number of particles of each type and of centres with more than 64
+        candidates.  ``counts`` / ``summary``: True for a new tensor, a tensor to write into, or False for None.  Exact;
+        full lists of whole builds only; allocates nothing on the handle, so the first call can be captured."""
+        n = self._check_q(q, None)
+        if n != self._n:
+            raise ValueError("q must hold the particles the list was built from")
+        rows = self._n_rows
+        types = torch.empty(rows, dtype=torch.int32, device=self.device)
+
+        def out(t, shape, dtype, what):
+            if t is True:
+                return torch.empty(shape, dtype=dtype, device=self.device)
+            if t is None or t is False:
+                return None
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()
+                    or t.device != self.device):
+                raise TypeError(f"{what} must be a contiguous {dtype} tensor of {shape} on the list's device")
+            return t
+
+        counts = out(counts, (rows, 8), torch.int32, "counts")
+        summary = out(summary, (6,), torch.int64, "summary")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        name = "nl_cna" + ("" if wait else "_enqueue")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        check(getattr(self._lib, name)(self._h, q.data_ptr(), q.shape[1], 1 if adaptive else 0, float(r_max), types.data_ptr(),
+                                       ptr(counts), ptr(summary), stream), name)
+        return types, counts, summary
+
     # ------------------------------------------------------------------ periodic re-sorting (SORT_FREQ)
     def cell_order(self):
         """order[s] = input index of the particle at cell-ordered slot s of the last build (nl_get_cell_order; the
